@@ -1,6 +1,6 @@
 """Benchmark: SGLD steps/s of the tensor-GP sampler on kin40k (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--chains C] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] ...
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE config 3/4): kin40k — Ntrain = 10 000 rows (the reference's
@@ -12,8 +12,13 @@ the feature kernel and stays resident in HBM.  Each GPU runs C independent poste
 (seeds differ, phi shared — BASELINE config 4 has one chain per GPU; C chains per GPU is the
 same thing with the GPU filled).  A "step" is one SGLD step of one chain over one minibatch;
 value = chain-steps/s summed over all chains and GPUs (weak scaling: work per GPU fixed).
-After the timed region each GPU predicts the 30 000 test rows with its chains' final
-samples; ranks all-reduce (RCCL) the predictive mean and rank 0 reports the ensemble RMSE.
+A plain run sets up, warms up, times the K steps and prints the line of what those steps
+measured (value, ms_per_step, the roofline from their own events).  --dump-outputs DIR writes
+every chain's (w, U) after the last timed step as DIR/<name>.npy; the inputs and seeds are fixed,
+so two builds run with the same arguments can be compared array for array.
+With --full, after the timed region every chain finishes its epochs, each GPU predicts the 30 000
+test rows with its chains' samples, ranks all-reduce (RCCL) the predictive mean and rank 0 reports
+the ensemble RMSE, the single-chain pass and the CPU baselines in the same line.
 """
 import argparse
 import json
@@ -261,12 +266,32 @@ def max_over_ranks(dt, device=None):
     return float(t.item())
 
 
-def compose_line(v):
-    """The bench's JSON line (rank 0) from the measured values in namespace v.  Every N keeps the
-    same fields: cpu_baseline (rank 0's host cores), kernel_us per rank, the single-chain pass."""
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write every named array as DIR/<name>.npy in float64, at most ``limit``
+    bytes together.  Past the limit every array is cut to the same fraction of its elements, a
+    fixed seeded sample of its flat (C-order) elements in ascending index order, so two runs with
+    the same arguments write the same elements."""
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    room = limit - 256 * len(arrays)                     # the .npy headers
+    if total > room:
+        rng = np.random.default_rng(0)
+        for k in sorted(arrays):
+            a = arrays[k].ravel()
+            cnt = max(1, int(a.size * (room / total)))
+            arrays[k] = a[np.sort(rng.choice(a.size, cnt, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def headline(v):
+    """The fields of the JSON line (rank 0) that the timed steps alone give: what a plain run
+    prints.  ``--full`` adds the legs that take runs of their own (compose_line)."""
     a = v.args
-    pred_tfs = v.pred_flop / (v.pred_ms * 1e-3) / 1e12
-    gemm_tfs = v.pred_flop / (v.gemm_ms * 1e-3) / 1e12
     return {
         "metric": METRICS[a.workload],
         "value": v.value,
@@ -299,12 +324,22 @@ def compose_line(v):
                      "algorithmic_bytes_per_launch": v.bytes_launch,
                      "algorithmic_bytes_per_step": v.bytes_launch,
                      "steps_run_per_chain": v.steps_run}),
+        "timed_region_host_us": v.host_us,
+    }
+
+
+def compose_line(v):
+    """The ``--full`` JSON line (rank 0) from the measured values in namespace v: the headline
+    fields plus the legs measured after the timed region.  Every N keeps the same fields:
+    cpu_baseline (rank 0's host cores), kernel_us per rank, the single-chain pass."""
+    pred_tfs = v.pred_flop / (v.pred_ms * 1e-3) / 1e12
+    gemm_tfs = v.pred_flop / (v.gemm_ms * 1e-3) / 1e12
+    return dict(headline(v), **{
         "cpu_baseline": v.cpu,
         "test_rmse": v.quality["test_rmse"],
         "test_rmse_note": v.quality["note"],
         "quality": v.quality,
         "allreduce_ms": v.allreduce_ms,
-        "timed_region_host_us": v.host_us,
         "pred": {"samples": v.npred, "Ntest": v.Nte, "ms": v.pred_ms, "gemm_flop": v.pred_flop,
                  "achieved_tflops": pred_tfs, "peak_tflops": FP64_MFMA_PEAK_TFS,
                  "frac": pred_tfs / FP64_MFMA_PEAK_TFS,
@@ -317,7 +352,7 @@ def compose_line(v):
                  "final_state_ensemble_rmse": v.rmse_final},
         "single_chain": v.single,
         "single_chain_steps_per_s": v.single["steps_per_s"] if v.single else None,
-    }
+    })
 
 
 ML_CONFIG = dict(signal_var=0.8, sigma_u=0.1, sigma_w=1.0, m=100, epsw=1e-4, epsU=1e-6, a=0.5,
@@ -477,8 +512,17 @@ def movielens_main(args):
     # the parameter line of :743-752 (signal_var = σ_u = 0.5, σ_w = ‖w_init‖_F / r, burnin 15,
     # avg = true, param_seed 10) at r = 20, timed on the wall clock (whole sweeps, host
     # bookkeeping included), with the running-average test RMSE beside fullWresults.h5's (r = 15)
+    if args.dump_outputs:
+        # what the timed call returned: every fold's per-epoch RMSE curves and last stored sample
+        arrs = {}
+        for i, o in enumerate(outs, 1):
+            arrs.update({"fold%d_trainRMSE" % i: o[4], "fold%d_testRMSE" % i: o[5],
+                         "fold%d_w_last" % i: o[0][:, :, -1], "fold%d_U_last" % i: o[1][:, :, -1],
+                         "fold%d_V_last" % i: o[2][:, :, -1]})
+        dump_outputs(args.dump_outputs if world == 1
+                     else os.path.join(args.dump_outputs, "rank%d" % rank), arrs)
     gibbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         tr1, te1, ud1, md1, mu1, sd1 = folds[0]
         wg = np.random.default_rng(10).standard_normal((r, r))
         sw_g = math.sqrt((wg ** 2).sum()) / r
@@ -510,7 +554,7 @@ def movielens_main(args):
         gr["achieved"] = gr["flops_per_sweep"] / (1e-3 * gibbs["ms_per_sweep"]) / 1e12
         gr["frac"] = gr["achieved"] / gr["peak"]
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = movielens_cpu_baseline(folds, w0, cfg)
     if rank == 0:
         nb = -(-trs[0].shape[0] // cfg["m"])
@@ -616,6 +660,14 @@ def main():
     ap.add_argument("--no-single-chain", dest="single_chain", action="store_false",
                     help="skip the C=1 latency pass (one chain on one CU)")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the "
+                         "epochs to the converged test RMSE, the stacked-sample prediction and its "
+                         "all-reduce, the single-chain pass and the CPU baselines (movielens: the "
+                         "Gibbs leg and the CPU baseline); a plain run stops at the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left, every chain's (w, U) and status, as "
+                         "DIR/<name>.npy (float64, at most 64 MB together)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: re-run under torchrun before any HIP call in this process
@@ -655,7 +707,9 @@ def main():
     Z, b = G.feature_inputs(n, D, 17)                     # Gen-C seeded feature inputs
     tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     phi_tr = feature_device(tt(Xtr.T), tt(ls), sigma_rbf, scale, tt(Z.T), tt(b.T))
-    phi_te = feature_device(tt(Xte.T), tt(ls), sigma_rbf, scale, tt(Z.T), tt(b.T))
+    # the test rows' features feed only the prediction legs of --full
+    phi_te = (feature_device(tt(Xte.T), tt(ls), sigma_rbf, scale, tt(Z.T), tt(b.T))
+              if args.full else None)
     y_tr = tt(ytr)
     torch.cuda.synchronize()
 
@@ -766,6 +820,22 @@ def main():
     value = total_steps / dt
     ms_per_step = 1000.0 * dt / args.steps
 
+    if args.dump_outputs:
+        # what the last timed step left: every chain's current (w, U), gathered on the session
+        # stream, and its status; a bailed-out chain's state is undefined and is written as zeros
+        w_now = torch.empty((C, Q), dtype=torch.float64, device=dev)
+        U_now = torch.empty((C, n * r * D), dtype=torch.float64, device=dev)
+        sess.gather_state(0, C, w_now, U_now)
+        sess.sync()
+        st_now = np.array([sess.status(c) for c in range(C)], dtype=np.float64)
+        w_np, U_np = w_now.cpu().numpy(), U_now.cpu().numpy()
+        w_np[st_now != 0] = 0.0
+        U_np[st_now != 0] = 0.0
+        dump_outputs(args.dump_outputs if world == 1
+                     else os.path.join(args.dump_outputs, "rank%d" % rank),
+                     {"w": w_np, "U": U_np, "status": st_now})
+        del w_now, U_now
+
     if sw is not None:
         sw.close()
     k_us_ranks = gather_over_ranks(k_us, dev)
@@ -805,6 +875,23 @@ def main():
                     os.path.relpath(args.pmc, ROOT), key, ent.get("source", "untagged"))
         except Exception:
             traffic = None
+
+    import types
+    world_seen = dist.get_world_size() if world > 1 else 1
+    timed = dict(args=args, value=value, world=world, world_seen=world_seen, warm_ms=warm_ms,
+                 ms_per_step=ms_per_step, wdesc=wdesc, N=N, Nte=Nte, D=D, n=n, r=r, Q=Q, m=m, C=C,
+                 info=info, roof=roof, alive=alive, traffic=traffic, traffic_src=traffic_src,
+                 k_us=k_us, dataset=loader.__name__, k_us_ranks=k_us_ranks,
+                 bytes_launch=bytes_launch, host_us=host_us)
+    if not args.full:
+        # a plain run ends here: the line holds what the timed steps themselves measured
+        if rank == 0:
+            print(json.dumps(headline(types.SimpleNamespace(
+                steps_run=sess.steps_done + warm_steps, **timed))))
+        sess.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- quality leg (the metric's "+ test RMSE"): every chain finishes its epochs_total epochs
     # (kin40kExperiment.jl:74) and the ensemble prediction is the mean over every chain's last
@@ -916,19 +1003,12 @@ def main():
             cpu["minibatch_256"] = cpu_b256_baseline(phi_np, ytr, I, args, args.cpu_seconds)
 
     if rank == 0:
-        import types
-        world_seen = dist.get_world_size() if world > 1 else 1
         steps_run = sess.total_steps + warm_steps
         out = compose_line(types.SimpleNamespace(
-            args=args, value=value, world=world, world_seen=world_seen, warm_ms=warm_ms,
-            ms_per_step=ms_per_step, wdesc=wdesc, N=N, Nte=Nte, D=D, n=n, r=r, Q=Q, m=m, C=C,
-            info=info, roof=roof, alive=alive, traffic=traffic, traffic_src=traffic_src, k_us=k_us,
-            dataset=loader.__name__,
-            k_us_ranks=k_us_ranks, bytes_launch=bytes_launch, steps_run=steps_run, cpu=cpu,
+            steps_run=steps_run, cpu=cpu,
             quality=quality, allreduce_ms=allreduce_ms, npred=npred, pred_ms=pred_ms,
             pred_flop=pred_flop, gemm_ms=gemm_ms, vphase_ms=vphase_ms, rmse_final=rmse_final,
-            vphase_kernel=vphase_kernel, host_us=host_us,
-            single=single))
+            vphase_kernel=vphase_kernel, single=single, **timed))
         print(json.dumps(out))
     sess.close()
     if world > 1:
