@@ -805,7 +805,8 @@ extern "C" int gpt_sgld_session_stamps(gpt_sgld_session* s, int64_t nsteps, int6
 extern "C" int64_t gpt_sgld_timeline_slots(void) { return kTimeline; }
 
 // Test entry: expm of `count` row-major nn × nn host matrices on the device, by the wave engine's
-// register-blocked Padé (mode 0) or the grid engine's wave_expm (mode 1).
+// register-blocked Padé (modes 0 and 4) or the grid engine's wave_expm (modes 1 and 3); the
+// (mode, nn) pairs are listed at wv_expm_check_kernel (wave.hip).
 extern "C" int gpt_debug_expm(int32_t nn, int32_t count, int32_t mode, const double* A, double* E,
                               int32_t* bad) {
   if (count < 1 || !A || !E || !bad) { set_error("bad arguments"); return GPT_ERR_BAD_DIMS; }
@@ -817,7 +818,7 @@ extern "C" int gpt_debug_expm(int32_t nn, int32_t count, int32_t mode, const dou
   HIPCHK(hipMemcpy(dA.p, A, b, hipMemcpyHostToDevice));
   hipError_t e = launch_expm_check(nn, count, dA.as<double>(), dE.as<double>(), dB.as<int32_t>(),
                                    mode, nullptr);
-  if (e == hipErrorInvalidValue) { set_error("nn not instantiated"); return GPT_ERR_BAD_DIMS; }
+  if (e == hipErrorInvalidValue) { set_error("(mode, nn) not instantiated"); return GPT_ERR_BAD_DIMS; }
   HIPCHK(e);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(E, dE.p, b, hipMemcpyDeviceToHost));

@@ -944,8 +944,13 @@ __device__ bool wave_expm(double* S, long long* st = nullptr) {
     for (int i = 0; i < NN; ++i) cs += fabs(A[i * NN + lane]);
   }
   // a non-finite ‖A‖₁ (an Inf or NaN entry): the oracle's NaN result (Julia's expm! would throw at
-  // ceil(Int, log2(nA/5.4))), i.e. geod's bail-out; wave_max (fmax) alone would drop a NaN column
-  if (__any(!(cs <= 1.79769313486231570e308))) return true;
+  // ceil(Int, log2(nA/5.4))), i.e. geod's bail-out; wave_max (fmax) alone would drop a NaN column.
+  // The result block is NaN-filled like the oracle's, for the callers that ignore the flag.
+  if (__any(!(cs <= 1.79769313486231570e308))) {
+    for (int o = lane; o < q; o += 64) A2[o] = __builtin_nan("");
+    wave_sync();
+    return true;
+  }
   const double nA = wave_max(cs);
   int si = 0;
   if (nA <= 2.1) {

@@ -185,8 +185,13 @@ __device__ __forceinline__ bool wv_expm(double* S0, double* S1, double* S2, int 
     if (lane >= NN) cs = 0.0;
   }
   // a non-finite ‖A‖₁ (an Inf or NaN entry): the oracle's NaN result (Julia's expm! would throw at
-  // ceil(Int, log2(nA/5.4))), i.e. geod's bail-out; wave_max (fmax) alone would drop a NaN column
-  if (__any(!(cs <= 1.79769313486231570e308))) return true;
+  // ceil(Int, log2(nA/5.4))), i.e. geod's bail-out; wave_max (fmax) alone would drop a NaN column.
+  // The result slot is NaN-filled like the oracle's, for the callers that ignore the flag.
+  if (__any(!(cs <= 1.79769313486231570e308))) {
+    for (int o = lane; o < NN * NN; o += 64) S1[o] = __builtin_nan("");
+    wave_sync();
+    return true;
+  }
   const double nA = wave_max(cs);
   int si = 0;
   Blk<NN> U, V;
@@ -1167,13 +1172,20 @@ hipError_t launch_wave(const StepParams& P, const ChainDesc* chains, int nchains
 
 // ------------------------------------------------------------------------ expm unit check (tests)
 namespace gpt {
-// One wave per matrix: wv_expm (mode 0) or the grid engine's wave_expm (mode 1) of an NN × NN
-// row-major matrix; NaN flags in bad.  Mode 2 (timing, gpt_debug_expm_stamps): wv_expm as geod
-// calls it (three slots, the first NN/2 result columns) with s_memtime stamps per matrix in
-// st[4·m + 0..3]: entry, polynomial done, solve done, exit.
-template <int NN>
+// One wave per matrix: the expm of an NN × NN row-major matrix by the function MODE names, NaN
+// flags in bad.  The kernel stages the matrix into LDS, calls the function and copies its result
+// slot out; it adds no logic of its own.
+//   0  wv_expm<NN>, every column                          NN in {6,8,10,12,15,16,20,24,30,32,40}
+//   1  wave_expm<NN> (grid, chain, TGP, MovieLens)        every production NN (r and 2r)
+//   2  timing (gpt_debug_expm_stamps): wv_expm as geod calls it (three slots, the first NN/2
+//      result columns) with s_memtime stamps per matrix in st[4·m + 0..3]: entry, polynomial
+//      done, solve done, exit                             NN in {12,16,20,24,30,32,40}
+//   3  wave_expm<NN, false> (the LDS GEPP of the 1024-thread kernels)          NN = 40
+//   4  wv_expm<NN> with ncols = NN/2, as geod calls it; the whole slot is copied out and
+//      columns [0, NN/2) are the result                   NN in {12,16,20,24,30,32,40}
+template <int NN, int MODE>
 __global__ __launch_bounds__(64) void wv_expm_check_kernel(const double* A, double* E, int32_t* bad,
-                                                           int mode, long long* st) {
+                                                           long long* st) {
   extern __shared__ __attribute__((aligned(16))) double wv_sm[];
   const int lane = lane_id();
   const double* a = A + (size_t)blockIdx.x * NN * NN;
@@ -1181,38 +1193,52 @@ __global__ __launch_bounds__(64) void wv_expm_check_kernel(const double* A, doub
   for (int o = lane; o < NN * NN; o += 64) S0[o] = a[o];
   wave_sync();
   bool b;
-  const double* res;
-  long long* sm = st ? st + 4 * (size_t)blockIdx.x : nullptr;
-  if (sm && lane == 0) sm[0] = (long long)__builtin_amdgcn_s_memtime();
-  if (mode == 2) {
+  const double* res = S0 + NN * NN;
+  if constexpr (MODE == 2) {
+    long long* sm = st ? st + 4 * (size_t)blockIdx.x : nullptr;
+    if (sm && lane == 0) sm[0] = (long long)__builtin_amdgcn_s_memtime();
     b = wv_expm<NN>(S0, S0 + NN * NN, S0 + 2 * NN * NN, lane, sm ? sm + 1 : nullptr, NN / 2);
     if (sm && lane == 0) sm[3] = (long long)__builtin_amdgcn_s_memtime();
-    res = S0 + NN * NN;
-  } else if (mode == 0) {
+  } else if constexpr (MODE == 0) {
     b = wv_expm<NN>(S0, S0 + NN * NN, S0 + 2 * NN * NN, lane);
-    res = S0 + NN * NN;
+  } else if constexpr (MODE == 4) {
+    b = wv_expm<NN>(S0, S0 + NN * NN, S0 + 2 * NN * NN, lane, nullptr, NN / 2);
+  } else if constexpr (MODE == 3) {
+    b = wave_expm<NN, false>(S0);
   } else {
     b = wave_expm<NN>(S0);
-    res = S0 + NN * NN;
   }
   wave_sync();
   for (int o = lane; o < NN * NN; o += 64) E[(size_t)blockIdx.x * NN * NN + o] = res[o];
   if (lane == 0) bad[blockIdx.x] = b ? 1 : 0;
 }
 
+template <int NN, int MODE>
+static hipError_t expm_check_launch(int count, const double* A, double* E, int32_t* bad,
+                                    hipStream_t st, long long* stamps) {
+  // wave_expm's scratch is seven NN² blocks, wv_expm's the three slots geod gives it
+  const size_t lds = 8 * (size_t)(MODE == 1 || MODE == 3 ? 7 : 3) * NN * NN;
+  hipError_t e = hipFuncSetAttribute((const void*)wv_expm_check_kernel<NN, MODE>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((wv_expm_check_kernel<NN, MODE>), dim3(count), dim3(64), lds, st, A, E, bad,
+                     stamps);
+  return hipGetLastError();
+}
+
+// hipErrorInvalidValue for a (mode, nn) pair that is not instantiated
 hipError_t launch_expm_check(int nn, int count, const double* A, double* E, int32_t* bad, int mode,
                              hipStream_t st, long long* stamps) {
-#define CASE(NNV)                                                                               \
-  if (nn == NNV) {                                                                              \
-    const size_t lds = 8 * (size_t)(mode == 2 ? 3 : 7) * NNV * NNV;                             \
-    hipError_t e = hipFuncSetAttribute((const void*)wv_expm_check_kernel<NNV>,                 \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    if (e != hipSuccess) return e;                                                              \
-    hipLaunchKernelGGL(wv_expm_check_kernel<NNV>, dim3(count), dim3(64), lds, st, A, E, bad,    \
-                       mode, stamps);                                                           \
-    return hipGetLastError();                                                                   \
-  }
-  CASE(12) CASE(16) CASE(20) CASE(24) CASE(30) CASE(32) CASE(40)
+#define CASE(MODEV, NNV) \
+  if (mode == MODEV && nn == NNV) return expm_check_launch<NNV, MODEV>(count, A, E, bad, st, stamps);
+#define GEOD_SIZES(M) CASE(M, 12) CASE(M, 16) CASE(M, 20) CASE(M, 24) CASE(M, 30) CASE(M, 32) CASE(M, 40)
+  CASE(0, 6) CASE(0, 8) CASE(0, 10) CASE(0, 15) GEOD_SIZES(0)
+  CASE(1, 1) CASE(1, 2) CASE(1, 3) CASE(1, 4) CASE(1, 5) CASE(1, 6) CASE(1, 8) CASE(1, 10)
+  CASE(1, 15) GEOD_SIZES(1)
+  GEOD_SIZES(2)
+  CASE(3, 40)
+  GEOD_SIZES(4)
+#undef GEOD_SIZES
 #undef CASE
   return hipErrorInvalidValue;
 }

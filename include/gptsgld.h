@@ -176,9 +176,19 @@ int gpt_sgld_session_stamps(gpt_sgld_session* s, int64_t nsteps, int64_t* out);
  * library fills slots 0, 1 and the last step's; the timeline build (`make timeline`) every step.
  * *event_us = the launch's hipEvent time. */
 int64_t gpt_sgld_timeline_slots(void);
-/* Test entry: E = expm(A) for `count` row-major nn x nn host matrices (nn in {12,16,20,24,30,32,
- * 40}) on the device: mode 0 the wave engine's register-blocked Padé (wave.hip wv_expm), mode 1 the
- * grid engine's wave_expm; bad[c] = 1 when E_c holds a NaN (the geodesic bail-out test). */
+/* Test entry: E = expm(A) for `count` row-major nn x nn host matrices on the device, at every size
+ * the samplers instantiate (the geodesic's 2r x 2r block and the r x r expm(-tA)):
+ *   mode 0  the wave engine's register-blocked Padé (wave.hip wv_expm), every column;
+ *           nn in {6,8,10,12,15,16,20,24,30,32,40}
+ *   mode 1  wave_expm of the grid, chain, TGP and MovieLens kernels;
+ *           nn in {1,2,3,4,5,6,8,10,12,15,16,20,24,30,32,40}
+ *   mode 3  wave_expm with the LDS partial-pivoting solve kept (the 1024-thread kernels); nn = 40
+ *   mode 4  wv_expm asked for the first nn/2 result columns only, as the wave engine's geodesic
+ *           calls it; E_c is the whole result slot, of which columns [0, nn/2) are defined;
+ *           nn in {12,16,20,24,30,32,40}
+ * (mode 2 is gpt_debug_expm_stamps' timing run.)  Any other (mode, nn) is GPT_ERR_BAD_DIMS.
+ * bad[c] = 1 when E_c holds a NaN (the geodesic bail-out test); for an A_c with an Inf or NaN
+ * entry bad[c] = 1 and E_c is all NaN. */
 int gpt_debug_expm(int32_t nn, int32_t count, int32_t mode, const double* A, double* E,
                    int32_t* bad);
 /* Test entry: the Gaussian conditional draw of the Gibbs samplers (tgp.hip gaussian_draw_prec,

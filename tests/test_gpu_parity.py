@@ -187,6 +187,7 @@ CASES = {
     # edge shapes: a last batch of one row (an odd row group), one input dimension, odd n with
     # one 64-row block (4-B row staging), odd n past one block (the chain engine declines: grid)
     "last_row_alone": (24, 2, 41, 2, 4, 8, 0, 2, 1, True, True),
+    "r1": (20, 3, 30, 1, 1, 8, 0, 2, 1, True, True),     # rank one: the 2 × 2 and 1 × 1 expm
     "d1": (32, 1, 30, 3, 3, 7, 0, 2, 1, True, True),
     "n17_odd": (17, 3, 40, 2, 6, 8, 0, 2, 1, True, True),
     "n101_odd": (101, 2, 33, 3, 9, 10, 0, 2, 1, True, True),
@@ -270,6 +271,74 @@ def test_chain_trajectory_without_diagnostics(name):
     assert info["status"] == 0
     assert rel(ws, wo) < 1e-8, rel(ws, wo)
     assert rel(Us, Uo) < 1e-8, rel(Us, Uo)
+
+
+# Geodesic steps large enough for the Padé degrees 9 and 13 and the squaring loop inside the step
+# kernels (the cases above stay at ‖t·T‖₁ <= 0.27: degrees 3, 5, 7): εw = 1e-4, εU = 1e-4, one
+# epoch.  Each run must pass the 1-norm in its last column somewhere: 5.4 (degree 13 with
+# squarings; every run passes 0.95, degree 9, on the way).  The r = 20 shape peaks at 5.05 at
+# εU = 1e-4 (degree 13, no squaring), so that run is asked for 2.1 and a second one at εU = 3e-4
+# (peak 19.1, s = 2) puts the squarings of the 40 × 40 block inside a step kernel as well.
+# tests/test_oracle.py holds the conditions on these runs that need no GPU (the norms visited, and
+# the oracle's own sensitivity to a 1e-15 perturbation of U_init, below 1e-11).
+LARGE_STEP_RUNS = [
+    # (n, D, N, r, Q, m), εU, engines, norm passed
+    ((16, 3, 40, 2, 6, 8), 1e-4, ("grid", "chain"), 5.4),
+    ((64, 4, 40, 5, 30, 8), 1e-4, ("grid", "chain"), 5.4),
+    ((40, 3, 40, 6, 30, 8), 1e-4, ("grid", "wave"), 5.4),
+    ((60, 3, 40, 20, 30, 8), 1e-4, ("grid", "wave"), 2.1),
+    ((60, 3, 40, 20, 30, 8), 3e-4, ("grid", "wave"), 5.4),
+]
+_large_step_runs = {}
+
+
+def large_step_oracle(shape, epsU, U_init=None):
+    """(problem, w_store, U_store, info, ‖·‖₁ of every expm argument) of the oracle's run of a
+    LARGE_STEP_RUNS entry; the run from the default initial state is computed once."""
+    if U_init is None and (shape, epsU) in _large_step_runs:
+        return _large_step_runs[shape, epsU]
+    n, D, N, r, Q, m = shape
+    p = make_problem(n, D, N, r, Q, seed=11)
+    norms = []
+    orig = R.expm
+
+    def logged(A):
+        norms.append(np.abs(A).sum(axis=0).max())
+        return orig(A)
+
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(R, "expm", logged)
+        wo, Uo, info = R.GPTregression(p["phi"], p["y"], 0.05, p["I"], r, Q, m, 1e-4, epsU, 0, 1,
+                                       23, record=True, U_init=U_init)
+    out = (p, wo, Uo, info, np.array(norms))
+    if U_init is None:
+        _large_step_runs[shape, epsU] = out
+    return out
+
+
+@pytest.mark.parametrize("engine,shape,epsU,passes",
+                         [(e, s, eu, t) for s, eu, engs, t in LARGE_STEP_RUNS for e in engs])
+def test_sampler_trajectory_large_geodesic_steps(engine, shape, epsU, passes):
+    """test_sampler_trajectory_matches_oracle at εw = 1e-4, εU = 1e-4 (3e-4) for one epoch: the
+    geodesic's ‖t·T‖₁ climbs past 0.95, 2.1 and 5.4 within the epoch, so the step kernels run
+    Padé 9, Padé 13 and the squarings, with the same bars (1e-8 on every stored sample, 1e-9 on the
+    gradient norms)."""
+    n, D, N, r, Q, m = shape
+    p, wo, Uo, info, norms = large_step_oracle(shape, epsU)
+    assert (norms > 0.95).any() and (norms > passes).any(), norms.max()
+    assert info["status"] == 0
+    ws, Us, dg = G().GPTregression(p["phi"], p["y"], 0.05, p["I"], r, Q, m, 1e-4, epsU, 0, 1, 23,
+                                   diag=True, engine=engine)
+    assert ws.shape == wo.shape and Us.shape == Uo.shape
+    assert rel(ws, wo) < 1e-8, rel(ws, wo)
+    assert rel(Us, Uo) < 1e-8, rel(Us, Uo)
+    gw = np.array(info["gradw_norm"]); gU = np.array(info["gradU_norm"]).T
+    assert rel(dg[0], gw) < 1e-9
+    assert rel(dg[1:], gU) < 1e-9
+    for s in range(Us.shape[3]):
+        for k in range(D):
+            Uk = Us[:, :, k, s]
+            assert np.abs(Uk.T @ Uk - np.eye(r)).max() < 1e-10
 
 
 RMS_CASES = {
@@ -581,6 +650,30 @@ def test_regression_chains_equals_session(shape):
         alive += st == 0
     s.close()
     assert alive >= C // 2
+
+
+@pytest.mark.parametrize("engine,shape", [("wave", (40, 3, 40, 6, 30, 8)),
+                                          ("chain", (64, 4, 40, 5, 30, 8))])
+def test_regression_chains_per_chain_phi_matches_oracle(engine, shape):
+    """gpt_sgld_regression_chains with one phi per chain (each from its own length scales, as the
+    sweep block of kin40kExperiment.jl:67-74 builds them) against the oracle run on that chain's
+    phi and seed: the session comparison above runs the same device code on both sides."""
+    n, D, N, r, Q, m = shape
+    p = make_problem(n, D, N, r, Q, seed=11)
+    seeds = [3, 4, 5]
+    phis = []
+    for c in seeds:
+        ls = 1.0 + 0.2 * np.random.default_rng(100 + c).standard_normal(D)
+        phis.append(R.feature(p["X"], ls, 1.0, p["scale"], p["Z"], p["b"]))
+    assert not np.array_equal(phis[0], phis[1]) and not np.array_equal(phis[1], phis[2])
+    got = G().GPTregression_chains(phis, p["y"], 0.05, p["I"], r, Q, m, 1e-4, 1e-6, 0, 2, seeds,
+                                   engine=engine)
+    for c, sd in enumerate(seeds):
+        wo, Uo, info = R.GPTregression(phis[c], p["y"], 0.05, p["I"], r, Q, m, 1e-4, 1e-6, 0, 2, sd)
+        ws, Us, st = got[c]
+        assert st == 0 and info["status"] == 0
+        assert rel(ws, wo) < 1e-8, (c, rel(ws, wo))
+        assert rel(Us, Uo) < 1e-8, (c, rel(Us, Uo))
 
 
 @pytest.mark.parametrize("engine", ["grid", "chain", "wave"])

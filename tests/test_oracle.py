@@ -13,8 +13,10 @@ import numpy as np
 import pytest
 import scipy.linalg
 
+from oracle import expm_cases as XC
 from oracle import gpt_sgld_ref as R
 from oracle import philox as px
+from test_gpu_parity import LARGE_STEP_RUNS, large_step_oracle
 
 
 @pytest.mark.parametrize("tag,expected", [("5D", 0.03125), ("10D", 0.0258)])
@@ -395,3 +397,119 @@ def test_movielens_cpp_port_matches_numpy_restatement():
                                      1e-3, 1e-3, 0.5, 0.25, 0.5, lazy=True)
     for got, ref in zip(outs_l[0], outs[0]):
         assert np.abs(got - ref).max() <= 1e-12 * np.abs(ref).max()
+
+
+# ------------------------------------------------- inputs of the device expm tests (test_gpu_expm.py)
+@pytest.mark.parametrize("nn", XC.ALL_SIZES)
+def test_expm_cases_reach_every_branch(nn):
+    """Conditions on the matrices tests/test_gpu_expm.py feeds the device, checked without one: at
+    every size each Padé degree, degree 13 with s = 0, 1 <= s <= 3 and s >= 8, a diagonally
+    dominant and a non-dominant denominator and (nn >= 2) one that partial pivoting permutes; every
+    1-norm at least 1e-6 (relative) from a branch threshold, so a last-ulp difference in the
+    device's column sums cannot flip a branch; the oracle within 1e-10 of mpmath on every matrix
+    (none is dropped as ill-conditioned); and the committed mpmath results cover every matrix.
+    A 1 × 1 denominator has no off-diagonal entries: it is always dominant."""
+    cs = XC.cases(nn)
+    assert len({name for name, _, _ in cs}) == len(cs)
+    with np.load(XC.golden_path(nn)) as f:
+        assert [str(d) for d in f["digest"]] == [XC.digest(X) for _, _, X in cs]
+    kinds = []
+    for (name, family, X), ref in zip(cs, XC.mp_reference(nn)):
+        assert X.shape == (nn, nn) and np.isfinite(X).all()
+        b = XC.branch(X)
+        assert XC.threshold_margin(b["norm"]) >= 1e-6, name
+        assert np.array_equal(XC.expm_from_parts(X), R.expm(X)), name
+        assert XC.err_vs_mp(R.expm(X), ref) <= 1e-10, name
+        if family == "swap":
+            assert b["swaps"] and not b["dd"] and (b["degree"], b["s"]) == (13, 0), name
+        if family == "large":
+            assert b["s"] in (8, 15), name
+        kinds.append(b)
+    for deg in (3, 5, 7, 9):
+        assert any(b["degree"] == deg for b in kinds), deg
+    d13 = [b["s"] for b in kinds if b["degree"] == 13]
+    assert 0 in d13 and any(1 <= s <= 3 for s in d13) and any(s >= 8 for s in d13)
+    assert any(b["dd"] for b in kinds)
+    if nn >= 2:
+        assert any(not b["dd"] for b in kinds)
+        assert any(b["swaps"] for b in kinds)
+
+
+def test_expm_mode_table_is_the_production_sizes():
+    ranks = (1, 2, 3, 4, 5, 6, 8, 10, 12, 15, 16, 20)
+    assert set(XC.MODE_SIZES[1]) == set(ranks) | {2 * r for r in ranks}
+    wave = [r for r in ranks if r > 5]
+    assert set(XC.MODE_SIZES[0]) == set(wave) | {2 * r for r in wave}
+    assert set(XC.MODE_SIZES[4]) == {2 * r for r in wave}
+
+
+@pytest.mark.parametrize("nn", [1, 2, 3, 5, 8, 12])
+def test_expm_golden_reference_is_mpmath(nn):
+    """The committed high-precision results are mpmath.expm's (recomputed here at the small sizes,
+    where it takes well under a second per matrix), to the 1e-22 their float64 + float32 pair holds."""
+    with np.load(XC.golden_path(nn)) as f:
+        hi, lo = f["hi"], f["lo"].astype(np.float64)
+    cs = XC.cases(nn)
+    for k in range(0, len(cs), 1 if nn <= 5 else 5):
+        h, l = XC.expm_mp(cs[k][2])
+        assert np.array_equal(h, hi[k])
+        assert np.abs(l - lo[k]).max() <= 1e-22 * np.abs(h).max()
+
+
+@pytest.mark.parametrize("nn", [nn for nn in XC.ALL_SIZES if nn >= 2])
+def test_expm_overflow_cases_are_far_from_the_edge(nn):
+    """exp(G + μI) = e^μ·exp(G) with tr G = 0: |det exp(G)| = 1 puts its largest entry above
+    1/√nn (Hadamard) and ‖exp(G)‖₁ <= e^‖G‖₁ puts it below e², so the overflowing matrix has an
+    entry above 1e400 and the bounded one none above 1e200; the oracle flags exactly the first.
+    Checked against mpmath itself at the sizes where that is quick."""
+    import mpmath
+    Xo, Xb = XC.overflow_cases(nn)
+    G = Xo - XC.OVERFLOW_SHIFT * np.eye(nn)
+    assert abs(np.trace(G)) < 1e-12 and XC.one_norm(G) <= 2.0 * (1 + 1e-12)
+    assert np.array_equal(G, Xb - XC.BOUNDED_SHIFT * np.eye(nn))
+    assert (XC.OVERFLOW_SHIFT - 0.5 * math.log(nn)) / math.log(10) > 400
+    assert (XC.BOUNDED_SHIFT + 2) / math.log(10) < 200
+    for X in (Xo, Xb):
+        assert XC.threshold_margin(XC.one_norm(X)) >= 1e-6
+    with np.errstate(all="ignore"):
+        assert np.isnan(R.expm(Xo)).any()
+        assert np.isfinite(R.expm(Xb)).all()
+    if nn <= 6:
+        with mpmath.workdps(XC.MP_DIGITS):
+            top = lambda X: max(abs(v) for v in mpmath.expm(mpmath.matrix(X.tolist())))
+            assert top(Xo) > mpmath.mpf("1e400") and top(Xb) < mpmath.mpf("1e200")
+
+
+def test_expm_nonfinite_cases():
+    for nn in XC.ALL_SIZES:
+        cs = XC.nonfinite_cases(nn)
+        assert len(cs) == (2 if nn == 1 else 4)
+        for name, X in cs:
+            bad = ~np.isfinite(X)
+            assert bad.sum() == 1 and bad[:, [0, nn - 1]].any()
+            assert np.isnan(R.expm(X)).all()
+        assert {int(np.argwhere(~np.isfinite(X))[0][1]) for _, X in cs} == {0, nn - 1}
+
+
+@pytest.mark.parametrize("shape,epsU,passes", [(s, eu, t) for s, eu, _, t in LARGE_STEP_RUNS])
+def test_large_geodesic_step_runs_are_well_conditioned(shape, epsU, passes):
+    """test_sampler_trajectory_large_geodesic_steps' runs (εw = 1e-4, εU = 1e-4 or 3e-4, one epoch),
+    without a GPU: status 0, the geodesic's ‖t·T‖₁ passes 0.95 and the run's own mark (5.4: Padé 13
+    with squarings; 2.1 for the r = 20 run at εU = 1e-4, which peaks at 5.05), and the oracle re-run
+    from a U_init perturbed by 1e-15 and re-orthonormalised moves every stored sample by less than
+    1e-11 relative (measured <= 7.4e-12), three decades inside the 1e-8 bar."""
+    n, D, N, r, Q, m = shape
+    p, wo, Uo, info, norms = large_step_oracle(shape, epsU)
+    assert info["status"] == 0
+    assert (norms > 0.95).any() and (norms > passes).any(), norms.max()
+    _, U0 = R.init_state(n, r, D, Q, 23)
+    rng = np.random.default_rng(1)
+    U1 = np.empty_like(U0)
+    for k in range(D):
+        Uk = U0[:, :, k] + 1e-15 * rng.standard_normal((n, r))
+        U1[:, :, k] = R.stiefel_init(Uk.T)
+    assert 0 < np.abs(U1 - U0).max() < 1e-14
+    _, w1, Us1, info1, _ = large_step_oracle(shape, epsU, U_init=U1)
+    assert info1["status"] == 0
+    rel = lambda a, b: np.abs(a - b).max() / np.abs(b).max()
+    assert rel(w1, wo) < 1e-11 and rel(Us1, Uo) < 1e-11, (rel(w1, wo), rel(Us1, Uo))
