@@ -11,6 +11,8 @@ Same function names, argument meaning, return values and error behaviour as the 
     samplenz(r, D, Q, seed)                                   GPT_SGLD_p.jl:57
     GPTregression(phi, y, signal_var, I, r, Q, m, epsw, epsU, burnin, maxepoch[, param_seed];
                   langevin, stiefel)                          GPT_SGLD.jl:345
+    GPTregression_chains(phis, y, ...) / GPTregression_chains_x(X, y, length_scales, sigma_RBFs,
+                  phi_scale, Z, b, ...)                       kin40kExperiment.jl:67-74 (the sweeps)
     GPT_SGLDERM(phi, y, sigma, I, r, Q, m, epsw, epsU, burnin, maxepoch)  GPT_SGLD_p.jl:146
     GPT_SGLDERMw(phi, y, signal_var, I, r, Q, m, epsw, burnin, maxepoch)  GPT_SGLD.jl:1065
     GPTclassification(phi, y, I, r, Q, m, epsw, epsU, burnin, maxepoch[, param_seed];
@@ -284,6 +286,62 @@ def GPTregression_chains(phis, y, signal_var, I, r, Q, m, epsw, epsU, burnin, ma
         check(lib().gpt_sgld_regression_chains(C.byref(cfg), nch, sd.ctypes.data_as(P_U64),
                                                arr(ph), arr([y] * nch), _ptr(I, P_I32), ew_p,
                                                eu_p, sv_p, arr(ws), arr(Us), _ptr(st, P_I32)))
+    return [(ws[c], Us[c], int(st[c])) for c in range(nch)]
+
+
+def GPTregression_chains_x(X, y, length_scales, sigma_RBFs, phi_scale, Z, b, signal_var, I, r, Q,
+                           m, epsw, epsU, burnin, maxepoch, seeds, sigma_w=1.0, store_every=1,
+                           max_steps=0, engine=None):
+    """GPTregression_chains from X (gpt_sgld_regression_chains_x): the sweep block of
+    kin40kExperiment.jl:67-74 with chain c's ``feature(X, length_scales[c], sigma_RBFs[c],
+    phi_scale, Z, b)`` formed on the device one minibatch ahead of the steps, so no phi (n, D, N)
+    is built, held or uploaded.  ``length_scales``: one row per chain ((nchains,) scalars,
+    (nchains, 1) or (nchains, D)); ``sigma_RBFs``: a scalar or one per chain; the rest and the
+    return value as GPTregression_chains, whose stores on those phis these equal bit for bit."""
+    seeds = [int(s) & (2 ** 64 - 1) for s in seeds]
+    nch = len(seeds)
+    X = _f64(X)
+    if X.ndim != 2:
+        raise ValueError("X must be (N, D)")
+    N, D = X.shape
+    Z = _f64(Z)
+    n = Z.shape[0]
+    if Z.shape != (n, D):
+        raise ValueError("Z must be (n, D)")
+    b = _f64(np.asarray(b, dtype=np.float64).reshape((n, D), order="F"))
+    ls = np.asarray(length_scales, dtype=np.float64)
+    if ls.ndim < 2:
+        ls = ls.reshape(-1, 1)
+    if ls.shape[0] != nch:
+        raise ValueError("length_scales needs one row per chain")
+    ls = np.ascontiguousarray(ls)                   # row c = chain c: Julia (ls_len, nchains)
+    sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_RBFs, dtype=np.float64), (nch,)))
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    if y.size != N:
+        raise ValueError("X and y disagree on N")
+    I = np.asfortranarray(np.asarray(I, dtype=np.int32))
+    if I.shape != (Q, D):
+        raise ValueError("I must be (Q, D)")
+
+    def per_chain(v):
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (nch,)))
+        return a, _ptr(a)
+    ew, ew_p = per_chain(epsw)
+    eu, eu_p = per_chain(epsU)
+    sv, sv_p = per_chain(signal_var)
+    cfg = make_config(n, D, N, r, Q, m, ew[0], eu[0], sv[0], sigma_w, burnin, maxepoch, 0, True,
+                      True, store_every, max_steps)
+    T = (maxepoch * (-(-N // m))) // store_every
+    ws = [np.zeros((Q, T), order="F") for _ in range(nch)]
+    Us = [np.zeros((n, r, D, T), order="F") for _ in range(nch)]
+    st = np.zeros(nch, dtype=np.int32)
+    arr = lambda xs: (P_D * nch)(*[_ptr(x) for x in xs])
+    sd = np.array(seeds, dtype=np.uint64)
+    with _engine_env(engine):
+        check(lib().gpt_sgld_regression_chains_x(
+            C.byref(cfg), nch, sd.ctypes.data_as(P_U64), _ptr(X), arr([y] * nch), _ptr(ls),
+            ls.shape[1], _ptr(sg), float(phi_scale), _ptr(Z), _ptr(b), _ptr(I, P_I32), ew_p, eu_p,
+            sv_p, arr(ws), arr(Us), _ptr(st, P_I32)))
     return [(ws[c], Us[c], int(st[c])) for c in range(nch)]
 
 

@@ -49,6 +49,15 @@ SIGNATURES = {
     "gpt_sgld_session_create": (C.c_int, [C.POINTER(SGLDConfig), C.c_int32, P_U64,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), P_I32,
                                           C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gpt_sgld_regression_chains_x": (C.c_int, [C.POINTER(SGLDConfig), C.c_int32, P_U64, P_D,
+                                               C.POINTER(P_D), P_D, C.c_int64, P_D, C.c_double,
+                                               P_D, P_D, P_I32, P_D, P_D, P_D, C.POINTER(P_D),
+                                               C.POINTER(P_D), P_I32]),
+    "gpt_sgld_session_create_x": (C.c_int, [C.POINTER(SGLDConfig), C.c_int32, P_U64, C.c_void_p,
+                                            C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, P_D,
+                                            C.c_double, C.c_void_p, C.c_void_p, P_I32, C.c_int32,
+                                            C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gpt_sgld_session_staging": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "gpt_sgld_session_run": (C.c_int, [C.c_void_p, C.c_int64]),
     "gpt_sgld_session_prepare": (C.c_int, [C.c_void_p, C.c_int64]),
     "gpt_sgld_session_set_rmsprop": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),

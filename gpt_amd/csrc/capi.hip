@@ -221,7 +221,21 @@ struct gpt_sgld_session {
   int max_inflight = 8;               // GPTSGLD_MAX_INFLIGHT; 0 = unbounded
   std::vector<hipEvent_t> inflight;
   long long chunks_enqueued = 0;
+  // X mode (gpt_sgld_session_create_x): chains_d keeps the real order rings and targets (the
+  // epoch-order kernel and the stager use it, its phi is null); the engines run on view_d, whose
+  // phi / y / order are the chain's feature ring, target ring and order view (StageParams).
+  bool xmode = false, x_primed = false;
+  int xspan = 1;                      // steps per launch at most; the ring holds xspan + 1 batches
+  StageParams S{};
+  DevMem view_d, xcoef;
+  std::vector<ChainDesc> view_h;
+  long long stage_bytes = 0;          // ring + view bytes per chain (gpt_sgld_session_staging)
 };
+
+// The ChainDesc array the step engines read.
+static const ChainDesc* engine_chains(const gpt_sgld_session* s) {
+  return s->xmode ? s->view_d.as<ChainDesc>() : s->chains_d.as<ChainDesc>();
+}
 
 // Engine choice: store_flags bit 2 (or bit 4 / 5, w-only steps / classification) forces the grid
 // engine (sgld.hip), bit 3 the chain engine (chain.hip), bit 7 the wave engine (wave.hip);
@@ -321,31 +335,44 @@ extern "C" int gpt_device_count(void) {
 static hipError_t session_launch(gpt_sgld_session* s, const StepParams& P, int t_local,
                                  int nsteps = 1) {
   if (P.ncls)
-    return launch_step_cls(P, s->chains_d.as<ChainDesc>(), s->nchains, s->tbase.as<long long>(),
+    return launch_step_cls(P, engine_chains(s), s->nchains, s->tbase.as<long long>(),
                            t_local, s->stream);
   if (P.wonly)
-    return launch_step_wonly(P, s->chains_d.as<ChainDesc>(), s->nchains, s->tbase.as<long long>(),
+    return launch_step_wonly(P, engine_chains(s), s->nchains, s->tbase.as<long long>(),
                              t_local, s->stream);
   if (P.rms)
-    return launch_step_rms(P, s->chains_d.as<ChainDesc>(), s->nchains, s->tbase.as<long long>(),
+    return launch_step_rms(P, engine_chains(s), s->nchains, s->tbase.as<long long>(),
                            t_local, s->stream);
   if (s->engine == kEngineChain)
-    return launch_chain(P, s->chains_d.as<ChainDesc>(), s->nchains, s->tbase.as<long long>(),
+    return launch_chain(P, engine_chains(s), s->nchains, s->tbase.as<long long>(),
                         t_local, nsteps, s->stream);
   if (s->engine == kEngineWave)
-    return launch_wave(P, s->chains_d.as<ChainDesc>(), s->nchains, s->tbase.as<long long>(),
+    return launch_wave(P, engine_chains(s), s->nchains, s->tbase.as<long long>(),
                        t_local, false, s->stream);
-  return launch_step(P, s->chains_d.as<ChainDesc>(), s->nchains, s->tbase.as<long long>(),
+  return launch_step(P, engine_chains(s), s->nchains, s->tbase.as<long long>(),
                      t_local, s->stream);
 }
 
-// temp of the first step (grid engine only: the chain engine forms temp inside its step).
+// X mode: stage batches tbase[0] + t_first .. + count - 1 into the rings (feature.hip).
+static hipError_t session_stage(gpt_sgld_session* s, int t_first, int count) {
+  return launch_stage_batches(s->S, s->chains_d.as<ChainDesc>(), s->view_d.as<ChainDesc>(),
+                              s->nchains, s->tbase.as<long long>(), t_first, count, s->stream);
+}
+
+// temp of the first step (grid engine only: the chain engine forms temp inside its step).  An X
+// session stages the batch of its first step here, once, on every engine: from then on each
+// launch's stager call leaves the batch after the launch's last step in the ring.
 static int session_prime(gpt_sgld_session* s) {
+  if (s->xmode && !s->x_primed) {
+    const hipError_t e = session_stage(s, 0, 1);
+    if (e != hipSuccess) return hip_fail(e, "launch_stage_batches");
+    s->x_primed = true;
+  }
   if (s->engine == kEngineChain || s->temp_ready) return GPT_OK;
   hipError_t e = s->engine == kEngineWave
-                     ? launch_wave(s->P, s->chains_d.as<ChainDesc>(), s->nchains,
+                     ? launch_wave(s->P, engine_chains(s), s->nchains,
                                    s->tbase.as<long long>(), 0, true, s->stream)
-                     : launch_temp_init(s->P, s->chains_d.as<ChainDesc>(), s->nchains,
+                     : launch_temp_init(s->P, engine_chains(s), s->nchains,
                                         s->tbase.as<long long>(), s->stream);
   if (e != hipSuccess) return hip_fail(e, "launch_temp_init");
   s->temp_ready = true;
@@ -363,10 +390,24 @@ static hipError_t session_epoch_order(gpt_sgld_session* s, long long t_host, int
 }
 
 // Steps of one epoch at most that one launch runs from host step t_host (chain engine: the rest of
-// the epoch within `left`; other engines: 1).
+// the epoch within `left`; other engines: 1).  An X session's launches stop at xspan steps: its
+// ring holds the launch's batches and the one after them (session_stage_ahead).
 static int session_span(const gpt_sgld_session* s, long long t_host, long long left) {
   if (s->engine != kEngineChain || s->P.rms || s->P.wonly || s->P.ncls) return 1;
-  return (int)std::min<long long>(left, s->P.nb - t_host % s->P.nb);
+  const long long span = std::min<long long>(left, s->P.nb - t_host % s->P.nb);
+  return (int)(s->xmode ? std::min<long long>(span, s->xspan) : span);
+}
+
+// X mode, before the launch of steps t_local .. t_local+span-1: step t reads batch t and already
+// batch t+1 (the wave and grid engines form the next batch's temp at the end of the step, the
+// chain engine's next launch starts on it), so batches t_local+1 .. t_local+span go into the ring
+// now (batch t_local is there since the launch before, or since session_prime).  The ring's
+// span + 1 <= KR slots are all distinct, so no write lands on a slot this launch reads.  Called
+// after session_epoch_order: batch t_local+span may open epoch e+1, whose order exists from the
+// first step of epoch e on.
+static hipError_t session_stage_ahead(gpt_sgld_session* s, int t_local, int span) {
+  if (!s->xmode) return hipSuccess;
+  return session_stage(s, t_local + 1, span);
 }
 
 static int session_enqueue(gpt_sgld_session* s, int count) {
@@ -375,6 +416,8 @@ static int session_enqueue(gpt_sgld_session* s, int count) {
     hipError_t e = session_epoch_order(s, s->steps_done + i, i);
     if (e != hipSuccess) return hip_fail(e, "launch_epoch_order");
     const int span = session_span(s, s->steps_done + i, count - i);
+    e = session_stage_ahead(s, i, span);
+    if (e != hipSuccess) return hip_fail(e, "launch_stage_batches");
     e = session_launch(s, s->P, i, span);
     if (e != hipSuccess) return hip_fail(e, "launch_step");
     i += span;
@@ -384,15 +427,26 @@ static int session_enqueue(gpt_sgld_session* s, int count) {
   return GPT_OK;
 }
 
-extern "C" int gpt_sgld_session_create(const gpt_sgld_config* cfg, int32_t nchains,
-                                       const uint64_t* seeds, const double* const* phi_dev,
-                                       const double* const* y_dev, const int32_t* I_host,
-                                       int32_t store_flags, void* hip_stream,
-                                       gpt_sgld_session** out) {
+// The inputs an X session keeps in place of per-chain phi (gpt_sgld_session_create_x).
+struct XInputs {
+  const double* X;                // (N, D) device, shared by the chains
+  const double* ls;               // (ls_len, nchains) device
+  int ls_len;
+  const double* sigma_rbf;        // nchains, host
+  double phi_scale;
+  const double* Z;                // (n, D) device, shared
+  const double* b;                // (n, D) device, shared
+};
+
+// A phi session (phi_dev, xin null) or an X session (xin, phi_dev null).
+static int session_create(const gpt_sgld_config* cfg, int32_t nchains, const uint64_t* seeds,
+                          const double* const* phi_dev, const double* const* y_dev,
+                          const int32_t* I_host, int32_t store_flags, void* hip_stream,
+                          const XInputs* xin, gpt_sgld_session** out) {
   if (!out) { set_error("null out"); return GPT_ERR_BAD_DIMS; }
   *out = nullptr;
   if (!valid_cfg(cfg)) return GPT_ERR_BAD_DIMS;
-  if (nchains < 1 || !seeds || !phi_dev || !y_dev || !I_host) {
+  if (nchains < 1 || !seeds || (!phi_dev && !xin) || !y_dev || !I_host) {
     set_error("bad chain arguments"); return GPT_ERR_BAD_DIMS;
   }
   const int n = (int)cfg->n, D = (int)cfg->D, N = (int)cfg->N, r = (int)cfg->r, Q = (int)cfg->Q,
@@ -476,14 +530,43 @@ extern "C" int gpt_sgld_session_create(const gpt_sgld_config* cfg, int32_t nchai
                b_Us = s->store ? up(8 * (size_t)n * r * D * s->nstore) : 0,
                b_dg = s->diag ? up(8 * (size_t)(1 + D) * s->total_steps) : 0,
                b_wv = s->engine == kEngineWave ? up(8 * (size_t)D * m * r) + up(8 * (size_t)n * r * D) : 0;
+  // X mode: per chain the feature ring (KR batch slots of m rows, 256-byte aligned: the chain
+  // engine's LDS-DMA takes 16-byte pieces), the target ring, the staged row numbers and the view
+  size_t b_ring = 0, b_yr = 0, b_rows = 0, b_view = 0;
+  if (xin) {
+    s->xmode = true;
+    s->xspan = s->engine == kEngineChain ? kXSpanCap : 1;
+    if (const char* ev = std::getenv("GPTSGLD_XSPAN")) {   // measurement (scripts/time_xmode.py)
+      const int v = std::atoi(ev);
+      if (s->engine == kEngineChain && (v == 4 || v == 8 || v == 16)) s->xspan = v;
+    }
+    const size_t KR = (size_t)s->xspan + 1;
+    b_ring = up(8 * KR * m * n * D); b_yr = up(8 * KR * m); b_rows = up(4 * KR * m);
+    b_view = up(4 * 2 * (size_t)N);
+    s->stage_bytes = (long long)(KR * m * (8 * (size_t)n * D + 8 + 4) + 4 * 2 * (size_t)N);
+    StageParams& S = s->S;
+    S.X = xin->X; S.Z = xin->Z; S.b = xin->b; S.ls = xin->ls; S.ls_len = xin->ls_len;
+    S.N = N; S.n = n; S.D = D; S.m = m; S.nb = (int)s->numbatches; S.KR = (int)KR;
+    S.total_steps = s->total_steps;
+    S.o_rows = b_ring + b_yr;
+    // c of gpt_feature, per chain
+    std::vector<double> cf(nchains);
+    for (int c = 0; c < nchains; ++c)
+      cf[c] = xin->phi_scale * std::pow(xin->sigma_rbf[c], 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
+    HIPCHK(s->xcoef.alloc(8 * (size_t)nchains));
+    HIPCHK(hipMemcpy(s->xcoef.p, cf.data(), 8 * (size_t)nchains, hipMemcpyHostToDevice));
+    S.cfeat = s->xcoef.as<double>();
+    s->view_h.resize(nchains);
+  }
+  const size_t b_x = b_ring + b_yr + b_rows + b_view;
   std::vector<double> w0(Q), U0((size_t)n * r * D);
   s->chains_h.resize(nchains);
   for (int c = 0; c < nchains; ++c) {
     std::unique_ptr<DevMem> mem(new DevMem());
-    HIPCHK(mem->alloc(b_w + b_U + b_temp + b_ord + b_ws + b_Us + b_dg + b_wv));
+    HIPCHK(mem->alloc(b_w + b_U + b_temp + b_ord + b_ws + b_Us + b_dg + b_wv + b_x));
     char* base = mem->as<char>();
     ChainDesc& C = s->chains_h[c];
-    C.phi = phi_dev[c];
+    C.phi = xin ? nullptr : phi_dev[c];
     C.y = y_dev[c];
     C.w = (double*)base;
     C.U = (double*)(base + b_w);
@@ -507,19 +590,95 @@ extern "C" int gpt_sgld_session_create(const gpt_sgld_config* cfg, int32_t nchai
     HIPCHK(hipMemcpy(C.U, U0.data(), 8 * U0.size(), hipMemcpyHostToDevice));
     if (s->store) HIPCHK(hipMemset(C.w_store, 0, b_ws + b_Us));
     if (s->diag) HIPCHK(hipMemset(C.diag, 0, b_dg));
+    if (xin) {
+      char* xb = base + b_w + b_U + b_temp + b_ord + b_ws + b_Us + b_dg + b_wv;
+      // every view entry is a ring row at all times: a read the engines discard stays in the ring
+      HIPCHK(hipMemset(xb, 0, b_x));
+      ChainDesc& V = s->view_h[c];
+      V = C;
+      V.phi = (const double*)xb;
+      V.y = (const double*)(xb + b_ring);
+      V.order = (int32_t*)(xb + b_ring + b_yr + b_rows);
+    }
     s->chain_mem.push_back(std::move(mem));
   }
   HIPCHK(s->chains_d.alloc(sizeof(ChainDesc) * nchains));
   HIPCHK(hipMemcpy(s->chains_d.p, s->chains_h.data(), sizeof(ChainDesc) * nchains,
                    hipMemcpyHostToDevice));
+  if (xin) {
+    HIPCHK(s->view_d.alloc(sizeof(ChainDesc) * nchains));
+    HIPCHK(hipMemcpy(s->view_d.p, s->view_h.data(), sizeof(ChainDesc) * nchains,
+                     hipMemcpyHostToDevice));
+  }
   // order_0 of every chain (the first step builds order_1, session_epoch_order)
   if (const size_t wsi = epoch_order_ws_ints(N, nchains)) HIPCHK(s->ord_ws.alloc(4 * wsi));
   HIPCHK(launch_epoch_order(s->chains_d.as<ChainDesc>(), nchains, N, (int)s->numbatches,
                             s->total_steps, s->tbase.as<long long>(), 0, 0, s->ord_ws.as<int32_t>(),
                             s->stream));
+  // (an X session's epoch graph holds several chain launches of at most xspan steps, each behind
+  // its stager call: session_span cuts them, session_next_chunk and the graph keys do not change)
   s->graph_steps = (int)std::min<long long>(std::max<long long>(s->numbatches, 1), 512);
   if (const char* ev = std::getenv("GPTSGLD_MAX_INFLIGHT")) s->max_inflight = std::max(0, std::atoi(ev));
   *out = s.release();
+  return GPT_OK;
+}
+
+extern "C" int gpt_sgld_session_create(const gpt_sgld_config* cfg, int32_t nchains,
+                                       const uint64_t* seeds, const double* const* phi_dev,
+                                       const double* const* y_dev, const int32_t* I_host,
+                                       int32_t store_flags, void* hip_stream,
+                                       gpt_sgld_session** out) {
+  if (out) *out = nullptr;
+  if (!phi_dev) { set_error("bad chain arguments"); return GPT_ERR_BAD_DIMS; }
+  return session_create(cfg, nchains, seeds, phi_dev, y_dev, I_host, store_flags, hip_stream,
+                        nullptr, out);
+}
+
+// Every check of an X session's arguments that needs no device (also the host-array form's).
+static bool valid_x_args(const gpt_sgld_config* cfg, int32_t nchains, const uint64_t* seeds,
+                         const double* X, const double* const* y, const double* ls, int64_t ls_len,
+                         const double* sigma_rbf, const double* Z, const double* b,
+                         const int32_t* I, int32_t store_flags) {
+  if (!valid_cfg(cfg)) return false;
+  if (nchains < 1 || nchains > 65535) { set_error("X mode: 1 <= nchains <= 65535"); return false; }
+  if (!seeds || !X || !y || !ls || !sigma_rbf || !Z || !b || !I) {
+    set_error("X mode: null argument"); return false;
+  }
+  if (ls_len != 1 && ls_len != cfg->D) {
+    set_error("dimensions of X and length_scale do not match"); return false;
+  }
+  for (int c = 0; c < nchains; ++c)
+    if (!y[c]) { set_error("X mode: null per-chain y"); return false; }
+  if (store_flags & ~(1 | 2 | 4 | 8 | 128)) {
+    set_error("X mode runs the regression steps of the grid, chain and wave engines (store_flags "
+              "bits 2, 3, 7): no w-only, classification or split-engine sessions");
+    return false;
+  }
+  return true;
+}
+
+extern "C" int gpt_sgld_session_create_x(const gpt_sgld_config* cfg, int32_t nchains,
+                                         const uint64_t* seeds, const double* X_dev,
+                                         const double* const* y_dev, const double* ls_dev,
+                                         int64_t ls_len, const double* sigma_rbf, double phi_scale,
+                                         const double* Z_dev, const double* b_dev,
+                                         const int32_t* I_host, int32_t store_flags,
+                                         void* hip_stream, gpt_sgld_session** out) {
+  if (!out) { set_error("null out"); return GPT_ERR_BAD_DIMS; }
+  *out = nullptr;
+  if (!valid_x_args(cfg, nchains, seeds, X_dev, y_dev, ls_dev, ls_len, sigma_rbf, Z_dev, b_dev,
+                    I_host, store_flags))
+    return GPT_ERR_BAD_DIMS;
+  const XInputs xin{X_dev, ls_dev, (int)ls_len, sigma_rbf, phi_scale, Z_dev, b_dev};
+  return session_create(cfg, nchains, seeds, nullptr, y_dev, I_host, store_flags, hip_stream, &xin,
+                        out);
+}
+
+extern "C" int gpt_sgld_session_staging(gpt_sgld_session* s, int64_t* out) {
+  if (!s || !out) { set_error("null argument"); return GPT_ERR_BAD_DIMS; }
+  out[0] = s->xmode ? s->S.KR : 0;
+  out[1] = s->stage_bytes;
+  out[2] = s->xmode ? 1 : 0;
   return GPT_OK;
 }
 
@@ -557,6 +716,11 @@ extern "C" int gpt_sgld_session_set_hyper(gpt_sgld_session* s, int32_t chain, do
   ChainDesc& C = s->chains_h[chain];
   C.epsw = epsw; C.epsU = epsU; C.signal_var = signal_var; C.sigma_w = sigma_w;
   HIPCHK(hipMemcpy(s->chains_d.as<ChainDesc>() + chain, &C, sizeof(ChainDesc), hipMemcpyHostToDevice));
+  if (s->xmode) {                          // the engines read the view's copy
+    ChainDesc& V = s->view_h[chain];
+    V.epsw = epsw; V.epsU = epsU; V.signal_var = signal_var; V.sigma_w = sigma_w;
+    HIPCHK(hipMemcpy(s->view_d.as<ChainDesc>() + chain, &V, sizeof(ChainDesc), hipMemcpyHostToDevice));
+  }
   return GPT_OK;
 }
 
@@ -592,6 +756,7 @@ static int session_alloc_aux(gpt_sgld_session* s) {
 
 extern "C" int gpt_sgld_session_set_rmsprop(gpt_sgld_session* s, double epsilon, double alpha) {
   if (!s) { set_error("null session"); return GPT_ERR_BAD_DIMS; }
+  if (s->xmode) { set_error("RMSprop steps are not available on an X session"); return GPT_ERR_BAD_DIMS; }
   if (s->engine != kEngineGrid) {
     set_error("RMSprop steps run on the grid engine: create the session with store_flags bit 2");
     return GPT_ERR_BAD_DIMS;
@@ -749,6 +914,8 @@ extern "C" int gpt_sgld_session_time_steps(gpt_sgld_session* s, int64_t nsteps, 
     hipError_t eo = session_epoch_order(s, s->steps_done + i, (int)i);   // outside the event pair
     if (eo != hipSuccess) return hip_fail(eo, "launch_epoch_order");
     const int span = session_span(s, s->steps_done + i, cnt - i);
+    eo = session_stage_ahead(s, (int)i, span);                           // likewise
+    if (eo != hipSuccess) return hip_fail(eo, "launch_stage_batches");
     HIPCHK(hipEventRecord(ev[2 * nl], s->stream));
     hipError_t e = session_launch(s, s->P, (int)i, span);
     if (e != hipSuccess) rc = hip_fail(e, "launch_step");
@@ -774,6 +941,7 @@ extern "C" int gpt_sgld_session_time_steps(gpt_sgld_session* s, int64_t nsteps, 
 
 extern "C" int gpt_sgld_session_stamps(gpt_sgld_session* s, int64_t nsteps, int64_t* out) {
   if (!s || !out) { set_error("null argument"); return GPT_ERR_BAD_DIMS; }
+  if (s->xmode) { set_error("stamps are not available on an X session"); return GPT_ERR_BAD_DIMS; }
   const long long cnt = std::min<long long>(nsteps, s->total_steps - s->steps_done);
   if (cnt <= 0) return GPT_OK;
   {
@@ -868,6 +1036,7 @@ extern "C" int gpt_debug_expm_stamps(int32_t nn, int32_t count, const double* A,
 extern "C" int gpt_sgld_session_timeline(gpt_sgld_session* s, int64_t nsteps, int64_t* out,
                                          double* event_us) {
   if (!s || !out) { set_error("null argument"); return GPT_ERR_BAD_DIMS; }
+  if (s->xmode) { set_error("the timeline is not available on an X session"); return GPT_ERR_BAD_DIMS; }
   if (s->engine != kEngineChain) { set_error("timeline: chain engine only"); return GPT_ERR_BAD_DIMS; }
   const long long left = s->total_steps - s->steps_done;
   const int span = session_span(s, s->steps_done, std::min<long long>(nsteps, left));
@@ -1099,6 +1268,73 @@ extern "C" int gpt_sgld_regression_chains(const gpt_sgld_config* cfg, int32_t nc
   gpt_sgld_session* s = nullptr;
   int rc = gpt_sgld_session_create(cfg, nchains, seeds, dphi.data(), dy.data(), I, stores ? 1 : 0,
                                    nullptr, &s);
+  if (rc != GPT_OK) return rc;
+  std::unique_ptr<gpt_sgld_session, void (*)(gpt_sgld_session*)> guard(s, gpt_sgld_session_destroy);
+  if (epsw || epsU || signal_var)
+    for (int c = 0; c < nchains; ++c) {
+      rc = gpt_sgld_session_set_hyper(s, c, epsw ? epsw[c] : cfg->epsw, epsU ? epsU[c] : cfg->epsU,
+                                      signal_var ? signal_var[c] : cfg->signal_var, cfg->sigma_w);
+      if (rc != GPT_OK) return rc;
+    }
+  rc = gpt_sgld_session_run(s, s->total_steps);
+  if (rc != GPT_OK) return rc;
+  for (int c = 0; c < nchains; ++c) {
+    rc = gpt_sgld_session_fetch(s, c, w_store ? w_store[c] : nullptr, U_store ? U_store[c] : nullptr,
+                                nullptr, &status[c]);
+    if (rc != GPT_OK) return rc;
+  }
+  return GPT_OK;
+}
+
+// gpt_sgld_regression_chains from X: the sweep block of kin40kExperiment.jl:67-74 with every sweep's
+// features formed on the device from the shared X, Z, b and its own length scales and sigma_RBF
+// (an X session), so the host neither computes nor uploads a phi.
+extern "C" int gpt_sgld_regression_chains_x(const gpt_sgld_config* cfg, int32_t nchains,
+                                            const uint64_t* seeds, const double* X,
+                                            const double* const* y, const double* length_scale,
+                                            int64_t ls_len, const double* sigma_rbf,
+                                            double phi_scale, const double* Z, const double* b,
+                                            const int32_t* I, const double* epsw,
+                                            const double* epsU, const double* signal_var,
+                                            double* const* w_store, double* const* U_store,
+                                            int32_t* status) {
+  if (!status) { set_error("gpt_sgld_regression_chains_x: null status"); return GPT_ERR_BAD_DIMS; }
+  const bool stores = w_store || U_store;
+  if (!valid_x_args(cfg, nchains, seeds, X, y, length_scale, ls_len, sigma_rbf, Z, b, I,
+                    stores ? 1 : 0))
+    return GPT_ERR_BAD_DIMS;
+  for (int c = 0; c < nchains; ++c)
+    if ((w_store && !w_store[c]) || (U_store && !U_store[c])) {
+      set_error("gpt_sgld_regression_chains_x: null per-chain pointer");
+      return GPT_ERR_BAD_DIMS;
+    }
+  for (long long x = 0; x < (long long)cfg->Q * cfg->D; ++x)
+    if (I[x] < 1 || I[x] > cfg->r) { set_error("I entries must be in 1..r"); return GPT_ERR_BAD_DIMS; }
+  const size_t N = (size_t)cfg->N, D = (size_t)cfg->D, n = (size_t)cfg->n;
+  std::vector<std::unique_ptr<DevMem>> mem;     // one device copy per distinct host array
+  std::unordered_map<const double*, const double*> dev_of;
+  auto upload = [&](const double* h, size_t count, const double** out) -> int {
+    auto it = dev_of.find(h);
+    if (it != dev_of.end()) { *out = it->second; return GPT_OK; }
+    std::unique_ptr<DevMem> m(new DevMem());
+    HIPCHK(m->alloc(8 * count));
+    HIPCHK(hipMemcpy(m->p, h, 8 * count, hipMemcpyHostToDevice));
+    *out = m->as<double>();
+    dev_of[h] = *out;
+    mem.push_back(std::move(m));
+    return GPT_OK;
+  };
+  const double *dX = nullptr, *dZ = nullptr, *db = nullptr, *dls = nullptr;
+  int rc = upload(X, N * D, &dX);
+  if (rc == GPT_OK) rc = upload(Z, n * D, &dZ);
+  if (rc == GPT_OK) rc = upload(b, n * D, &db);
+  if (rc == GPT_OK) rc = upload(length_scale, (size_t)ls_len * nchains, &dls);
+  std::vector<const double*> dy(nchains);
+  for (int c = 0; c < nchains && rc == GPT_OK; ++c) rc = upload(y[c], N, &dy[c]);
+  if (rc != GPT_OK) return rc;
+  gpt_sgld_session* s = nullptr;
+  rc = gpt_sgld_session_create_x(cfg, nchains, seeds, dX, dy.data(), dls, ls_len, sigma_rbf,
+                                 phi_scale, dZ, db, I, stores ? 1 : 0, nullptr, &s);
   if (rc != GPT_OK) return rc;
   std::unique_ptr<gpt_sgld_session, void (*)(gpt_sgld_session*)> guard(s, gpt_sgld_session_destroy);
   if (epsw || epsU || signal_var)

@@ -61,6 +61,73 @@ hipError_t launch_feature_notensor(const double* X, long long N, int D, const do
   return hipGetLastError();
 }
 
+// The stager of X-mode sessions (gpt_sgld_session_create_x): the feature rows, targets and view
+// entries of whole minibatches into a chain's ring (gpt_internal.h StageParams), so that no
+// n·D·N phi exists (kin40kExperiment.jl:67-74: every sweep's phi differs only in length_scale and
+// sigma_RBF).  One workgroup per (chain, dimension k, batch, group of kStageRows rows): lanes over
+// j keep zt = Z[j,k]·(1/ls_c[k]) and b[j,k] in registers across the rows, X[row,k] is one
+// wave-uniform scalar per row, and every row's n doubles go out as one coalesced run.  Each
+// feature is feature_kernel's double: c·cos(x·zt + b) with round-to-nearest multiply and add and
+// the library cos, so an X-mode trajectory is the phi-mode trajectory bit for bit.  The step
+// counter comes from the device (captured graphs replay), and a batch at or past total_steps is
+// skipped: no step reads it and its epoch's order may not exist.
+constexpr int kStageRows = 8;
+__global__ __launch_bounds__(256) void stage_batches_kernel(const StageParams S,
+                                                            const ChainDesc* __restrict__ real,
+                                                            const ChainDesc* __restrict__ view,
+                                                            const long long* __restrict__ tbase,
+                                                            int t_first) {
+  const int c = blockIdx.z, k = blockIdx.y;
+  const int ngrp = (S.m + kStageRows - 1) / kStageRows;
+  const int q = blockIdx.x / ngrp, g = blockIdx.x - q * ngrp;
+  const long long t = tbase[0] + t_first + q;
+  if (t >= S.total_steps) return;
+  const int e = (int)(t / S.nb), bb = (int)(t - (long long)e * S.nb);
+  const int Bt = min(S.m, S.N - bb * S.m);
+  const int i0 = g * kStageRows, i1 = min(Bt, i0 + kStageRows);
+  if (i0 >= Bt) return;
+  const int slot = (int)(t % S.KR);
+  const int n = S.n, N = S.N;
+  const size_t at = (size_t)(e & 1) * N + (size_t)bb * S.m;        // the batch in an order ring
+  const int32_t* ord = real[c].order + at;
+  double* ring = (double*)view[c].phi + (size_t)slot * S.m * n * S.D + (size_t)n * k;
+  const double* Xk = S.X + (size_t)N * k;
+  const double inv = 1.0 / S.ls[(size_t)S.ls_len * c + (S.ls_len == 1 ? 0 : k)];
+  const double cc = S.cfeat[c];
+  for (int j = threadIdx.x; j < n; j += blockDim.x) {
+    const double zt = __dmul_rn(S.Z[j + (size_t)n * k], inv);
+    const double bj = S.b[j + (size_t)n * k];
+#pragma unroll 1
+    for (int i = i0; i < i1; ++i) {
+      const int row = min(max(ord[i], 0), N - 1);                   // in range whatever the ring holds
+      ring[(size_t)i * n * S.D + j] = cc * cos(__dadd_rn(__dmul_rn(Xk[row], zt), bj));
+    }
+  }
+  if (k == 0) {
+    double* yr = (double*)view[c].y + (size_t)slot * S.m;
+    int32_t* rows = (int32_t*)((char*)view[c].phi + S.o_rows) + (size_t)slot * S.m;
+    int32_t* vw = view[c].order + at;
+    for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+      const int row = min(max(ord[i], 0), N - 1);
+      yr[i] = real[c].y[row];
+      rows[i] = row;
+      vw[i] = slot * S.m + i;
+    }
+  }
+}
+
+hipError_t launch_stage_batches(const StageParams& S, const ChainDesc* real, const ChainDesc* view,
+                                int nchains, const long long* tbase, int t_first, int count,
+                                hipStream_t st) {
+  if (count < 1 || nchains < 1) return hipSuccess;
+  if (nchains > 65535 || S.D > 65535 || count > S.KR) return hipErrorInvalidValue;
+  const int ngrp = (S.m + kStageRows - 1) / kStageRows;
+  const int nt = min(256, (S.n + 63) / 64 * 64);
+  hipLaunchKernelGGL(stage_batches_kernel, dim3((unsigned)(count * ngrp), S.D, nchains), dim3(nt),
+                     0, st, S, real, view, tbase, t_first);
+  return hipGetLastError();
+}
+
 // One full-theta SGLD step (GPT_SGLD.jl:826-843) in one workgroup:
 //   res = y_B − Φ_Bᵀθ ;  θ += ε_t/2·(−θ/σθ² + (N/B)Φ_B res/σ²) + sqrt(ε_t)·ξ ;  store θ.
 __global__ __launch_bounds__(kNT) void gpnt_step_kernel(

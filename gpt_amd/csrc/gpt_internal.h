@@ -227,6 +227,29 @@ hipError_t launch_feature(const double* X, long long N, int D, const double* ls,
 hipError_t launch_feature_notensor(const double* X, long long N, int D, const double* ls,
                                    double c, const double* Z, const double* b, int n,
                                    double* phi, hipStream_t st);
+// X mode (gpt_sgld_session_create_x): the session keeps X, Z, b and per-chain length scales
+// instead of an n·D·N phi per chain, and the stager (feature.hip) writes the feature rows of the
+// coming minibatches into a per-chain ring of KR batch slots.  The engines run on a second
+// ChainDesc array, the engine view: phi = the ring (KR·m rows of n·D doubles), y = a ring of KR·m
+// targets, order = a 2·N view laid out like the real order ring whose entry for (epoch e, batch b,
+// row i) is the ring row (t mod KR)·m + i, t = e·nb + b.
+constexpr int kXSpanCap = 8;      // X mode, chain engine: steps per launch at most
+struct StageParams {
+  const double* X;                // N*D  training inputs, X[i + N k]
+  const double* Z;                // n*D
+  const double* b;                // n*D
+  const double* ls;               // ls_len*nchains length scales, chain c at ls + ls_len*c
+  const double* cfeat;            // nchains: the feature scale c of gpt_feature, per chain
+  int ls_len;                     // 1 or D
+  int N, n, D, m, nb, KR;
+  long long total_steps;
+  size_t o_rows;                  // bytes from a chain's feature ring to its KR*m staged row numbers
+};
+// Stage batches tbase[0] + t_first .. + count - 1 (those below total_steps) of every chain:
+// `real` holds the order rings and the targets, `view` the rings written.
+hipError_t launch_stage_batches(const StageParams& S, const ChainDesc* real, const ChainDesc* view,
+                                int nchains, const long long* tbase, int t_first, int count,
+                                hipStream_t st);
 // MovieLens tensor CF (cf.hip, 100k_movielensExperiment.jl:409-551)
 struct CfParams {
   int n1, D1, n2, D2, r, m, rowsU, rowsV;

@@ -58,10 +58,88 @@ class SGLDSession:
         check(lib().gpt_sgld_session_create(C.byref(self.cfg), nch, sd, pp, yy,
                                             I.ctypes.data_as(_lib.P_I32), flags, st, C.byref(h)))
         self._h = h
-        self.numbatches = -(-self.N // m)
+        self._counts(burnin, maxepoch, store_every, max_steps)
+
+    def _counts(self, burnin, maxepoch, store_every, max_steps):
+        self.numbatches = -(-self.N // self.m)
         total = (burnin + maxepoch) * self.numbatches
         self.total_steps = total if max_steps <= 0 else min(total, max_steps)
         self.nstore = (maxepoch * self.numbatches) // store_every
+
+    @classmethod
+    def from_X(cls, X, ys, length_scales, sigma_RBFs, phi_scale, Z, b, I, r, Q, m, epsw, epsU,
+               signal_var, burnin, maxepoch, seeds, sigma_w=1.0, langevin=True, stiefel=True,
+               store_every=1, max_steps=0, store=True, diag=False, stream=None, engine="auto"):
+        """An X-mode session (gpt_sgld_session_create_x): the sweep block of
+        kin40kExperiment.jl:67-74 without a phi per sweep.  Chain c trains on
+        ``feature(X, length_scales[c], sigma_RBFs[c], phi_scale, Z, b)``, formed on the device one
+        minibatch ahead of the steps (same doubles, same trajectory as a phi session on it).
+
+        ``X`` (N, D), ``Z`` and ``b`` (n, D): numpy arrays, or float64 device tensors of the
+        transposed torch shape ((D, N), (D, n): Julia column-major).  ``length_scales``: one row
+        per chain, (nchains, 1) or (nchains, D) (a device tensor is taken as is);
+        ``sigma_RBFs``: one value per chain; ``ys``: one device tensor (N,) or one per chain."""
+        import torch
+
+        def dev(a, what):
+            if isinstance(a, torch.Tensor):
+                if a.dtype != torch.float64 or not a.is_cuda or not a.is_contiguous():
+                    raise ValueError("%s must be a contiguous float64 device tensor" % what)
+                return a
+            a = np.asarray(a, dtype=np.float64)
+            return torch.from_numpy(np.ascontiguousarray(a.T if a.ndim == 2 else a)).cuda()
+        seeds = list(seeds)
+        nch = len(seeds)
+        Xd, Zd, bd = dev(X, "X"), dev(Z, "Z"), dev(b, "b")
+        D, N = Xd.shape
+        n = Zd.shape[1]
+        if Zd.shape != (D, n) or bd.shape != (D, n):
+            raise ValueError("Z and b must be (n, D) for X (N, D)")
+        if isinstance(length_scales, torch.Tensor):
+            lsd = dev(length_scales, "length_scales")
+        else:
+            ls = np.asarray(length_scales, dtype=np.float64)
+            ls = ls.reshape(nch, 1) if ls.ndim < 2 else ls
+            lsd = torch.from_numpy(np.ascontiguousarray(ls)).cuda()
+        if lsd.dim() != 2 or lsd.shape[0] != nch:
+            raise ValueError("length_scales needs one row per chain")
+        sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_RBFs, dtype=np.float64), (nch,)))
+        if not isinstance(ys, (list, tuple)):
+            ys = [ys]
+        ys = [dev(y, "y") for y in ys]
+        if len(ys) == 1 and nch > 1:
+            ys = ys * nch
+        if len(ys) != nch or any(y.numel() != N for y in ys):
+            raise ValueError("need one y of length N per chain or a shared one")
+        self = cls.__new__(cls)
+        self._keep = (Xd, Zd, bd, lsd, ys)
+        self.n, self.D, self.N, self.r, self.Q, self.m = int(n), int(D), int(N), r, Q, m
+        self.nchains = nch
+        I = np.asfortranarray(np.asarray(I, dtype=np.int32))
+        self.cfg = make_config(self.n, self.D, self.N, r, Q, m, epsw, epsU, signal_var, sigma_w,
+                               burnin, maxepoch, 0, langevin, stiefel, store_every, max_steps)
+        yy = (C.c_void_p * nch)(*[y.data_ptr() for y in ys])
+        sd = (C.c_uint64 * nch)(*[int(s) & (2 ** 64 - 1) for s in seeds])
+        if engine not in ENGINES:
+            raise ValueError("engine must be one of %s" % sorted(ENGINES))
+        flags = (1 if store else 0) | (2 if diag else 0) | ENGINES[engine]
+        h = C.c_void_p()
+        self._h = None
+        check(lib().gpt_sgld_session_create_x(
+            C.byref(self.cfg), nch, sd, C.c_void_p(Xd.data_ptr()), yy, C.c_void_p(lsd.data_ptr()),
+            int(lsd.shape[1]), sg.ctypes.data_as(_lib.P_D), float(phi_scale),
+            C.c_void_p(Zd.data_ptr()), C.c_void_p(bd.data_ptr()), I.ctypes.data_as(_lib.P_I32),
+            flags, C.c_void_p(stream) if stream else None, C.byref(h)))
+        self._h = h
+        self._counts(burnin, maxepoch, store_every, max_steps)
+        return self
+
+    def staging(self):
+        """dict(slots, bytes_per_chain, xmode) of gpt_sgld_session_staging: the batch slots of a
+        chain's feature ring and its staging bytes (an X session; zeros for a phi session)."""
+        out = (C.c_int64 * 3)()
+        check(lib().gpt_sgld_session_staging(self._h, out))
+        return dict(slots=int(out[0]), bytes_per_chain=int(out[1]), xmode=int(out[2]))
 
     def set_hyper(self, chain, epsw, epsU, signal_var, sigma_w=1.0):
         check(lib().gpt_sgld_session_set_hyper(self._h, chain, float(epsw), float(epsU),

@@ -108,6 +108,23 @@ int gpt_sgld_regression_chains(const gpt_sgld_config* cfg, int32_t nchains, cons
                                const double* epsw, const double* epsU, const double* signal_var,
                                double* const* w_store, double* const* U_store, int32_t* status);
 
+/* gpt_sgld_regression_chains from X (kin40kExperiment.jl:67-74: every sweep's phitrain is
+ * feature(Xtrain, n, length_scale_j, sigma_RBF_j, seed, scale) of the same Xtrain, Z and b): chain
+ * c's features are formed on the device, minibatch by minibatch, from X (N,D), Z (n,D), b (n,D)
+ * (shared), length_scale (ls_len, nchains) with ls_len 1 or D, sigma_rbf (nchains) and phi_scale,
+ * so no phi (n,D,N) is computed, held or copied: the same doubles gpt_feature makes, hence the
+ * same stores as gpt_sgld_regression_chains on feature(X, length_scale[:,c], sigma_rbf[c], ...).
+ * y[c], seeds, epsw / epsU / signal_var, w_store, U_store and status as there.  Each distinct
+ * host array is copied to the device once; every argument is checked before the first device
+ * call. */
+int gpt_sgld_regression_chains_x(const gpt_sgld_config* cfg, int32_t nchains, const uint64_t* seeds,
+                                 const double* X, const double* const* y,
+                                 const double* length_scale, int64_t ls_len,
+                                 const double* sigma_rbf, double phi_scale, const double* Z,
+                                 const double* b, const int32_t* I, const double* epsw,
+                                 const double* epsU, const double* signal_var,
+                                 double* const* w_store, double* const* U_store, int32_t* status);
+
 /* GPT_SGLDERM_RMSprop(phi,y,signal_var,I,r,Q,m,epsilon,alpha,burnin,maxepoch)
  * GPT_SGLD.jl:1121-1237: per-entry RMSprop step sizes for w, one averaged step per U^(k), w
  * updated before A.  cfg's epsw/epsU/sigma_w are not used (sigma_w = 1 as in the reference);
@@ -140,6 +157,27 @@ int gpt_sgld_session_create(const gpt_sgld_config* cfg, int32_t nchains, const u
                             const double* const* phi_dev, const double* const* y_dev,
                             const int32_t* I_host, int32_t store_on_device, void* hip_stream,
                             gpt_sgld_session** out);
+/* X mode: a session that trains from X (the sweep block of kin40kExperiment.jl:67-74, where the
+ * sweeps' phi differ only in length_scale and sigma_RBF).  It holds X_dev (N,D), Z_dev, b_dev
+ * (n,D) (device, column-major, shared by the chains), ls_dev (ls_len, nchains) (device; ls_len 1
+ * or D) and sigma_rbf (host, nchains), and never an n*D*N phi: before the steps that read them, a
+ * kernel writes the feature rows of the coming minibatches into a ring of a few batch slots per
+ * chain (gpt_sgld_session_staging), as the doubles gpt_feature_dev makes, and the step engines
+ * read the ring.  store_flags: bits 0, 1 (stores, diagnostics) and the engine bits 2, 3, 7; the
+ * RMSprop, w-only and classification steps and the stamps / timeline diagnostics are
+ * GPT_ERR_BAD_DIMS on an X session; every other session call works as for a phi session.  The
+ * arguments are checked before the first device call. */
+int gpt_sgld_session_create_x(const gpt_sgld_config* cfg, int32_t nchains, const uint64_t* seeds,
+                              const double* X_dev, const double* const* y_dev,
+                              const double* ls_dev, int64_t ls_len, const double* sigma_rbf,
+                              double phi_scale, const double* Z_dev, const double* b_dev,
+                              const int32_t* I_host, int32_t store_flags, void* hip_stream,
+                              gpt_sgld_session** out);
+/* out[3] = {batch slots KR of a chain's ring, staging bytes per chain = KR*m*(8*n*D + 8 + 4) for
+ * the feature rows, targets and row numbers + 4*2*N for the order view, 1 for an X session};
+ * {0, 0, 0} for a phi session.  KR = the steps of one launch + 1 (2 on the grid and wave engines,
+ * 9 on the chain engine, whose X-mode launches run 8 steps at most), whatever N. */
+int gpt_sgld_session_staging(gpt_sgld_session* s, int64_t* out);
 /* Per-chain step sizes / variances (a hyper-parameter sweep, kin40kExperiment.jl:67-74);
  * call before the first run. */
 int gpt_sgld_session_set_hyper(gpt_sgld_session* s, int32_t chain, double epsw, double epsU,

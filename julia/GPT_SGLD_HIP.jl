@@ -9,8 +9,8 @@
 # exactly as the reference functions allocate and return them.
 module GPT_SGLD_HIP
 
-export datawhitening, feature, featureNotensor, samplenz, GPTregression, GPTregression_chains,
-       GPT_SGLDERM, pred, RMSE,
+export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTregression, GPTregression_chains,
+       GPTregression_chains_x, GPT_SGLDERM, pred, RMSE,
        GPNT_SGLD, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
        init_state
 
@@ -56,6 +56,15 @@ function feature(X::Array{Float64,2}, n::Integer, length_scale, sigma_RBF::Real,
     check(ccall((:gpt_feature_inputs, LIB), Cint, (Int64, Int64, UInt64, Ptr{Float64}, Ptr{Float64}),
                 n, D, seed, Z, b))
     return feature(X, length_scale, sigma_RBF, scale, Z, b)
+end
+
+# The Z = randn(n,D), b = 2π·rand(n,D) that the seeded form above draws, for the entry points that
+# take X, Z and b in place of a phi (GPTregression_chains_x, pred_mean_x)
+function feature_inputs(n::Integer, D::Integer, seed::Integer)
+    Z = Array{Float64}(undef, n, D); b = Array{Float64}(undef, n, D)
+    check(ccall((:gpt_feature_inputs, LIB), Cint, (Int64, Int64, UInt64, Ptr{Float64}, Ptr{Float64}),
+                n, D, seed, Z, b))
+    return Z, b
 end
 
 # Generation-A seeded form feature(X,n,length_scale,seed) (GPT_SGLD_p.jl:40-54): Z = randn(n,D)
@@ -136,11 +145,18 @@ function GPTregression_chains(phis::Vector{Array{Float64,3}}, y::Array{Float64},
                               burnin::Integer, maxepoch::Integer, param_seeds::Vector{<:Integer};
                               sigma_w::Real=1.0, store_every::Integer=1)
     C = length(param_seeds)
+    C >= 1 || error("need at least one chain")
     length(phis) == C || error("one phi per chain")
     n, D, N = size(phis[1])
+    # the library reads n*D*N doubles of every phi, N of y, Q*D of I and C of every per-chain vector
+    all(p -> size(p) == (n, D, N), phis) || error("every phi must have the same (n, D, N)")
+    length(y) == N || error("phi and y disagree on N")
+    size(I) == (Q, D) || error("I must be (Q, D)")
     T = div(maxepoch * cld(N, m), store_every)
     perchain(v) = v isa Real ? fill(Float64(v), C) : collect(Float64, v)
     ew, eu, sv = perchain(epsw), perchain(epsU), perchain(signal_var)
+    length(ew) == C && length(eu) == C && length(sv) == C ||
+        error("epsw, epsU and signal_var: one value, or one per chain")
     cfg = Ref(SGLDConfig(n, D, N, r, Q, m, ew[1], eu[1], sv[1], sigma_w, burnin, maxepoch,
                          UInt64(0), Int32(1), Int32(1), store_every, 0))
     ws = [zeros(Q, T) for c = 1:C]; Us = [zeros(n, r, D, T) for c = 1:C]
@@ -152,6 +168,56 @@ function GPTregression_chains(phis::Vector{Array{Float64,3}}, y::Array{Float64},
                      Ptr{Ptr{Float64}}, Ptr{Int32}),
                     cfg, Int32(C), seeds, pointer.(phis), fill(pointer(yv), C), I, ew, eu, sv,
                     pointer.(ws), pointer.(Us), status))
+    end
+    for c = 1:C
+        status[c] == 1 && println("Get NaN when moving along Geodesic. Try smaller epsU")
+    end
+    return [(ws[c], Us[c], Int(status[c])) for c = 1:C]
+end
+
+# GPTregression_chains from X: the same sweep block without a phi per sweep.  Chain j trains on
+# feature(X, length_scales[:,j], sigma_RBFs[j], phi_scale, Z, b), which the library forms on the
+# device one minibatch ahead of the steps (gpt_sgld_regression_chains_x; the same doubles, so the
+# same stores as GPTregression_chains on those phis): the host computes, holds and uploads X, Z, b
+# and ls_len + 1 hyper-parameters per sweep instead of n*D*N doubles per sweep.
+# length_scales: (ls_len, C) with ls_len 1 or D (a Vector of C scalars is taken as (1, C)).
+function GPTregression_chains_x(X::Array{Float64,2}, y::Array{Float64}, length_scales,
+                                sigma_RBFs, phi_scale::Real, Z::Array{Float64,2},
+                                b::Array{Float64}, signal_var, I::Array{Int32,2}, r::Integer,
+                                Q::Integer, m::Integer, epsw, epsU, burnin::Integer,
+                                maxepoch::Integer, param_seeds::Vector{<:Integer};
+                                sigma_w::Real=1.0, store_every::Integer=1)
+    C = length(param_seeds)
+    C >= 1 || error("need at least one chain")
+    N, D = size(X); n = size(Z, 1)
+    ls = length_scales isa AbstractVector ? reshape(collect(Float64, length_scales), 1, :) :
+                                            collect(Float64, length_scales)
+    ls_len = size(ls, 1)
+    # the library reads N*D of X, n*D of Z and b, N of y, Q*D of I, ls_len*C length scales and C
+    # of every per-chain vector
+    (ls_len == 1 || ls_len == D) || error("dimensions of X and length_scale do not match")
+    size(ls, 2) == C || error("one column of length scales per chain")
+    size(Z) == (n, D) || error("Z must be (n, D)")
+    length(b) == n * D || error("b must be (n, D)")
+    length(y) == N || error("X and y disagree on N")
+    size(I) == (Q, D) || error("I must be (Q, D)")
+    perchain(v) = v isa Real ? fill(Float64(v), C) : collect(Float64, v)
+    sg, ew, eu, sv = perchain(sigma_RBFs), perchain(epsw), perchain(epsU), perchain(signal_var)
+    length(sg) == C && length(ew) == C && length(eu) == C && length(sv) == C ||
+        error("sigma_RBFs, epsw, epsU and signal_var: one value, or one per chain")
+    T = div(maxepoch * cld(N, m), store_every)
+    cfg = Ref(SGLDConfig(n, D, N, r, Q, m, ew[1], eu[1], sv[1], sigma_w, burnin, maxepoch,
+                         UInt64(0), Int32(1), Int32(1), store_every, 0))
+    ws = [zeros(Q, T) for c = 1:C]; Us = [zeros(n, r, D, T) for c = 1:C]
+    yv = vec(y); status = zeros(Int32, C); seeds = UInt64.(param_seeds)
+    GC.@preserve yv ws Us begin
+        check(ccall((:gpt_sgld_regression_chains_x, LIB), Cint,
+                    (Ref{SGLDConfig}, Int32, Ptr{UInt64}, Ptr{Float64}, Ptr{Ptr{Float64}},
+                     Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{Float64}},
+                     Ptr{Ptr{Float64}}, Ptr{Int32}),
+                    cfg, Int32(C), seeds, X, fill(pointer(yv), C), ls, ls_len, sg, phi_scale, Z, b,
+                    I, ew, eu, sv, pointer.(ws), pointer.(Us), status))
     end
     for c = 1:C
         status[c] == 1 && println("Get NaN when moving along Geodesic. Try smaller epsU")
