@@ -18,6 +18,7 @@ GPT_ERR_NOT_SPD = 5
 
 P_D = C.POINTER(C.c_double)
 P_I32 = C.POINTER(C.c_int32)
+P_U32 = C.POINTER(C.c_uint32)
 P_U64 = C.POINTER(C.c_uint64)
 
 
@@ -77,6 +78,9 @@ SIGNATURES = {
     "gpt_sgld_timeline_slots": (C.c_int64, []),
     "gpt_debug_expm_stamps": (C.c_int, [C.c_int32, C.c_int32, P_D, C.POINTER(C.c_int64)]),
     "gpt_debug_expm": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P_D, P_D, P_I32]),
+    "gpt_debug_fastmath": (C.c_int, [C.c_int32, C.c_int64, P_D, P_U32, P_D, P_D]),
+    "gpt_debug_normals": (C.c_int, [C.c_int32, C.c_uint64, C.c_uint32, C.c_int64, C.c_uint32,
+                                    C.c_uint32, C.c_uint32, P_D, P_U32]),
     "gpt_debug_gaussian_draw": (C.c_int, [C.c_int32, P_D, P_D, C.c_uint64, C.c_uint32, C.c_uint32,
                                           C.c_uint32, P_D, P_I32]),
     "gpt_pred_trim_pool": (C.c_int, []),

@@ -4,10 +4,14 @@
 // constants the compiler hoists into registers next to the kernels' resident U / gradU tiles.
 // Box–Muller only needs log on (0, 1] and sin/cos of 2πu with u in (0, 1), so:
 //   log: fdlibm's e_log.c scheme (s = f/(2+f), degree-14 minimax in s; on the device the
-//        quotient is f times a Newton-refined reciprocal) — error < 2 ulp;
+//        quotient is f times a Newton-refined reciprocal) — error < 2 ulp (measured on the device:
+//        0.71 ulp);
 //   sincos(2πu): exact quadrant reduction on 4u (no π rounding in the reduction), then
-//        fdlibm's __kernel_sin / __kernel_cos on |φ| <= π/4 — error < 1 ulp.
+//        fdlibm's __kernel_sin / __kernel_cos on |φ| <= π/4 — error < 2 ulp of the true value and
+//        < 2·2⁻⁵³ absolute (measured on the device: 1.20 ulp, 0.96·2⁻⁵³; the exactly rounded host
+//        path: 1.33 ulp); exactly 0 and ±1 at u = k/4.
 // Results can differ from glibc (the oracle's numpy) in the last bit; parity tolerances cover it.
+// The bounds are tested against mpmath on the device (tests/test_gpu_fastmath.py).
 //
 // The coefficients come from a table the caller passes (kernels pass an opaque pointer to a
 // __constant__ copy, so they are fetched by scalar loads at their use instead of being hoisted
@@ -37,7 +41,8 @@ namespace gpt {
    -1.98412698412698412698e-04, -5.0e-01, 4.16666666666666666667e-02,                           \
    -1.38888888888888888889e-03, 2.48015873015873015873e-05}
 
-// 1/x: on the device the hardware reciprocal plus two Newton steps (within 1 ulp)
+// 1/x: on the device the hardware reciprocal plus two Newton steps (within 1 ulp; measured on the
+// divisors 2 + f of fm_log_c: 0.499 ulp, correctly rounded on every one)
 GPT_HD double fm_rcp(double x) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(GPT_FM_OLD)
   double r = __builtin_amdgcn_rcp(x);
@@ -125,8 +130,10 @@ GPT_HD void fm_sincos_tab(uint32_t x, const TP* tab, double& sn, double& cs, CP 
 // (sin, cos)(2πj/16) and tab[32 + 2j], tab[33 + 2j] = (sin, cos)(2πj/256), j < 16, so i = 16·ih + il
 // takes the angle sum of entries ih and il first.  Each 16-entry table is 256 contiguous bytes —
 // every LDS bank once — so the per-lane 16-B reads of a wave never conflict (lanes with the same
-// entry share it; the 256-entry table's random rows cost ~3 passes per read).  Within 3 ulp of
-// fm_sincos_2pi_c.
+// entry share it; the 256-entry table's random rows cost ~3 passes per read).  Within 3·2⁻⁵³ of
+// fm_sincos_2pi_c and 4·2⁻⁵³ of the true value, both ABSOLUTE (measured on the device: 2.00 and
+// 1.87): near a zero of sin or cos the angle sum has no relative accuracy left (at x = 0xFFFFFFFF
+// about 7e7 ulp of a 7e-10 value), which Box–Muller, multiplying by a radius, does not see.
 template <class CP, class TP>
 GPT_HD void fm_sincos_tab2(uint32_t x, const TP* tab, double& sn, double& cs, CP c) {
   const unsigned ih = x >> 28, il = (x >> 24) & 15u;
@@ -146,9 +153,12 @@ GPT_HD void fm_sincos_tab2(uint32_t x, const TP* tab, double& sn, double& cs, CP
   cs = fma(ct, cp, -(st * sp));
 }
 
-// √x for finite normal x > 0 (the Box–Muller radius: x = −2 ln u in [2e-10, 46]): on the device
-// the hardware rsq refined by two Newton steps (the refinement of the library expansion without
-// its denormal scaling and class checks).
+// √x for finite normal x > 0 (the Box–Muller radius: x = −2 ln u in [2.2e-16, 75] for the 53-bit
+// uniforms, [2.3e-10, 46] for the 32-bit ones): on the device the hardware rsq refined by two
+// Newton steps (the refinement of the library expansion without its denormal scaling and class
+// checks).  Within 1 ulp of the exact root (measured on the device from 5.6e-17 to 46: 0.500 ulp);
+// the radius fm_sqrt_pos(−2·fm_log_c(u)) within 2 ulp of √(−2 ln u) (measured: 0.90 ulp).  x = ±0
+// gives NaN (rsq = ±Inf): u53 and u32u never return 1.
 GPT_HD double fm_sqrt_pos(double x) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(GPT_FM_OLD)
   double y = __builtin_amdgcn_rsq(x);

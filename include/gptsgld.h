@@ -235,6 +235,36 @@ int gpt_debug_expm(int32_t nn, int32_t count, int32_t mode, const double* A, dou
  * normals (seed, c1, c2, c3) of element e = 0..p-1; *status = 1 if M is not positive definite. */
 int gpt_debug_gaussian_draw(int32_t p, const double* M, const double* x, uint64_t seed, uint32_t c1,
                             uint32_t c2, uint32_t c3, double* out, int32_t* status);
+/* Test entry: one function of the noise path (gpt_amd/csrc/fastmath.h, gpt_common.h) evaluated on
+ * the device on `count` host inputs, called as the engines call it (coefficients through the
+ * constant table, the sin/cos tables filled in LDS by sincos_tab_fill).  fn:
+ *   0  fm_log_c(x[i]) -> out0                   5  the 64 doubles of the filled LDS table -> out0
+ *   1  fm_sqrt_pos(x[i]) -> out0                   (count must be 64; no input)
+ *   2  fm_rcp(x[i]) -> out0                     6  u53(xi[2i], xi[2i+1]) -> out0
+ *   3  fm_sincos_2pi_c(x[i]) -> sin out0,       7  u32u(xi[i]) -> out0
+ *      cos out1                                 8  fm_sqrt_pos(-2 fm_log_c(x[i])) -> out0, the
+ *   4  fm_sincos_tab2(xi[i]) -> sin out0,          Box–Muller radius as the generators form it
+ *      cos out1
+ * x is read by fn 0-3 and 8, xi by fn 4, 6 and 7, out1 is written by fn 3 and 4; the others may be
+ * null.  An unknown fn, count < 1 or > 2^24, or a missing array is GPT_ERR_BAD_DIMS. */
+int gpt_debug_fastmath(int32_t fn, int64_t count, const double* x, const uint32_t* xi, double* out0,
+                       double* out1);
+/* Test entry: Philox blocks c0 = c0_first .. c0_first + nblocks - 1 of stream (c1, c2, c3) under
+ * `seed` on the device: words[4b .. 4b+3] = the four raw Philox words of block b, and z = the
+ * normals generator `gen` makes of each block:
+ *   0  normal_at, elements 2 c0 and 2 c0 + 1      -> z[2b], z[2b+1]   (c0_first + nblocks <= 2^31:
+ *                                                     the element index is a 32-bit word)
+ *   1  normal_pair                                -> z[2b], z[2b+1]
+ *   2  normal_quad<4>                             -> z[4b .. 4b+3]
+ *   3  normal_quad<2> (the first pair)            -> z[2b], z[2b+1]
+ *   4  normal_quad_tab<4>                         -> z[4b .. 4b+3]
+ *   5  normal_quad_tab<2>                         -> z[2b], z[2b+1]
+ *   6  no device work: the host's philox4x32 words, and z[2b], z[2b+1] = the host's u53 of words
+ *      (0, 1) and (2, 3)
+ * c0_first + nblocks may reach 2^32 (gen 1-6).  An unknown gen, nblocks < 1 or > 2^24, a block
+ * range past the top, or a null array is GPT_ERR_BAD_DIMS. */
+int gpt_debug_normals(int32_t gen, uint64_t seed, uint32_t c0_first, int64_t nblocks, uint32_t c1,
+                      uint32_t c2, uint32_t c3, double* z, uint32_t* words);
 /* Timing of the wave engine's expm as geod calls it (three LDS slots, the first nn/2 result
  * columns), one wave per matrix: stamps[4·m + 0..3] = s_memtime at entry, after the Padé
  * polynomial, after the solve, at exit (diagnostics; scripts/expm_bench.py). */

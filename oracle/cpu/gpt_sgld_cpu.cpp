@@ -48,8 +48,10 @@ inline U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t se
   }
   return U4{c0, c1, c2, c3};
 }
-inline double u53(uint32_t a, uint32_t b) {
-  return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6) + 0.5) * (1.0 / 9007199254740992.0);
+inline double u53(uint32_t a, uint32_t b) {   // the all-ones words round to 1.0: clamped below 1
+  const double u =
+      ((double)(a >> 5) * 67108864.0 + (double)(b >> 6) + 0.5) * (1.0 / 9007199254740992.0);
+  return std::min(u, 0x1.fffffffffffffp-1);
 }
 // element e of normal stream (c1, c2, c3): Box–Muller on the block c0 = e >> 1
 inline double normal_at(uint64_t seed, uint32_t e, uint32_t c1, uint32_t c2, uint32_t c3) {

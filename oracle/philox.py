@@ -74,9 +74,14 @@ def philox4x32(c0, c1, c2, c3, seed):
 
 
 def _u53(a, b):
-    """Two uint32 words -> uniform double in (0, 1) with 53 random bits."""
-    return ((a >> np.uint32(5)).astype(np.float64) * 67108864.0
-            + (b >> np.uint32(6)).astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+    """Two uint32 words -> uniform double in (0, 1) with 53 random bits k: (k + 1/2)·2^-53 rounded
+    to a double.  From k = 2^52 up k + 1/2 is a tie and rounds to even, so the all-ones k would
+    give 1.0 (ln u = 0, radius 0); it is clamped to the largest double below 1."""
+    a = np.asarray(a, dtype=np.uint32)
+    b = np.asarray(b, dtype=np.uint32)
+    u = ((a >> np.uint32(5)).astype(np.float64) * 67108864.0
+         + (b >> np.uint32(6)).astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+    return np.minimum(u, 1.0 - 2.0 ** -53)
 
 
 def normals(count, seed, c1, c2, c3):

@@ -68,6 +68,54 @@ def test_feature_inputs_generation_a_host_matches_oracle():
     assert np.array_equal(Z, Zc)                           # the Z stream is shared with Gen C
 
 
+BIG_SEED = (0x299f31d0 << 32) | 0xa4093822
+
+
+def test_host_draws_take_the_whole_64_bit_seed():
+    """gpt_samplenz, gpt_sgld_init and gpt_feature_inputs under a seed above 2^32 (the Philox key's
+    second word is seed >> 32): equal to the oracle's, and not the draws of the low word alone."""
+    from gpt_amd import GPT_SGLD as G
+    low = BIG_SEED & 0xFFFFFFFF
+    I = G.samplenz(5, 8, 200, BIG_SEED)
+    assert (I == R.samplenz(5, 8, 200, BIG_SEED)).all()
+    assert not (I == G.samplenz(5, 8, 200, low)).all()
+    w, U = G.init_state(60, 5, 3, 40, BIG_SEED)
+    wo, Uo = R.init_state(60, 5, 3, 40, BIG_SEED)
+    assert np.abs(w - wo).max() == 0.0 and np.abs(U - Uo).max() < 1e-14
+    wl, Ul = G.init_state(60, 5, 3, 40, low)
+    assert np.abs(w - wl).max() > 1e-3 and np.abs(U - Ul).max() > 1e-3
+    Z, b = G.feature_inputs(30, 6, BIG_SEED)
+    Zo, bo = R.seeded_feature_inputs(30, 6, BIG_SEED)
+    assert np.abs(Z - Zo).max() < 1e-15 and np.abs(b - bo).max() < 1e-15
+    Zl, bl = G.feature_inputs(30, 6, low)
+    assert np.abs(Z - Zl).max() > 1e-3 and np.abs(b - bl).max() > 1e-3
+
+
+def test_host_philox_and_u53_equal_the_oracle():
+    """The host C++ philox4x32 and u53 (gpt_debug_normals gen 6, no device work) on every seed and
+    counter family of oracle/fastmath_cases.py and on the Random123 vectors."""
+    from gpt_amd import _lib
+    from oracle import fastmath_cases as FC
+    from oracle import philox as P
+
+    def host(case):
+        seed, c0, nb, c1, c2, c3 = case
+        z = np.zeros((nb, 2))
+        w = np.zeros((nb, 4), dtype=np.uint32)
+        _lib.check(_lib.lib().gpt_debug_normals(FC.GEN_HOST, seed, c0, nb, c1, c2, c3,
+                                                z.ctypes.data_as(_lib.P_D),
+                                                w.ctypes.data_as(_lib.P_U32)))
+        return z, w
+    for ctr, key, want in FC.KAT:
+        _, w = host((key[0] | (key[1] << 32), ctr[0], 1, ctr[1], ctr[2], ctr[3]))
+        assert tuple(int(v) for v in w[0]) == want
+    for case in FC.stream_cases():
+        z, w = host(case)
+        assert np.array_equal(w, FC.case_words(case)), case
+        assert np.array_equal(z[:, 0], P._u53(w[:, 0], w[:, 1]))
+        assert np.array_equal(z[:, 1], P._u53(w[:, 2], w[:, 3]))
+
+
 def test_bad_arguments_fail_without_device():
     from gpt_amd import GPT_SGLD as G
     from gpt_amd._lib import GPTError

@@ -144,6 +144,9 @@ def test_every_ccall_matches_the_header():
         for i, (jt, ct) in enumerate(zip(types, cparams)):
             assert ct in C2J, "unmapped C type %r (%s arg %d)" % (ct, sym, i)
             assert jt in C2J[ct], "%s: %s arg %d is %s, C wants %s" % (fname, sym, i, jt, ct)
+            if ct == "uint64_t":      # a seed: no 32-bit conversion in the expression passed either
+                assert not re.search(r"Int32|Cu?int\b|%", args[i]), "%s: %s arg %d narrows: %s" % (
+                    fname, sym, i, args[i])
 
 
 def test_sgld_config_mirror_matches_the_header():
