@@ -24,6 +24,8 @@ Same function names, argument meaning, return values and error behaviour as the 
     pred_mean_x(w_store, U_store, I, Xtest, ytest, ls, σ, scale, Z, b)  fused feature + pred
     GPNT_SGLD(phi, y, signal_var, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch,
               param_seed)                                     GPT_SGLD.jl:809
+    NoTensorMarginal(X, y, Z, b), GPNT_nlogmarginal, GPNT_gradnlogmarginal, GPNT_hyperparameters,
+    GPNT_hyperparameters_optim                                GPT_SGLD.jl:921-1002
     datawhitening(X), proj, geod are not on the device path (host prep / inside the kernel).
 
 Arrays follow Julia's column-major layout: ``phi`` is (n, D, N) Fortran-ordered, ``U`` is
@@ -562,3 +564,142 @@ def GPNT_SGLD(phi, y, signal_var, sigma_theta, m, eps_theta, decay_rate, burnin,
         return np.zeros(n)
     check(code)
     return out
+
+
+# ------------------------------------------------------------------ full-theta model: hyper-parameters
+class NoTensorMarginal:
+    """Device-resident Gaussian marginal likelihood of the no-tensor RFF GP (GPT_SGLD.jl:921-962
+    with featureNotensor / gradfeatureNotensor as the feature closures).
+
+    ``X`` (N, D), ``y`` (N), ``Z`` (n, D), ``b`` (n) are uploaded once; every method takes
+    ``h = [length_scale (D entries, or one: the scalar form); sigma_RBF; signal_var]``.
+    n <= 1024, D <= 16.  A failed Cholesky raises ``GPTError`` (GPT_ERR_NOT_SPD), as the
+    reference's ``cholfact`` throws."""
+
+    def __init__(self, X, y, Z, b):
+        X = _f64(X)
+        if X.ndim != 2:
+            raise ValueError("X must be (N, D)")
+        N, D = X.shape
+        Z = _f64(Z)
+        n = Z.shape[0]
+        y = _f64(np.asarray(y, dtype=np.float64).ravel())
+        b = _f64(np.asarray(b, dtype=np.float64).ravel())
+        if Z.shape != (n, D) or b.size != n or y.size != N:
+            raise ValueError("Z must be (n, D), b of length n and y of length N")
+        self.n, self.N, self.D = n, N, D
+        self._h = C.c_void_p()
+        check(lib().gpt_nlml_create(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), n, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gpt_nlml_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # interpreter shutdown: the library may be gone already
+            pass
+
+    def _eval(self, h, want_grad, want_theta=False):
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        val = C.c_double()
+        grad = np.empty(h.size) if want_grad else None
+        theta = np.empty(self.n) if want_theta else None
+        check(lib().gpt_nlml_eval(self._h, _ptr(h), h.size, 1 if want_grad else 0, C.byref(val),
+                                  _ptr(grad) if want_grad else None,
+                                  _ptr(theta) if want_theta else None))
+        return val.value, grad, theta
+
+    def nlogmarginal(self, h):
+        return self._eval(h, False)[0]
+
+    def gradnlogmarginal(self, h):
+        return self._eval(h, True)[1]
+
+    def value_and_grad(self, h):
+        return self._eval(h, True)[:2]
+
+    def theta_mean(self, h):
+        """l = A^-1 phi y at h: the posterior mean of the full-theta weights."""
+        return self._eval(h, False, True)[2]
+
+    def features(self, sin=False):
+        """phi (n, N) of the last evaluation (and S = c sin f of the last gradient one)."""
+        phi = np.empty((self.n, self.N), order="F")
+        S = np.empty((self.n, self.N), order="F") if sin else None
+        check(lib().gpt_nlml_features(self._h, _ptr(phi), _ptr(S) if sin else None))
+        return (phi, S) if sin else phi
+
+
+def _marginal(obj, what):
+    if not isinstance(obj, NoTensorMarginal):
+        raise TypeError("%s must be a NoTensorMarginal (it stands for the reference's closure over "
+                        "featureNotensor / gradfeatureNotensor)" % what)
+    return obj
+
+
+def GPNT_nlogmarginal(y, n, hyperparams, randfeature):
+    """GPT_SGLD.jl:921-933 with ``randfeature`` a NoTensorMarginal (which holds y and n)."""
+    return _marginal(randfeature, "randfeature").nlogmarginal(hyperparams)
+
+
+def GPNT_gradnlogmarginal(y, n, hyperparams, randfeature, gradfeature):
+    """GPT_SGLD.jl:939-962 with ``randfeature`` and ``gradfeature`` the same NoTensorMarginal."""
+    _marginal(gradfeature, "gradfeature")
+    return _marginal(randfeature, "randfeature").gradnlogmarginal(hyperparams)
+
+
+def gpnt_nlogmarginal_oneshot(X, y, Z, b, hyperparams, want_grad=True):
+    """The one-shot host-pointer entry the Julia shim binds (gpt_gpnt_nlogmarginal)."""
+    X = _f64(X)
+    N, D = X.shape
+    Z = _f64(Z)
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    b = _f64(np.asarray(b, dtype=np.float64).ravel())
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    val = C.c_double()
+    grad = np.empty(h.size)
+    check(lib().gpt_gpnt_nlogmarginal(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), Z.shape[0], _ptr(h),
+                                      h.size, 1 if want_grad else 0, C.byref(val), _ptr(grad)))
+    return (val.value, grad) if want_grad else val.value
+
+
+def _log_space_minimize(nlogmarginal, gradnlogmarginal, init_hyperparams, bounds, xtol, ftol):
+    from scipy.optimize import minimize
+
+    def fun(lh):
+        h = np.exp(lh)
+        return float(nlogmarginal(h)), np.asarray(gradnlogmarginal(h), dtype=np.float64) * h
+    x0 = np.log(np.asarray(init_hyperparams, dtype=np.float64))
+    # ftol is a relative decrease of the objective as in the reference's optimisers; xtol has no
+    # L-BFGS-B counterpart and bounds the projected gradient instead
+    res = minimize(fun, x0, jac=True, method="L-BFGS-B", bounds=bounds,
+                   options={"ftol": float(ftol), "gtol": float(xtol), "maxiter": 200})
+    return np.exp(res.x), float(res.fun)
+
+
+def GPNT_hyperparameters(nlogmarginal, gradnlogmarginal, init_hyperparams, lbounds, xtol=1e-4,
+                         ftol=1e-3):
+    """GPT_SGLD.jl:971-989: minimise ``nlogmarginal`` over positive hyper-parameters bounded below
+    by ``lbounds`` (a scalar or one per entry).  Returns ``(minx, minf)``.
+
+    The optimiser differs from the reference's: NLopt's ``:LD_MMA`` is replaced by
+    ``scipy.optimize.minimize(method="L-BFGS-B")`` over log-hyper-parameters with the chain-rule
+    gradient ``g·h`` (as :992-993) and the bounds taken to log space, so iterates and stopping
+    point are not the reference's.  Only the objective and its gradient are parity-tested."""
+    init = np.asarray(init_hyperparams, dtype=np.float64)
+    lb = np.broadcast_to(np.asarray(lbounds, dtype=np.float64), init.shape)
+    if (lb <= 0).any() or (init < lb).any():
+        raise ValueError("lbounds must be positive and below init_hyperparams")
+    return _log_space_minimize(nlogmarginal, gradnlogmarginal, init,
+                               [(math.log(v), None) for v in lb], xtol, ftol)
+
+
+def GPNT_hyperparameters_optim(nlogmarginal, gradnlogmarginal, init_hyperparams, xtol=1e-4,
+                               ftol=1e-3):
+    """GPT_SGLD.jl:991-1002: the unconstrained form over log-hyper-parameters.  Returns
+    ``(minx, minf)``.  Optim.jl's ``:cg`` is replaced by L-BFGS-B without bounds (see
+    GPNT_hyperparameters); only the objective and its gradient are parity-tested."""
+    return _log_space_minimize(nlogmarginal, gradnlogmarginal, init_hyperparams, None, xtol, ftol)

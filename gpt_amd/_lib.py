@@ -107,6 +107,14 @@ SIGNATURES = {
                                 C.c_int64, C.c_int64, C.c_int64, C.c_double, P_D, P_D]),
     "gpt_gpnt_sgld": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64,
                                 C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_uint64, P_D]),
+    "gpt_nlml_create": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_int64,
+                                  C.POINTER(C.c_void_p)]),
+    "gpt_nlml_eval": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int32, P_D, P_D, P_D]),
+    "gpt_nlml_eval_timed": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int32, P_D, P_D, P_D]),
+    "gpt_nlml_features": (C.c_int, [C.c_void_p, P_D, P_D]),
+    "gpt_nlml_destroy": (C.c_int, [C.c_void_p]),
+    "gpt_gpnt_nlogmarginal": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_int64, P_D,
+                                        C.c_int64, C.c_int64, P_D, P_D]),
     "gpt_sgld_wonly": (C.c_int, [C.POINTER(SGLDConfig), P_D, P_D, P_I32, P_D, P_D, P_D, P_D, P_D]),
     "gpt_pred_mean_x": (C.c_int, [P_D, P_D, P_I32, P_D, P_D, C.c_int64, C.c_int64, P_D, C.c_int64,
                                   C.c_double, C.c_double, P_D, P_D, C.c_int64, C.c_int64, C.c_int64,

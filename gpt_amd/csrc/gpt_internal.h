@@ -325,6 +325,15 @@ hipError_t gaussian_draw_dense(const double* A, int p, long long N, const double
                                double beta, double ysc, uint64_t seed, uint32_t c1, uint32_t c2,
                                uint32_t c3, double* M, double* x, double* z, double* out,
                                int32_t* status, hipStream_t st);
+// tgp.hip's dense kernels for other translation units: M = alpha·A·Aᵀ + beta·I (lower 16 × 16
+// tiles, fp64 MFMA), out = alpha·A·y, the Cholesky factor in place (blocked for p <= 1024, with Lᵀ
+// in the upper triangle) and x := L⁻¹x / L⁻ᵀx against it.
+hipError_t dense_syrk(const double* A, int p, long long N, double alpha, double beta, double* M,
+                      hipStream_t st);
+hipError_t dense_gemv(const double* A, int p, long long N, const double* y, double alpha,
+                      double* out, hipStream_t st);
+void dense_chol(double* M, int p, int32_t* status, hipStream_t st);
+void dense_trsv(const double* M, int p, double* x, int trans, hipStream_t st);
 bool gmc_supported(int n, int r);
 hipError_t gmc_run(const double* phi, const double* y, const int32_t* I0, int n, int D,
                    long long N, int r, int Q, double signal_var, double epsw, double epsU,

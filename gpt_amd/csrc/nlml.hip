@@ -1,0 +1,591 @@
+// Gaussian marginal likelihood of the no-tensor random-Fourier-feature GP and its gradient with
+// respect to [length_scale; sigma_RBF; signal_var] (GPNT_nlogmarginal / GPNT_gradnlogmarginal,
+// GPT_SGLD.jl:921-962, with gradfeatureNotensor :142-177) for MI355X (gfx950).  DESIGN §6c.
+//
+// phi (n × N) = c·cos f, S = c·sin f, f = Zt·Xᵀ + b, Zt = Z ./ ℓ, c = sqrt(2/n)·σ_RBF;
+// A = phi·phiᵀ + σ²I = L·Lᵀ, bv = phi·y, l = A⁻¹bv.  The value needs only those (tgp.hip's SYRK,
+// GEMV, Cholesky and triangular solves).  The reference's gradient forms dphi/dh for every
+// hyper-parameter and runs a GEMM and two n × n solves on each; here, with P = A⁻¹, e = phiᵀl − y,
+// W = P·phi and T = S ∘ (W + l·eᵀ/σ²),
+//   d/dℓ_k = (1/ℓ_k) Σ_j Zt[j,k]·(T·X)[j,k],   d/dσ_RBF = (n − σ² tr P − lᵀl)/σ_RBF,
+//   d/dσ²  = (N−n)/(2σ²) + tr P/2 + (lᵀbv − yᵀy)/(2σ⁴) + lᵀl/(2σ²):
+// one GEMM (W, never stored) whose epilogue contracts with S and X.  All fp64, no atomics, every
+// sum in a fixed order.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <type_traits>
+#include <vector>
+
+#include "device_util.h"
+
+namespace gpt {
+
+typedef double nd4 __attribute__((ext_vector_type(4)));
+typedef double nd2 __attribute__((ext_vector_type(2)));
+
+constexpr int kNlmlNMax = 1024;      // the blocked single-workgroup Cholesky's limit
+
+// phi[j + n i] = c·cos(f), S[j + n i] = c·sin(f): the argument formed exactly as
+// feature_notensor_kernel forms it, so phi is gpt_feature_notensor's double.  S may be null.
+__global__ __launch_bounds__(256) void nlml_feature_kernel(
+    const double* __restrict__ X, long long N, int D, const double* __restrict__ ls, double c,
+    const double* __restrict__ Z, const double* __restrict__ b, int n, double* __restrict__ phi,
+    double* __restrict__ S) {
+  const long long total = (long long)n * N;
+  for (long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x; x < total;
+       x += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(x % n);
+    const long long i = x / n;
+    double s = 0.0;
+    for (int k = 0; k < D; ++k)
+      s = __dadd_rn(s, __dmul_rn(X[i + N * k], __dmul_rn(Z[j + (long long)n * k], 1.0 / ls[k])));
+    const double f = __dadd_rn(s, b[j]);
+    phi[x] = c * cos(f);
+    if (S) S[x] = c * sin(f);
+  }
+}
+
+// e[i] = Σ_j phi[j + n i]·l[j] − y[i]: one wave per data column, lanes over j (coalesced), the
+// lane sums combined in wave_sum's fixed pattern.
+__global__ __launch_bounds__(256) void nlml_resid_kernel(const double* __restrict__ phi,
+                                                         const double* __restrict__ l,
+                                                         const double* __restrict__ y, int n,
+                                                         long long N, double* __restrict__ e) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= N) return;
+  const double* col = phi + (size_t)n * i;
+  double s = 0.0;
+  for (int j = lane; j < n; j += 64) s = fma(col[j], l[j], s);
+  s = wave_sum(s);
+  if (lane == 0) e[i] = s - y[i];
+}
+
+// Xt = L⁻ᵀ (column-major n × n, Xt[c + n i] = (L⁻¹)[i, c]; the caller zeroes it first) from the
+// factor chol_blk_kernel leaves: L in the lower triangle, Lᵀ in the upper one.  One workgroup per
+// block of kTiRC right-hand-side columns of the identity; rows in panels of 16 from the block's
+// first row down (the rows above are zero).  Per panel: the 256 threads hold one (row, column)
+// entry each and subtract Σ_k L[i,k]·X[k,c] over the rows solved so far, with L[i, k..] read from
+// the upper triangle (contiguous in k) through LDS in chunks of kTiKC and the solved X block kept
+// in LDS; then 16 threads solve the panel's 16 × 16 triangle, a column each.
+constexpr int kTiRC = 16;
+constexpr int kTiKC = 128;
+static size_t trinv_lds_bytes(int n) {
+  const int NP = (n + 15) / 16 * 16;
+  return 8 * ((size_t)NP * kTiRC + 16 * (kTiKC + 1) + 2 * 16 * 17);
+}
+__global__ __launch_bounds__(256) void nlml_trinv_kernel(const double* __restrict__ M, int n,
+                                                         double* __restrict__ Xt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int NP = (n + 15) / 16 * 16;
+  double* Xs = (double*)smem;                  // Xs[(i − c0)·16 + c]
+  double* Lp = Xs + (size_t)NP * kTiRC;        // Lp[row·(kTiKC+1) + k]
+  double* Tr = Lp + 16 * (kTiKC + 1);          // the panel's triangle, Tr[row·17 + col]
+  double* Ac = Tr + 16 * 17;                   // right-hand sides of the triangle solve
+  const int tid = threadIdx.x, il = tid & 15, cl = tid >> 4;
+  const int c0 = blockIdx.x * kTiRC;
+  for (int r0 = c0; r0 < NP; r0 += 16) {
+    double a = (r0 + il == c0 + cl) ? 1.0 : 0.0;
+    for (int kc = c0; kc < r0; kc += kTiKC) {
+      const int len = min(kTiKC, r0 - kc);
+      __syncthreads();
+      for (int x = tid; x < 16 * len; x += 256) {
+        const int ii = x / len, kk = x - ii * len, i = r0 + ii;
+        Lp[ii * (kTiKC + 1) + kk] = i < n ? M[(size_t)(kc + kk) + (size_t)n * i] : 0.0;
+      }
+      __syncthreads();
+      const double* lrow = Lp + il * (kTiKC + 1);
+      const double* xcol = Xs + (size_t)(kc - c0) * kTiRC + cl;
+      for (int kk = 0; kk < len; ++kk) a -= lrow[kk] * xcol[(size_t)kk * kTiRC];
+    }
+    {
+      const int i = r0 + il, k = r0 + cl;
+      Tr[il * 17 + cl] = (i < n && cl <= il) ? M[(size_t)i + (size_t)n * k] : (il == cl ? 1.0 : 0.0);
+      Ac[il * 17 + cl] = a;
+    }
+    __syncthreads();
+    if (tid < kTiRC) {
+      double x[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        double s = Ac[i * 17 + tid];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= Tr[i * 17 + k] * x[k];
+        x[i] = s / Tr[i * 17 + i];
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) Xs[(size_t)(r0 - c0 + i) * kTiRC + tid] = x[i];
+    }
+    __syncthreads();
+    {
+      const int i = r0 + (tid >> 4), c = c0 + (tid & 15);
+      if (i < n && c < n) Xt[(size_t)c + (size_t)n * i] = Xs[(size_t)(i - c0) * kTiRC + (tid & 15)];
+    }
+  }
+}
+
+// The SYRK writes the lower 16 × 16 tiles: mirror them (nlml_grad_kernel reads whole rows).
+__global__ __launch_bounds__(256) void nlml_mirror_kernel(double* __restrict__ P, int n) {
+  const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (x >= (long long)n * n) return;
+  const int a = (int)(x % n), c = (int)(x / n);
+  if (a < c) P[x] = P[(size_t)c + (size_t)n * a];
+}
+
+// The gradient's hot path.  W = P·phi on v_mfma_f64_16x16x4f64 with K = n, never stored: a wave
+// owns 32 features j (two 16-wide tiles) of one block of CB data columns and walks the block 32
+// columns at a time (2 × 2 MFMA tiles).  The MFMA's first operand is phi (rows ↔ data columns i)
+// and its second P (columns ↔ features j; P is symmetric, so row j is contiguous in K), so lane λ
+// receives D[i = (λ>>4) + 4·reg][j = λ&15]: the sum over i of T[j,i]·X[i,k] runs inside the lane
+// over reg and over the tiles of the block (g[·][k], D <= DP registers), and only the four lane
+// groups λ>>4 are combined at the end (two exchange rounds).  Both operands are K-contiguous:
+// lane λ loads the K pair 2(λ>>4) + {0,1} of its row as one 16-B load (n even) and the halves go
+// to two MFMAs, two operand sets in flight, addresses clamped in-row so the loop has no branch
+// (pred_temp_mfma_kernel's scheme).  Lanes of rows i >= N or features j >= n read row 0 and their
+// T is selected to an exact zero.  part[(cb·n + j)·D + k] = Σ_{i in block cb} T[j,i]·X[i,k].
+template <bool V2, int DP>
+__global__ __launch_bounds__(256) void nlml_grad_kernel(
+    const double* __restrict__ P, const double* __restrict__ phi, const double* __restrict__ S,
+    const double* __restrict__ l, const double* __restrict__ e, const double* __restrict__ X, int n,
+    long long N, int D, int CB, int ncb, double inv_s2, double* __restrict__ part) {
+  const int lane = threadIdx.x & 63, wv = uni(threadIdx.x >> 6), kl = lane >> 4, li = lane & 15;
+  const int npair = ((n + 15) / 16 + 1) / 2;
+  const long long task = (long long)blockIdx.x * 4 + wv;
+  if (task >= (long long)ncb * npair) return;
+  const int cb = (int)(task / npair), jp = (int)(task - (long long)cb * npair);
+  const long long i_begin = (long long)cb * CB, i_end = min(N, i_begin + CB);
+  const int j0 = jp * 32;
+  const double* pb[2];
+  double lj[2];
+  bool jok[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int j = j0 + 16 * u + li;
+    jok[u] = j < n;
+    pb[u] = P + (size_t)n * (jok[u] ? j : 0);
+    lj[u] = l[jok[u] ? j : 0];
+  }
+  double g[2][DP];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int k = 0; k < DP; ++k) g[u][k] = 0.0;
+
+  auto ld = [&](const double* p, int j, double& x0, double& x1) {
+    if constexpr (V2) {              // n even: j even, rows 16-B aligned
+      const nd2 v = *(const nd2*)(p + min(j, n - 2));
+      x0 = v[0]; x1 = v[1];
+    } else {
+      x0 = p[min(j, n - 1)];
+      x1 = p[min(j + 1, n - 1)];
+    }
+  };
+  struct Ops { double a0[2], a1[2], b0[2], b1[2]; };
+  const int nfull = n & ~15;
+
+  for (long long it = i_begin; it < i_end; it += 32) {
+    const double* pa[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const long long i = it + 16 * t + li;
+      pa[t] = phi + (size_t)n * (i < i_end ? i : i_begin);
+    }
+    nd4 acc[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) acc[t][u] = nd4{0.0, 0.0, 0.0, 0.0};
+    auto load = [&](int j, Ops& o) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) ld(pa[t], j, o.a0[t], o.a1[t]);
+#pragma unroll
+      for (int u = 0; u < 2; ++u) ld(pb[u], j, o.b0[u], o.b1[u]);
+    };
+    auto ktail = [&](int j, Ops& o) {    // zero the phi halves past n (one operand suffices)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        o.a0[t] = j < n ? o.a0[t] : 0.0;
+        o.a1[t] = j + 1 < n ? o.a1[t] : 0.0;
+      }
+    };
+    auto mma = [&](const Ops& o) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+          acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0[t], o.b0[u], acc[t][u], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+          acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1[t], o.b1[u], acc[t][u], 0, 0, 0);
+    };
+    Ops Xo, Yo;
+    load(2 * kl, Xo);
+    for (int k0 = 0; k0 < nfull; k0 += 16) {
+      load(k0 + 8 + 2 * kl, Yo);
+      mma(Xo);
+      load(k0 + 16 + 2 * kl, Xo);
+      mma(Yo);
+    }
+    if (nfull < n) {
+      load(nfull + 8 + 2 * kl, Yo);
+      ktail(nfull + 2 * kl, Xo);
+      ktail(nfull + 8 + 2 * kl, Yo);
+      mma(Xo);
+      mma(Yo);
+    }
+    // epilogue in the MFMA output layout: acc[t][u][reg] = W[j0 + 16u + li, it + 16t + kl + 4reg]
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const long long i = it + 16 * t + kl + 4 * reg;
+        const bool iok = i < i_end;
+        const long long ic = iok ? i : i_begin;
+        const double ei = e[ic] * inv_s2;
+        double xv[DP];
+#pragma unroll
+        for (int k = 0; k < DP; ++k) xv[k] = k < D ? X[ic + N * k] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int jc = jok[u] ? j0 + 16 * u + li : 0;
+          const double sv = S[(size_t)jc + (size_t)n * ic];
+          const double tv = (iok && jok[u]) ? sv * (acc[t][u][reg] + lj[u] * ei) : 0.0;
+#pragma unroll
+          for (int k = 0; k < DP; ++k) g[u][k] = fma(tv, xv[k], g[u][k]);
+        }
+      }
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int k = 0; k < DP; ++k) {
+      double v = self_sum<32>(g[u][k], lane);
+      v = self_sum<16>(v, lane);
+      if (kl == 0 && jok[u] && k < D) part[((size_t)cb * n + (j0 + 16 * u + li)) * D + k] = v;
+    }
+}
+
+// gl[k] = (1/ℓ_k) Σ_j Zt[j,k]·Σ_cb part[cb][j][k]: the column blocks in block order, then the
+// features over the workgroup (blk_sum's fixed pattern).  One workgroup per k.
+__global__ __launch_bounds__(kNT) void nlml_finish_kernel(const double* __restrict__ part, int ncb,
+                                                          const double* __restrict__ Z,
+                                                          const double* __restrict__ ls, int n,
+                                                          int D, double* __restrict__ gl) {
+  __shared__ double red[kNW];
+  const int k = blockIdx.x;
+  const double inv = 1.0 / ls[k];
+  double s = 0.0;
+  for (int j = threadIdx.x; j < n; j += kNT) {
+    double gsum = 0.0;
+    for (int cb = 0; cb < ncb; ++cb) gsum += part[((size_t)cb * n + j) * D + k];
+    s = fma(__dmul_rn(Z[j + (size_t)n * k], inv), gsum, s);
+  }
+  const double tot = blk_sum(s, red);
+  if (threadIdx.x == 0) gl[k] = tot / ls[k];
+}
+
+// out = {Σ log diag(L), yᵀy, bvᵀl, lᵀl, tr P (0 when P is null)}
+__global__ __launch_bounds__(kNT) void nlml_scalars_kernel(const double* __restrict__ M,
+                                                           const double* __restrict__ P,
+                                                           const double* __restrict__ y,
+                                                           const double* __restrict__ bv,
+                                                           const double* __restrict__ l, int n,
+                                                           long long N, double* __restrict__ out) {
+  __shared__ double red[kNW];
+  double ld = 0.0, yy = 0.0, bl = 0.0, ll = 0.0, tp = 0.0;
+  for (int j = threadIdx.x; j < n; j += kNT) {
+    ld += log(M[(size_t)j + (size_t)n * j]);
+    bl = fma(bv[j], l[j], bl);
+    ll = fma(l[j], l[j], ll);
+    if (P) tp += P[(size_t)j + (size_t)n * j];
+  }
+  for (long long i = threadIdx.x; i < N; i += kNT) yy = fma(y[i], y[i], yy);
+  const double a = blk_sum(ld, red), b = blk_sum(yy, red), c = blk_sum(bl, red),
+               d = blk_sum(ll, red), f = blk_sum(tp, red);
+  if (threadIdx.x == 0) { out[0] = a; out[1] = b; out[2] = c; out[3] = d; out[4] = f; }
+}
+
+template <bool V2>
+static hipError_t launch_grad(int D, unsigned grid, hipStream_t st, const double* P,
+                              const double* phi, const double* S, const double* l, const double* e,
+                              const double* X, int n, long long N, int CB, int ncb, double inv_s2,
+                              double* part) {
+#define NLML_GRAD(DP)                                                                          \
+  hipLaunchKernelGGL((nlml_grad_kernel<V2, DP>), dim3(grid), dim3(256), 0, st, P, phi, S, l, e, X, \
+                     n, N, D, CB, ncb, inv_s2, part)
+  if (D <= 1) NLML_GRAD(1);
+  else if (D <= 2) NLML_GRAD(2);
+  else if (D <= 4) NLML_GRAD(4);
+  else if (D <= 8) NLML_GRAD(8);
+  else NLML_GRAD(16);
+#undef NLML_GRAD
+  return hipGetLastError();
+}
+
+}  // namespace gpt
+
+using namespace gpt;
+
+// ------------------------------------------------------------------------------ host side
+struct gpt_nlml {
+  int n = 0, D = 0, CB = 0, ncb = 0;
+  long long N = 0;
+  double *X = nullptr, *y = nullptr, *Z = nullptr, *b = nullptr, *ls = nullptr, *phi = nullptr,
+         *S = nullptr, *A = nullptr, *Xt = nullptr, *P = nullptr, *bv = nullptr, *l = nullptr,
+         *e = nullptr, *part = nullptr, *gl = nullptr, *scal = nullptr;
+  int32_t* status = nullptr;
+  bool have_features = false, have_sin = false;
+  std::vector<void*> mem;
+  std::vector<hipEvent_t> ev;         // gpt_nlml_eval_timed's phase marks
+  ~gpt_nlml() {
+    for (void* p : mem) (void)hipFree(p);
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+};
+
+#define NLCHK(call)                                    \
+  do {                                                 \
+    hipError_t _e = (call);                            \
+    if (_e != hipSuccess) return hip_fail(_e, #call);  \
+  } while (0)
+
+static bool nlml_dims_ok(const void* X, int64_t N, int64_t D, const void* y, const void* Z,
+                         const void* b, int64_t n) {
+  if (!X || !y || !Z || !b) { set_error("nlml: null input array"); return false; }
+  if (n < 1 || n > kNlmlNMax) { set_error("nlml: n must be in 1..1024"); return false; }
+  if (N < 1 || N > (1LL << 31) - 1) { set_error("nlml: N must be in 1..2^31-1"); return false; }
+  if (D < 1 || D > kDMax) { set_error("nlml: D must be in 1..16"); return false; }
+  return true;
+}
+
+static bool nlml_hyper_ok(const double* hyper, int64_t Lh, int64_t D) {
+  if (!hyper) { set_error("nlml: null hyperparams"); return false; }
+  if (Lh != 3 && Lh != D + 2) { set_error("nlml: hyperparams must have 3 or D + 2 entries"); return false; }
+  for (int64_t k = 0; k < Lh; ++k)
+    if (!(hyper[k] > 0.0) || !std::isfinite(hyper[k])) {
+      set_error("nlml: hyperparams must be positive and finite");
+      return false;
+    }
+  return true;
+}
+
+// column block of the gradient GEMM: the largest of 256 .. 32 columns that still gives 256
+// workgroups (a function of the shape alone, so that equal shapes sum in the same order)
+static int nlml_col_block(int n, long long N) {
+  const long long npair = ((n + 15) / 16 + 1) / 2;
+  for (int cb = 256; cb > 32; cb /= 2)
+    if (((N + cb - 1) / cb) * npair >= 4 * 256) return cb;
+  return 32;
+}
+
+extern "C" int gpt_nlml_create(const double* X, int64_t N, int64_t D, const double* y,
+                               const double* Z, const double* b, int64_t n, gpt_nlml** out) {
+  if (!out) { set_error("nlml: null handle pointer"); return GPT_ERR_BAD_DIMS; }
+  *out = nullptr;
+  if (!nlml_dims_ok(X, N, D, y, Z, b, n)) return GPT_ERR_BAD_DIMS;
+  std::unique_ptr<gpt_nlml> h(new gpt_nlml);
+  h->n = (int)n; h->D = (int)D; h->N = N;
+  h->CB = nlml_col_block((int)n, N);
+  h->ncb = (int)((N + h->CB - 1) / h->CB);
+  hipError_t err = hipSuccess;
+  auto al = [&](auto** p, size_t bytes) {
+    if (err != hipSuccess) return;
+    void* q = nullptr;
+    err = hipMalloc(&q, bytes ? bytes : 16);
+    if (err == hipSuccess) { h->mem.push_back(q); *p = (std::remove_reference_t<decltype(*p)>)q; }
+  };
+  const size_t nN = (size_t)n * N, nn = (size_t)n * n;
+  al(&h->X, 8 * (size_t)N * D); al(&h->y, 8 * (size_t)N); al(&h->Z, 8 * (size_t)n * D);
+  al(&h->b, 8 * (size_t)n); al(&h->ls, 8 * (size_t)D); al(&h->phi, 8 * nN); al(&h->S, 8 * nN);
+  al(&h->A, 8 * nn); al(&h->Xt, 8 * nn); al(&h->P, 8 * nn); al(&h->bv, 8 * (size_t)n);
+  al(&h->l, 8 * (size_t)n); al(&h->e, 8 * (size_t)N);
+  al(&h->part, 8 * (size_t)h->ncb * n * D); al(&h->gl, 8 * (size_t)D); al(&h->scal, 8 * 8);
+  al(&h->status, 16);
+  if (err != hipSuccess) return hip_fail(err, "nlml: hipMalloc");
+  NLCHK(hipMemcpy(h->X, X, 8 * (size_t)N * D, hipMemcpyHostToDevice));
+  NLCHK(hipMemcpy(h->y, y, 8 * (size_t)N, hipMemcpyHostToDevice));
+  NLCHK(hipMemcpy(h->Z, Z, 8 * (size_t)n * D, hipMemcpyHostToDevice));
+  NLCHK(hipMemcpy(h->b, b, 8 * (size_t)n, hipMemcpyHostToDevice));
+  *out = h.release();
+  return GPT_OK;
+}
+
+extern "C" int gpt_nlml_destroy(gpt_nlml* h) {
+  if (h) {
+    (void)hipDeviceSynchronize();
+    delete h;
+  }
+  return GPT_OK;
+}
+
+static void nlml_nan_fill(int64_t Lh, int n, double* nlml, double* grad, double* theta) {
+  const double q = std::nan("");
+  if (nlml) *nlml = q;
+  if (grad) for (int64_t k = 0; k < Lh; ++k) grad[k] = q;
+  if (theta) for (int j = 0; j < n; ++j) theta[j] = q;
+}
+
+// phase_ms (kNlmlPhases, optional): device-event times of features, SYRK, GEMV, Cholesky, the two
+// triangular solves, L⁻ᵀ, P (SYRK + mirror), e, the gradient GEMM, its finish, the scalars.
+constexpr int kNlmlPhases = 11;
+static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t want_grad,
+                          double* nlml, double* grad, double* theta_mean, double* phase_ms) {
+  if (!h || !nlml || (want_grad && !grad)) {
+    set_error("nlml: null handle or output"); return GPT_ERR_BAD_DIMS;
+  }
+  if (!nlml_hyper_ok(hyper, Lh, h->D)) return GPT_ERR_BAD_DIMS;
+  const int n = h->n, D = h->D;
+  const long long N = h->N;
+  hipStream_t st = nullptr;
+  if (phase_ms && h->ev.empty()) {
+    h->ev.resize(kNlmlPhases + 1);
+    for (auto& e : h->ev) NLCHK(hipEventCreate(&e));
+  }
+  int marks = 0;
+  auto mark = [&]() {
+    if (phase_ms) (void)hipEventRecord(h->ev[marks], st);
+    ++marks;
+  };
+  double lsv[kDMax];
+  for (int k = 0; k < D; ++k) lsv[k] = hyper[Lh == D + 2 ? k : 0];
+  const double sigma = hyper[Lh - 2], s2 = hyper[Lh - 1];
+  const double c = std::sqrt(2.0 / (double)n) * sigma;
+  NLCHK(hipMemcpyAsync(h->ls, lsv, 8 * (size_t)D, hipMemcpyHostToDevice, st));
+  NLCHK(hipMemsetAsync(h->status, 0, 16, st));
+  h->have_features = h->have_sin = false;
+  mark();
+  {
+    const long long total = (long long)n * N;
+    const int blocks = (int)std::min((total + 255) / 256, (long long)256 * 16);
+    hipLaunchKernelGGL(nlml_feature_kernel, dim3(blocks), dim3(256), 0, st, h->X, N, D, h->ls, c,
+                       h->Z, h->b, n, h->phi, want_grad ? h->S : nullptr);
+    NLCHK(hipGetLastError());
+  }
+  mark();
+  NLCHK(dense_syrk(h->phi, n, N, 1.0, s2, h->A, st));
+  mark();
+  NLCHK(dense_gemv(h->phi, n, N, h->y, 1.0, h->bv, st));
+  mark();
+  dense_chol(h->A, n, h->status, st);
+  mark();
+  NLCHK(hipMemcpyAsync(h->l, h->bv, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
+  dense_trsv(h->A, n, h->l, 0, st);
+  dense_trsv(h->A, n, h->l, 1, st);
+  NLCHK(hipGetLastError());
+  mark();
+  if (want_grad) {
+    static std::atomic<uint64_t> attr{0};
+    NLCHK(set_max_lds_once((const void*)nlml_trinv_kernel, 160 * 1024, attr));
+    NLCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
+    hipLaunchKernelGGL(nlml_trinv_kernel, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
+                       trinv_lds_bytes(n), st, h->A, n, h->Xt);
+    NLCHK(hipGetLastError());
+    mark();
+    NLCHK(dense_syrk(h->Xt, n, n, 1.0, 0.0, h->P, st));
+    hipLaunchKernelGGL(nlml_mirror_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256),
+                       0, st, h->P, n);
+    mark();
+    hipLaunchKernelGGL(nlml_resid_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, h->phi,
+                       h->l, h->y, n, N, h->e);
+    NLCHK(hipGetLastError());
+    mark();
+    const long long npair = ((n + 15) / 16 + 1) / 2;
+    const unsigned grid = (unsigned)((npair * h->ncb + 3) / 4);
+    NLCHK((n % 2 == 0)
+              ? launch_grad<true>(D, grid, st, h->P, h->phi, h->S, h->l, h->e, h->X, n, N, h->CB,
+                                  h->ncb, 1.0 / s2, h->part)
+              : launch_grad<false>(D, grid, st, h->P, h->phi, h->S, h->l, h->e, h->X, n, N, h->CB,
+                                   h->ncb, 1.0 / s2, h->part));
+    mark();
+    hipLaunchKernelGGL(nlml_finish_kernel, dim3(D), dim3(kNT), 0, st, h->part, h->ncb, h->Z, h->ls,
+                       n, D, h->gl);
+    mark();
+  } else {
+    for (int q = 0; q < 5; ++q) mark();
+  }
+  hipLaunchKernelGGL(nlml_scalars_kernel, dim3(1), dim3(kNT), 0, st, h->A,
+                     want_grad ? h->P : nullptr, h->y, h->bv, h->l, n, N, h->scal);
+  NLCHK(hipGetLastError());
+  mark();
+  double sc[5], gl[kDMax];
+  int32_t bad = 0;
+  std::vector<double> lh(n);
+  NLCHK(hipMemcpyAsync(sc, h->scal, 8 * 5, hipMemcpyDeviceToHost, st));
+  NLCHK(hipMemcpyAsync(&bad, h->status, 4, hipMemcpyDeviceToHost, st));
+  NLCHK(hipMemcpyAsync(lh.data(), h->l, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (want_grad) NLCHK(hipMemcpyAsync(gl, h->gl, 8 * (size_t)D, hipMemcpyDeviceToHost, st));
+  NLCHK(hipStreamSynchronize(st));
+  if (phase_ms)
+    for (int q = 0; q < kNlmlPhases; ++q) {
+      float ms = 0.f;
+      NLCHK(hipEventElapsedTime(&ms, h->ev[q], h->ev[q + 1]));
+      phase_ms[q] = ms;
+    }
+  h->have_features = true;
+  h->have_sin = want_grad != 0;
+  if (bad) {
+    nlml_nan_fill(Lh, n, nlml, want_grad ? grad : nullptr, theta_mean);
+    set_error("nlml: phi*phi' + signal_var*I is not positive definite (PosDefException)");
+    return GPT_ERR_NOT_SPD;
+  }
+  const double logdet = sc[0], yy = sc[1], bl = sc[2], ll = sc[3], trP = sc[4];
+  const double dN = (double)N, dn = (double)n;
+  *nlml = (dN - dn) / 2 * std::log(s2) + logdet + (yy - bl) / (2 * s2) +
+          dN / 2 * std::log(2 * M_PI);
+  if (want_grad) {
+    if (Lh == D + 2) {
+      for (int k = 0; k < D; ++k) grad[k] = gl[k];
+    } else {
+      double s = 0.0;
+      for (int k = 0; k < D; ++k) s += gl[k];
+      grad[0] = s;
+    }
+    grad[Lh - 2] = (dn - s2 * trP) / sigma - ll / sigma;
+    grad[Lh - 1] = (dN - dn) / (2 * s2) + trP / 2 + (bl - yy) / (2 * s2 * s2) + ll / (2 * s2);
+  }
+  if (theta_mean) std::memcpy(theta_mean, lh.data(), 8 * (size_t)n);
+  return GPT_OK;
+}
+
+extern "C" int gpt_nlml_eval(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t want_grad,
+                             double* nlml, double* grad, double* theta_mean) {
+  return nlml_eval_impl(h, hyper, Lh, want_grad, nlml, grad, theta_mean, nullptr);
+}
+
+extern "C" int gpt_nlml_eval_timed(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t want_grad,
+                                   double* nlml, double* grad, double* phase_ms) {
+  if (!phase_ms) { set_error("nlml: null phase_ms"); return GPT_ERR_BAD_DIMS; }
+  return nlml_eval_impl(h, hyper, Lh, want_grad, nlml, grad, nullptr, phase_ms);
+}
+
+extern "C" int gpt_nlml_features(gpt_nlml* h, double* phi_out, double* sin_out) {
+  if (!h || (!phi_out && !sin_out)) { set_error("nlml: null handle or output"); return GPT_ERR_BAD_DIMS; }
+  if (!h->have_features || (sin_out && !h->have_sin)) {
+    set_error("nlml: no evaluation yet (sin_out needs one with want_grad)");
+    return GPT_ERR_BAD_DIMS;
+  }
+  const size_t bytes = 8 * (size_t)h->n * h->N;
+  if (phi_out) NLCHK(hipMemcpy(phi_out, h->phi, bytes, hipMemcpyDeviceToHost));
+  if (sin_out) NLCHK(hipMemcpy(sin_out, h->S, bytes, hipMemcpyDeviceToHost));
+  return GPT_OK;
+}
+
+extern "C" int gpt_gpnt_nlogmarginal(const double* X, int64_t N, int64_t D, const double* y,
+                                     const double* Z, const double* b, int64_t n,
+                                     const double* hyper, int64_t Lh, int64_t want_grad,
+                                     double* nlml_out, double* grad_out) {
+  if (!nlml_dims_ok(X, N, D, y, Z, b, n) || !nlml_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
+  if (!nlml_out || (want_grad && !grad_out)) {
+    set_error("nlml: null output"); return GPT_ERR_BAD_DIMS;
+  }
+  gpt_nlml* h = nullptr;
+  int rc = gpt_nlml_create(X, N, D, y, Z, b, n, &h);
+  if (rc != GPT_OK) return rc;
+  rc = gpt_nlml_eval(h, hyper, Lh, want_grad ? 1 : 0, nlml_out, grad_out, nullptr);
+  gpt_nlml_destroy(h);
+  return rc;
+}

@@ -522,6 +522,23 @@ static void launch_trsv(const double* M, int p, double* x, int trans, hipStream_
   }
 }
 
+// The dense building blocks for the other translation units (nlml.hip): the same kernels.
+hipError_t dense_syrk(const double* A, int p, long long N, double alpha, double beta, double* M,
+                      hipStream_t st) {
+  const long long T = (p + 15) / 16;
+  hipLaunchKernelGGL(syrk_mfma_kernel, (unsigned)((T * (T + 1) / 2 + 3) / 4), 256, 0, st, A, p, N,
+                     alpha, beta, M);
+  return hipGetLastError();
+}
+hipError_t dense_gemv(const double* A, int p, long long N, const double* y, double alpha,
+                      double* out, hipStream_t st) {
+  return launch_gemv(A, p, N, y, alpha, out, st);
+}
+void dense_chol(double* M, int p, int32_t* status, hipStream_t st) { launch_chol(M, p, status, st); }
+void dense_trsv(const double* M, int p, double* x, int trans, hipStream_t st) {
+  launch_trsv(M, p, x, trans, st);
+}
+
 // ------------------------------------------------------------------------------ host side
 #define GPT_TGP_RANKS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(15) X(16) X(20)
 

@@ -335,6 +335,39 @@ int gpt_gpnt_sgld(const double* phi, const double* y, int64_t n, int64_t N, doub
                   double sigma_theta, int64_t m, double eps_theta, double decay_rate,
                   int64_t burnin, int64_t maxepoch, uint64_t seed, double* theta_store);
 
+/* ---- full-theta model: hyper-parameter learning -------------------------------------- */
+/* GPNT_nlogmarginal / GPNT_gradnlogmarginal (GPT_SGLD.jl:921-962) with featureNotensor and
+ * gradfeatureNotensor (:109-120, :142-177) as the feature closures: the negative log marginal
+ * likelihood of the no-tensor RFF GP and its gradient with respect to
+ *   hyper = [length_scale (D entries, or 1: the scalar form); sigma_RBF; signal_var],
+ * Lh = D + 2 or 3.  X (N, D), y (N), Z (n, D), b (n); n <= 1024 (the single-workgroup Cholesky),
+ * D <= 16.  A hyper-parameter that is not positive and finite, or a dimension out of range, is
+ * GPT_ERR_BAD_DIMS before any device call.  When phi*phi' + signal_var*I fails its Cholesky
+ * factorisation (a NaN in X, for one) the call returns GPT_ERR_NOT_SPD and fills nlml, grad
+ * and theta_mean with NaN.
+ *
+ * The evaluator keeps X, y, Z, b and its scratch on the device, so an optimiser's evaluations
+ * upload only the hyper-parameters.  grad (Lh) may be NULL when want_grad = 0; theta_mean (n,
+ * optional) receives l = A^-1 phi y, the posterior mean of the full-theta weights at hyper. */
+typedef struct gpt_nlml gpt_nlml;
+int gpt_nlml_create(const double* X, int64_t N, int64_t D, const double* y, const double* Z,
+                    const double* b, int64_t n, gpt_nlml** out);
+int gpt_nlml_eval(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t want_grad, double* nlml,
+                  double* grad, double* theta_mean);
+/* Test entry: phi (n, N) of the last evaluation and S = c*sin(f) of the last one with
+ * want_grad (either may be NULL). */
+int gpt_nlml_features(gpt_nlml* h, double* phi_out, double* sin_out);
+/* Diagnostics (scripts/time_nlml.py): gpt_nlml_eval with device-event times in ms of its 11
+ * phases: features, SYRK, GEMV, Cholesky, the two triangular solves, L^-T, P = A^-1, e, the
+ * gradient GEMM, its finish, the scalar sums (the gradient's five are 0 when want_grad = 0). */
+int gpt_nlml_eval_timed(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t want_grad,
+                        double* nlml, double* grad, double* phase_ms);
+int gpt_nlml_destroy(gpt_nlml* h);
+/* One-shot host-pointer form (create, one evaluation, destroy). */
+int gpt_gpnt_nlogmarginal(const double* X, int64_t N, int64_t D, const double* y, const double* Z,
+                          const double* b, int64_t n, const double* hyper, int64_t Lh,
+                          int64_t want_grad, double* nlml_out, double* grad_out);
+
 /* ---- tensor-GP Gibbs sampler (§8 a25) ----------------------------------------------- */
 /* GPT_inf(b,y,sigma,n,r,q,num_iterations,burnin) TGP.jl:37-86 on whitened data.
  * b (n, D, N) column-major feature array (TGP.feature, TGP.jl:6-14), y (N).

@@ -12,7 +12,7 @@ module GPT_SGLD_HIP
 export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTregression, GPTregression_chains,
        GPTregression_chains_x, GPT_SGLDERM, pred, RMSE,
        GPNT_SGLD, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
-       init_state
+       init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal
 
 const LIB = get(ENV, "GPTSGLD_LIB", joinpath(@__DIR__, "..", "gpt_amd", "libgptsgld.so"))
 
@@ -379,5 +379,24 @@ function GPNT_SGLD(phi::Array{Float64,2}, y::Array{Float64}, signal_var::Real, s
     check(rc)
     return store
 end
+
+# GPNT_nlogmarginal / GPNT_gradnlogmarginal (GPT_SGLD.jl:921-962) with featureNotensor /
+# gradfeatureNotensor as the feature closures: X, Z, b take the closures' place.
+# hyperparams = [length_scale (D entries, or one); sigma_RBF; signal_var].  A failed Cholesky
+# (the reference's PosDefException) is error code 5.
+function gpnt_marginal(X::Array{Float64,2}, y::Array{Float64}, Z::Array{Float64,2},
+                       b::Array{Float64}, hyperparams::Vector{Float64}, want_grad::Bool)
+    N, D = size(X); n = size(Z, 1)
+    nlml = Array{Float64}(undef, 1)
+    grad = Array{Float64}(undef, length(hyperparams))
+    check(ccall((:gpt_gpnt_nlogmarginal, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+                 Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+                X, N, D, vec(y), Z, vec(b), n, hyperparams, length(hyperparams), Int64(want_grad),
+                nlml, grad))
+    return nlml[1], grad
+end
+GPNT_nlogmarginal(X, y, Z, b, hyperparams) = gpnt_marginal(X, y, Z, b, hyperparams, false)[1]
+GPNT_gradnlogmarginal(X, y, Z, b, hyperparams) = gpnt_marginal(X, y, Z, b, hyperparams, true)[2]
 
 end # module
