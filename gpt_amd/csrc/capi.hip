@@ -2344,6 +2344,13 @@ extern "C" int gpt_pred_last_vphase(int32_t* kind) {
   return GPT_OK;
 }
 
+extern "C" int gpt_pred_last_route(int32_t* out, int32_t len) {
+  if (!out || len < 0) { set_error("gpt_pred_last_route: bad output"); return GPT_ERR_BAD_DIMS; }
+  pred_last_route(out, (int)len);
+  for (int32_t x = kPredRouteLen; x < len; ++x) out[x] = 0;
+  return GPT_OK;
+}
+
 extern "C" int gpt_cf_last_mode(int32_t* mode) {
   if (!mode) { set_error("gpt_cf_last_mode: null output"); return GPT_ERR_BAD_DIMS; }
   *mode = g_cf_mode;

@@ -216,6 +216,8 @@ size_t pred_x_lds_bytes(int n, int D, int r, int Q);
 // gemm_ms / vphase_ms accumulate over the sample chunks of one call.
 struct PredPhaseTiming { double gemm_ms = 0.0, vphase_ms = 0.0; };
 int pred_last_vphase();
+constexpr int kPredRouteLen = 7;
+void pred_last_route(int32_t* out, int len);   // the first len of kPredRouteLen entries
 hipError_t launch_pred(const double* w, const double* U, const int32_t* I0, const double* phitest,
                        int n, int D, long long Ntest, int r, int Q, int S, double* fhat,
                        hipStream_t st, PredPhaseTiming* timing = nullptr);

@@ -5,6 +5,7 @@
 #include "device_util.h"
 
 #include <algorithm>
+#include <cerrno>
 #include <cstdlib>
 #include <cstring>
 
@@ -663,6 +664,19 @@ static hipError_t vphase_pairs(int NTp, const double* w, const double* T, const 
 static thread_local int g_pred_vphase = -1;
 int pred_last_vphase() { return g_pred_vphase; }
 
+// The route of the last prediction call on this thread (gpt_pred_last_route): the kind as above,
+// the kernel's template dimension (NT of the pairs kernel, DD of the persistent rows kernel, else
+// 0), its prefetched rows per wave (NPW, else 0), the V-phase grid.x and the (sample, 64-row) tiles
+// of the last pass, the number of passes and the samples in the first one.
+struct PredRoute { int32_t tdim = 0, npw = 0, grid = 0, tiles = 0, passes = 0, first = 0; };
+static thread_local PredRoute g_pred_route;
+void pred_last_route(int32_t* out, int len) {
+  const int32_t v[kPredRouteLen] = {g_pred_vphase,        g_pred_route.tdim,   g_pred_route.npw,
+                                    g_pred_route.grid,    g_pred_route.tiles,  g_pred_route.passes,
+                                    g_pred_route.first};
+  for (int x = 0; x < len && x < kPredRouteLen; ++x) out[x] = v[x];
+}
+
 // The rows V-phase: the persistent prefetching kernel while a tile's D·R rows fit 16 per wave and
 // its LDS fits a CU (as many workgroups as the LDS lets every CU hold), else the
 // one-tile-per-workgroup kernel.
@@ -684,6 +698,9 @@ static hipError_t launch_rows_pf(const double* w, const double* T, const int32_t
   const long long per_cu = std::max<long long>(1, (long long)(160 * 1024) / (long long)lds);
   const long long ntiles = (Ntest + 63) / 64 * (long long)Sc;
   const unsigned grid = (unsigned)std::min<long long>(ntiles, per_cu * cus);
+  g_pred_route.tdim = DD;
+  g_pred_route.npw = NPW;
+  g_pred_route.grid = (int32_t)grid;
   hipLaunchKernelGGL((pred_vphase_rows_pf_kernel<DD, NW, NPW>), dim3(grid), dim3(64 * NW), lds, st,
                      w, T, offs, D, r, Ntest, Q, fhat, Sc);
   return hipGetLastError();
@@ -714,6 +731,8 @@ static hipError_t launch_vphase_rows(const double* w, const double* T, const int
     if (e != hipSuccess) return e;
   }
   g_pred_vphase = 2;
+  g_pred_route.tdim = g_pred_route.npw = 0;
+  g_pred_route.grid = (int32_t)((Ntest + 63) / 64);
   hipLaunchKernelGGL(pred_vphase_rows_kernel, dim3((unsigned)((Ntest + 63) / 64), Sc),
                      dim3(64 * kRowsWaves), rlds, st, w, T, offs, D, r, Ntest, Q, fhat);
   return hipGetLastError();
@@ -777,7 +796,16 @@ static hipError_t launch_pred_mfma(const double* w, const double* U, const int32
   // tile's rows are one block (row-major [D·r][Ntest] made each tile 160 strided 512-B reads at
   // r = 20: 1.9 TB/s, 4.1 ms of the 224-sample call with no arithmetic at all)
   const size_t per_sample = 8 * (size_t)D * r * (size_t)((Ntest + 63) / 64 * 64);
-  int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, ((size_t)8 << 30) / per_sample));
+  // GPTSGLD_PRED_PASS_BYTES (a positive integer, read on every call) replaces the 8 GiB budget,
+  // never below one sample: tests/test_gpu_pred.py splits small calls into several passes with it
+  size_t budget = (size_t)8 << 30;
+  if (const char* pb = std::getenv("GPTSGLD_PRED_PASS_BYTES")) {
+    char* end = nullptr;
+    errno = 0;
+    const long long v = std::strtoll(pb, &end, 10);
+    if (errno == 0 && end != pb && *end == '\0' && v > 0) budget = (size_t)v;
+  }
+  int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, budget / per_sample));
   int unit = 1;
   {
     int g = 128, b = r;
@@ -828,8 +856,14 @@ static hipError_t launch_pred_mfma(const double* w, const double* U, const int32
                            r, offs);
     }
     if (timing) (void)hipEventRecord(ev[1], st);
+    g_pred_route.passes = s0 == 0 ? 1 : g_pred_route.passes + 1;
+    if (s0 == 0) g_pred_route.first = Sc;
+    g_pred_route.tiles = (int32_t)((Ntest + 63) / 64 * Sc);
     if (pairs) {
       g_pred_vphase = 0;
+      g_pred_route.tdim = NTp;
+      g_pred_route.npw = 0;
+      g_pred_route.grid = (int32_t)((Ntest + 63) / 64);
       e = vphase_pairs(NTp, w + (size_t)s0 * Q, T, offp, D, r, Ntest, Q, fhat + (size_t)s0 * Ntest,
                        Sc, Ntest, plds, st);
       if (timing && e == hipSuccess) {
@@ -887,12 +921,14 @@ hipError_t launch_pred(const double* w, const double* U, const int32_t* I0, cons
                        int n, int D, long long Ntest, int r, int Q, int S, double* fhat,
                        hipStream_t st, PredPhaseTiming* timing) {
   if (Ntest <= 0 || S <= 0) return hipSuccess;
-  static const bool direct = [] {
-    const char* ev = std::getenv("GPTSGLD_PRED");
-    return ev && std::strcmp(ev, "direct") == 0;
-  }();
-  if (direct) {
+  const char* ev = std::getenv("GPTSGLD_PRED");       // read on every call, as gpt_pred_mean_x does
+  if (ev && std::strcmp(ev, "direct") == 0) {
     g_pred_vphase = 4;
+    g_pred_route = PredRoute{};
+    g_pred_route.grid = (int32_t)((Ntest + 63) / 64);
+    g_pred_route.tiles = (int32_t)((Ntest + 63) / 64 * S);
+    g_pred_route.passes = 1;
+    g_pred_route.first = S;
     return launch_pred_direct(w, U, I0, phitest, n, D, Ntest, r, Q, S, fhat, st);
   }
   return launch_pred_mfma(w, U, I0, phitest, n, D, Ntest, r, Q, S, fhat, st, timing);

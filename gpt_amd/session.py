@@ -280,3 +280,17 @@ def pred_last_vphase():
     k = C.c_int32(-1)
     check(lib().gpt_pred_last_vphase(C.byref(k)))
     return VPHASE_KERNELS.get(k.value)
+
+
+ROUTE_FIELDS = ("kind", "tdim", "npw", "grid", "tiles", "passes", "first")
+
+
+def pred_last_route():
+    """The route of the last prediction call on this thread (gpt_pred_last_route) as a dict: kind
+    (the codes of VPHASE_KERNELS, -1 before any call), tdim (NT of the pair-table kernel, DD of the
+    persistent rows kernel with 0 = run-time D, else 0), npw (its prefetched rows per wave, else
+    0), grid and tiles (the V-phase grid.x and the (sample, 64-row) tiles of the last pass), passes
+    and first (the samples in the first pass)."""
+    out = np.zeros(len(ROUTE_FIELDS), dtype=np.int32)
+    check(lib().gpt_pred_last_route(out.ctypes.data_as(_lib.P_I32), out.size))
+    return dict(zip(ROUTE_FIELDS, (int(v) for v in out)))

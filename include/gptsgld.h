@@ -310,6 +310,14 @@ int gpt_pred_dev_timed(const double* w_dev, const double* U_dev, const int32_t* 
  * counterpart): 0 pred_vphase_pairs_kernel, 1 pred_vphase_rows_pf_kernel, 2 pred_vphase_rows_kernel,
  * 4 pred_kernel (the direct path, no separate V-phase); -1 before any call. */
 int gpt_pred_last_vphase(int32_t* kind);
+/* The route of the last gpt_pred* call on this thread (measurement, for the route assertions of
+ * tests/test_gpu_pred.py); the first min(len, 7) of: [0] the kind of gpt_pred_last_vphase, [1] the
+ * kernel's template dimension (NT of the pair-table kernel, DD of the persistent rows kernel with
+ * 0 = run-time D, else 0), [2] its prefetched rows per wave (else 0), [3] the V-phase grid.x and
+ * [4] the (sample, 64-row) tiles of the last pass, [5] the passes, [6] the samples in the first
+ * pass.  Entries past 7 are set to 0.  GPTSGLD_PRED_PASS_BYTES=<bytes> (read on every call) replaces
+ * the 8 GiB temp budget of a pass, never below one sample. */
+int gpt_pred_last_route(int32_t* out, int32_t len);
 /* Posterior-mean prediction over S samples + RMSE (GPT_SGLD_p.jl:124-132,
  * kin40kExperiment.jl:80-87): mean_out (Ntest), returns rmse*scale in *rmse_out. */
 int gpt_pred_mean(const double* w_store, const double* U_store, const int32_t* I,
