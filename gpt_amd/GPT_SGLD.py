@@ -24,6 +24,10 @@ Same function names, argument meaning, return values and error behaviour as the 
     pred_mean_x(w_store, U_store, I, Xtest, ytest, ls, σ, scale, Z, b)  fused feature + pred
     GPNT_SGLD(phi, y, signal_var, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch,
               param_seed)                                     GPT_SGLD.jl:809
+    GPNT_SGLDclass(phi, y, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch, param_seed)
+                                                              GPT_SGLD.jl:851
+    GPNT_SGLDclass_chains, class_eval(scores, ytest, window), GPNT_pred_class, pred_class
+                                                              ImageExperiment.jl:50-72
     NoTensorMarginal(X, y, Z, b), GPNT_nlogmarginal, GPNT_gradnlogmarginal, GPNT_hyperparameters,
     GPNT_hyperparameters_optim                                GPT_SGLD.jl:921-1002
     datawhitening(X), proj, geod are not on the device path (host prep / inside the kernel).
@@ -564,6 +568,170 @@ def GPNT_SGLD(phi, y, signal_var, sigma_theta, m, eps_theta, decay_rate, burnin,
         return np.zeros(n)
     check(code)
     return out
+
+
+# ------------------------------------------------------------------ classification
+def GPNT_SGLDclass(phi, y, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch, param_seed=0):
+    """Full-theta softmax SGLD (GPT_SGLD.jl:851-901), labels y in 1..C.  Returns theta_store
+    (n, C, T); on NaN prints the reference's message and returns zeros(n) (:894-897)."""
+    phi = _f64(phi)
+    n, N = phi.shape
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    if y.size != N:
+        raise ValueError("phi and y disagree on N")
+    ncls = int(y.max() - y.min() + 1)
+    nb = -(-N // m)
+    out = np.empty((n, max(ncls, 1), (maxepoch + burnin) * nb), order="F")
+    code = lib().gpt_gpnt_sgld_class(_ptr(phi), _ptr(y), n, N, float(sigma_theta), int(m),
+                                     float(eps_theta), float(decay_rate), int(burnin),
+                                     int(maxepoch), int(param_seed) & (2 ** 64 - 1), _ptr(out))
+    if code == _lib.GPT_ERR_NAN_THETA:
+        print("Get NaN in theta. Try smaller epsilon")
+        return np.zeros(n)
+    check(code)
+    return out
+
+
+def GPNT_SGLDclass_chains(phi, y, sigma_theta, m, eps_thetas, decay_rate, burnin, maxepoch, seeds,
+                          store_every=1, ncls=None):
+    """Sibling GPNT_SGLDclass chains on one phi / y in one launch (step-size and seed sweeps):
+    chain k uses eps_thetas[k] and seeds[k].  ``store_every`` keeps the 1-based steps divisible
+    by it (numbatches: the epoch ends).  Returns (theta_store (n, C, kept, nchains), status
+    (nchains)); a chain that met a NaN has a zero store and status GPT_ERR_NAN_THETA."""
+    phi = _f64(phi)
+    n, N = phi.shape
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    if y.size != N:
+        raise ValueError("phi and y disagree on N")
+    if ncls is None:
+        ncls = int(y.max() - y.min() + 1)
+    seeds = np.ascontiguousarray([int(s) & (2 ** 64 - 1) for s in np.atleast_1d(seeds)], dtype=np.uint64)
+    eps = _f64(np.atleast_1d(eps_thetas))
+    if eps.size == 1 and seeds.size > 1:
+        eps = _f64(np.full(seeds.size, eps[0]))
+    if eps.size != seeds.size:
+        raise ValueError("eps_thetas and seeds must have one entry per chain")
+    if int(store_every) < 1:
+        raise ValueError("store_every must be >= 1")
+    nb = -(-N // m)
+    kept = (maxepoch + burnin) * nb // int(store_every)
+    out = np.zeros((n, max(int(ncls), 1), kept, seeds.size), order="F")
+    status = np.zeros(seeds.size, dtype=np.int32)
+    check(lib().gpt_gpnt_sgld_class_chains(_ptr(phi), _ptr(y), n, N, int(ncls), float(sigma_theta),
+                                           int(m), _ptr(eps), float(decay_rate), int(burnin),
+                                           int(maxepoch), _ptr(seeds, P_U64), seeds.size,
+                                           int(store_every), _ptr(out), _ptr(status, P_I32)))
+    return out, status
+
+
+class ClassEval:
+    """Result of the evaluation functions: ``prop_missed`` and ``mean_nlp`` (one per sample),
+    ``avg_prop_missed`` and ``avg_mean_nlp`` of the scores averaged over the window, ``mean_fhat``
+    (Ntest, C) those averaged scores, ``prediction`` (Ntest, 1-based) and ``nlp`` (Ntest) on them,
+    ``window`` the half-open 0-based sample range, and ``scores`` (Ntest, C, T) when asked."""
+    __slots__ = ("prop_missed", "mean_nlp", "avg_prop_missed", "avg_mean_nlp", "mean_fhat",
+                 "prediction", "nlp", "window", "scores")
+
+    def __repr__(self):
+        return "ClassEval(T=%d, avg_prop_missed=%.6g, avg_mean_nlp=%.6g, window=%r)" % (
+            self.prop_missed.size, self.avg_prop_missed, self.avg_mean_nlp, self.window)
+
+
+def _labels(ytest, Nt):
+    yt = np.asarray(ytest).ravel()
+    if yt.size != Nt:
+        raise ValueError("ytest must have one label per test row")
+    yi = np.ascontiguousarray(yt, dtype=np.int32)
+    if not np.array_equal(yi, yt):
+        raise ValueError("labels must be integers")
+    return yi
+
+
+def _window(window, T):
+    first, last = (0, T) if window is None else (int(window[0]), int(window[1]))
+    return first, last
+
+
+def _class_eval_call(fn, head, Nt, ncls, T, window, want_scores):
+    first, last = _window(window, T)
+    res = ClassEval()
+    res.prop_missed = np.empty(T)
+    res.mean_nlp = np.empty(T)
+    avg = np.empty(2)
+    res.mean_fhat = np.empty((Nt, ncls), order="F")
+    res.prediction = np.empty(Nt, dtype=np.int32)
+    res.nlp = np.empty(Nt)
+    res.scores = np.empty((Nt, ncls, T), order="F") if want_scores else None
+    tail = [first, last, _ptr(res.prop_missed), _ptr(res.mean_nlp), _ptr(avg), _ptr(res.mean_fhat),
+            _ptr(res.prediction, P_I32), _ptr(res.nlp)]
+    if want_scores is not None:
+        tail.append(_ptr(res.scores) if want_scores else None)
+    check(fn(*(head + tail)))
+    res.avg_prop_missed, res.avg_mean_nlp = float(avg[0]), float(avg[1])
+    res.window = (first, last)
+    return res
+
+
+def class_eval(scores, ytest, window=None):
+    """Miss rate and mean negative log predictive probability of class scores (Ntest, C, T)
+    against labels in 1..C, per sample and on the scores averaged over ``window`` (0-based,
+    half open; default all samples): ImageExperiment.jl:50-72."""
+    scores = _f64(scores)
+    if scores.ndim == 2:
+        scores = scores.reshape(scores.shape + (1,), order="F")
+    Nt, ncls, T = scores.shape
+    yi = _labels(ytest, Nt)
+    return _class_eval_call(lib().gpt_class_eval, [_ptr(scores), _ptr(yi, P_I32), Nt, ncls, T], Nt,
+                            ncls, T, window, None)
+
+
+def GPNT_pred_class(theta_store, phitest, ytest, cols=None, window=None, scores=False):
+    """Evaluation of GPNT_SGLDclass samples (ImageNoTensorExperiment.jl:50-75): theta_store
+    (n, C, T), phitest (n, Ntest).  ``cols`` selects stored samples (0-based; the end of 1-based
+    epoch e is numbatches*e - 1) on the host before the call."""
+    theta = np.asarray(theta_store, dtype=np.float64)
+    if theta.ndim == 2:
+        theta = theta.reshape(theta.shape + (1,))
+    if cols is not None:
+        theta = theta[:, :, np.asarray(cols, dtype=np.int64)]
+    theta = _f64(theta)
+    phitest = _f64(phitest)
+    n, Nt = phitest.shape
+    if theta.shape[0] != n:
+        raise ValueError("theta_store and phitest disagree on n")
+    _, ncls, T = theta.shape
+    yi = _labels(ytest, Nt)
+    return _class_eval_call(lib().gpt_gpnt_pred_class,
+                            [_ptr(theta), _ptr(phitest), _ptr(yi, P_I32), n, Nt, ncls, T], Nt, ncls,
+                            T, window, bool(scores))
+
+
+def pred_class(w_store, U_store, I, phitest, ytest, cols=None, window=None, scores=False):
+    """Evaluation of GPTclassification samples (ImageExperiment.jl:50-72): w_store (Q, C, T),
+    U_store (n, r, D, C, T), phitest (n, D, Ntest) uploaded once; the scores are ``pred`` of every
+    (class, sample).  ``cols`` as in GPNT_pred_class."""
+    w = np.asarray(w_store, dtype=np.float64)
+    U = np.asarray(U_store, dtype=np.float64)
+    if w.ndim == 2:
+        w = w.reshape(w.shape + (1,))
+        U = U.reshape(U.shape + (1,))
+    if cols is not None:
+        cols = np.asarray(cols, dtype=np.int64)
+        w, U = w[:, :, cols], U[:, :, :, :, cols]
+    w, U = _f64(w), _f64(U)
+    phitest = _f64(phitest)
+    n, D, Nt = phitest.shape
+    Q, ncls, T = w.shape
+    r = U.shape[1]
+    if U.shape != (n, r, D, ncls, T):
+        raise ValueError("U_store must be (n, r, D, C, T)")
+    I = np.asfortranarray(np.asarray(I, dtype=np.int32))
+    if I.shape != (Q, D):
+        raise ValueError("I must be (Q, D)")
+    yi = _labels(ytest, Nt)
+    return _class_eval_call(lib().gpt_pred_class,
+                            [_ptr(w), _ptr(U), _ptr(I, P_I32), _ptr(phitest), _ptr(yi, P_I32), n, D,
+                             Nt, r, Q, ncls, T], Nt, ncls, T, window, bool(scores))
 
 
 # ------------------------------------------------------------------ full-theta model: hyper-parameters

@@ -108,6 +108,23 @@ SIGNATURES = {
                                 C.c_int64, C.c_int64, C.c_int64, C.c_double, P_D, P_D]),
     "gpt_gpnt_sgld": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64,
                                 C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_uint64, P_D]),
+    "gpt_gpnt_sgld_class": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_double, C.c_int64,
+                                      C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_uint64,
+                                      P_D]),
+    "gpt_gpnt_sgld_class_chains": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_int64, C.c_double,
+                                             C.c_int64, P_D, C.c_double, C.c_int64, C.c_int64,
+                                             P_U64, C.c_int32, C.c_int64, P_D, P_I32]),
+    "gpt_class_eval": (C.c_int, [P_D, P_I32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                 P_D, P_D, P_D, P_D, P_I32, P_D]),
+    "gpt_class_eval_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpt_gpnt_pred_class": (C.c_int, [P_D, P_D, P_I32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                      C.c_int64, C.c_int64, P_D, P_D, P_D, P_D, P_I32, P_D, P_D]),
+    "gpt_pred_class": (C.c_int, [P_D, P_D, P_I32, P_D, P_I32, C.c_int64, C.c_int64, C.c_int64,
+                                 C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                 P_D, P_D, P_D, P_D, P_I32, P_D, P_D]),
+    "gpt_class_last_timing": (C.c_int, [P_D]),
     "gpt_nlml_create": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_int64,
                                   C.POINTER(C.c_void_p)]),
     "gpt_nlml_eval": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int32, P_D, P_D, P_D]),

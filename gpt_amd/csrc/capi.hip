@@ -1799,6 +1799,349 @@ extern "C" int gpt_gpnt_sgld(const double* phi, const double* y, int64_t n, int6
   return GPT_OK;
 }
 
+// ====================================================================== classification
+// Device-event times of the last classification calls on this thread (gpt_class_last_timing):
+// [0] the sampler's launches, [1] the scores (nt_scores_kernel or the stacked prediction),
+// [2] the evaluation kernels.
+static thread_local double g_cls_ms[3] = {0.0, 0.0, 0.0};
+struct ClsTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  hipStream_t st;
+  int slot;
+  ClsTimer(int slot_, hipStream_t st_) : st(st_), slot(slot_) {
+    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
+    (void)hipEventRecord(a, st);
+  }
+  void stop() { if (b) (void)hipEventRecord(b, st); }
+  ~ClsTimer() {                       // after the caller's synchronisation
+    float ms = 0.0f;
+    if (a && b && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess)
+      g_cls_ms[slot] = ms;
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+extern "C" int gpt_class_last_timing(double* ms_out) {
+  if (!ms_out) { set_error("gpt_class_last_timing: null argument"); return GPT_ERR_BAD_DIMS; }
+  for (int k = 0; k < 3; ++k) ms_out[k] = g_cls_ms[k];
+  return GPT_OK;
+}
+
+// GPNT_SGLDclass (GPT_SGLD.jl:851-901) for sibling chains on one phi / y: chain k draws
+// theta[:, c] = sigma_theta·normals(n, seeds[k], 0, THETA_INIT, c), its epoch orders are
+// GPNT_SGLD's for seeds[k], and the kernel draws the step noise (cls.hip).  One launch per epoch.
+extern "C" int gpt_gpnt_sgld_class_chains(const double* phi, const double* y, int64_t n, int64_t N,
+                                          int64_t ncls, double sigma_theta, int64_t m,
+                                          const double* eps_theta, double decay_rate,
+                                          int64_t burnin, int64_t maxepoch, const uint64_t* seeds,
+                                          int32_t nchains, int64_t store_every, double* theta_store,
+                                          int32_t* status) {
+  if (!phi || !y || !eps_theta || !seeds || !theta_store || !status) {
+    set_error("gpt_gpnt_sgld_class_chains: null argument"); return GPT_ERR_BAD_DIMS;
+  }
+  if (n < 1 || N < 1 || m < 1 || burnin < 0 || maxepoch < 0 || nchains < 1 || store_every < 1 ||
+      n > (1 << 20) || N > (1LL << 31) - 1 || m > (1 << 20) || nchains > 65535 ||
+      store_every > (1 << 30) ||
+      burnin + maxepoch > (1 << 24)) {
+    set_error("bad GPNT_SGLDclass dimensions"); return GPT_ERR_BAD_DIMS;
+  }
+  if (ncls < 1 || ncls > 32) {
+    set_error("GPNT_SGLDclass: the number of classes must be in 1..32"); return GPT_ERR_BAD_DIMS;
+  }
+  const int C = (int)ncls;
+  std::vector<int32_t> y0((size_t)N);
+  for (int64_t i = 0; i < N; ++i) {
+    const double v = y[i];
+    if (!(v >= 1.0 && v <= (double)C) || v != std::floor(v)) {
+      set_error("GPNT_SGLDclass: labels must be integers in 1..C"); return GPT_ERR_BAD_DIMS;
+    }
+    y0[i] = (int32_t)v - 1;
+  }
+  const NtcLayout L = ntc_layout((int)n, C, (int)m);
+  if (L.bytes > 160 * 1024) {
+    set_error("GPNT_SGLDclass: theta (n x C) and the batch residual exceed 160 KiB of LDS");
+    return GPT_ERR_BAD_DIMS;
+  }
+  const long long nb = (N + m - 1) / m;
+  const int epochs = (int)(burnin + maxepoch);
+  const long long total = (long long)epochs * nb;
+  const long long kept = total / store_every;
+  const size_t nC = (size_t)n * C;
+  for (int k = 0; k < nchains; ++k) status[k] = 0;
+  if (total == 0) return GPT_OK;
+  // epoch orders: one set per distinct seed
+  std::unordered_map<uint64_t, size_t> ord_of;
+  std::vector<size_t> ord_at(nchains);
+  for (int k = 0; k < nchains; ++k) {
+    auto it = ord_of.find(seeds[k]);
+    if (it == ord_of.end()) it = ord_of.emplace(seeds[k], ord_of.size()).first;
+    ord_at[k] = it->second;
+  }
+  const size_t per = (size_t)epochs * N;
+  std::vector<int32_t> ord(per * ord_of.size());
+  for (const auto& kv : ord_of) host_epoch_orders((int)N, kv.first, epochs, ord.data() + per * kv.second);
+  std::vector<double> th0(nC * nchains);
+  for (int k = 0; k < nchains; ++k)
+    for (int c = 0; c < C; ++c)
+      for (int64_t j = 0; j < n; ++j)
+        th0[nC * k + (size_t)n * c + j] =
+            sigma_theta * host_normal(seeds[k], (uint32_t)j, 0, kThetaInit, (uint32_t)c);
+  DevMem dphi, dy, dord, dth, dst, dstat, dch;
+  HIPCHK(dphi.alloc(8 * (size_t)n * N));
+  HIPCHK(dy.alloc(4 * (size_t)N));
+  HIPCHK(dord.alloc(4 * ord.size()));
+  HIPCHK(dth.alloc(8 * th0.size()));
+  HIPCHK(dst.alloc(8 * nC * (size_t)kept * nchains));
+  HIPCHK(dstat.alloc(4 * (size_t)nchains));
+  HIPCHK(dch.alloc(sizeof(NtcChain) * (size_t)nchains));
+  std::vector<NtcChain> ch(nchains);
+  for (int k = 0; k < nchains; ++k) {
+    ch[k].order = dord.as<int32_t>() + per * ord_at[k];
+    ch[k].theta = dth.as<double>() + nC * k;
+    ch[k].store = dst.as<double>() + nC * (size_t)kept * k;
+    ch[k].status = dstat.as<int32_t>() + k;
+    ch[k].seed = seeds[k];
+    ch[k].eps_theta = eps_theta[k];
+  }
+  HIPCHK(hipMemcpy(dphi.p, phi, 8 * (size_t)n * N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dy.p, y0.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dord.p, ord.data(), 4 * ord.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dth.p, th0.data(), 8 * th0.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dch.p, ch.data(), sizeof(NtcChain) * (size_t)nchains, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(dstat.p, 0, 4 * (size_t)nchains));
+  HIPCHK(hipMemset(dst.p, 0, 8 * nC * (size_t)kept * nchains));
+  const int chunk = (int)std::min<long long>(nb, 4096);       // steps per launch, within an epoch
+  ClsTimer tm(0, nullptr);
+  for (int e = 0; e < epochs; ++e)
+    for (long long b0 = 0; b0 < nb; b0 += chunk) {
+      hipError_t er = launch_ntc_chain(dphi.as<double>(), dy.as<int32_t>(), dch.as<NtcChain>(),
+                                       nchains, (int)n, (int)N, C, (int)m, (int)nb, total,
+                                       decay_rate, (int)store_every,
+                                       (long long)e * nb + b0,
+                                       (int)std::min<long long>(chunk, nb - b0), nullptr);
+      if (er != hipSuccess) return hip_fail(er, "ntc_chain kernel");
+    }
+  tm.stop();
+  HIPCHK(hipMemcpy(status, dstat.p, 4 * (size_t)nchains, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(theta_store, dst.p, 8 * nC * (size_t)kept * nchains, hipMemcpyDeviceToHost));
+  for (int k = 0; k < nchains; ++k)
+    if (status[k]) std::memset(theta_store + nC * (size_t)kept * k, 0, 8 * nC * (size_t)kept);
+  return GPT_OK;
+}
+
+extern "C" int gpt_gpnt_sgld_class(const double* phi, const double* y, int64_t n, int64_t N,
+                                   double sigma_theta, int64_t m, double eps_theta,
+                                   double decay_rate, int64_t burnin, int64_t maxepoch,
+                                   uint64_t seed, double* theta_store) {
+  if (!phi || !y || !theta_store || N < 1) {
+    set_error("bad GPNT_SGLDclass arguments"); return GPT_ERR_BAD_DIMS;
+  }
+  double lo = y[0], hi = y[0];
+  for (int64_t i = 1; i < N; ++i) { lo = std::min(lo, y[i]); hi = std::max(hi, y[i]); }
+  const double Cd = hi - lo + 1.0;                            // :854
+  if (!(Cd >= 1.0 && Cd <= 32.0)) {
+    set_error("GPNT_SGLDclass: C = max(y) - min(y) + 1 must be in 1..32"); return GPT_ERR_BAD_DIMS;
+  }
+  int32_t st = 0;
+  const int rc = gpt_gpnt_sgld_class_chains(phi, y, n, N, (int64_t)Cd, sigma_theta, m, &eps_theta,
+                                            decay_rate, burnin, maxepoch, &seed, 1, 1, theta_store,
+                                            &st);
+  if (rc != GPT_OK) return rc;
+  if (st) { set_error("Get NaN in theta. Try smaller epsilon"); return GPT_ERR_NAN_THETA; }
+  return GPT_OK;
+}
+
+// Evaluation of device scores (Ntest, C, T) against device labels; every output is a device
+// pointer, the last three optional.  Synchronises st (the workspace is freed on return).
+static int class_eval_core(const double* scores, const int32_t* y, int64_t Ntest, int64_t C,
+                           int64_t T, int64_t avg_first, int64_t avg_last, double* prop_missed,
+                           double* mean_nlp, double* avg, double* mean_scores, int32_t* prediction,
+                           double* nlp, hipStream_t st) {
+  const size_t ntiles = class_eval_tiles(Ntest);
+  DevMem dpn, dpm, dms;
+  HIPCHK(dpn.alloc(8 * ntiles * (size_t)T));
+  HIPCHK(dpm.alloc(4 * ntiles * (size_t)T));
+  if (!mean_scores) {
+    HIPCHK(dms.alloc(8 * (size_t)Ntest * C));
+    mean_scores = dms.as<double>();
+  }
+  ClsTimer tm(2, st);
+  hipError_t e = launch_class_eval(scores, y, Ntest, (int)C, (int)T, dpn.as<double>(),
+                                   dpm.as<int32_t>(), prop_missed, mean_nlp, nullptr, nullptr, st);
+  if (e != hipSuccess) return hip_fail(e, "class_eval kernel");
+  e = launch_class_mean(scores, Ntest, (int)C, (int)avg_first, (int)avg_last, mean_scores, st);
+  if (e != hipSuccess) return hip_fail(e, "class_mean kernel");
+  e = launch_class_eval(mean_scores, y, Ntest, (int)C, 1, dpn.as<double>(), dpm.as<int32_t>(), avg,
+                        avg + 1, prediction, nlp, st);
+  if (e != hipSuccess) return hip_fail(e, "class_eval kernel");
+  tm.stop();
+  HIPCHK(hipStreamSynchronize(st));
+  return GPT_OK;
+}
+
+static bool valid_class_eval(const void* scores, const void* ytest, int64_t Ntest, int64_t C,
+                             int64_t T, int64_t avg_first, int64_t avg_last, const void* pm,
+                             const void* nl, const void* avg) {
+  if (!scores || !ytest || !pm || !nl || !avg) { set_error("class_eval: null argument"); return false; }
+  if (Ntest < 1 || C < 1 || T < 1 || C > (1 << 20) || T > (1 << 24) || Ntest > (1LL << 40)) {
+    set_error("class_eval: bad dimensions"); return false;
+  }
+  if (avg_first < 0 || avg_last > T || avg_first >= avg_last) {
+    set_error("class_eval: the window must satisfy 0 <= avg_first < avg_last <= T"); return false;
+  }
+  return true;
+}
+
+static bool valid_labels(const int32_t* y, int64_t Ntest, int64_t C) {
+  for (int64_t i = 0; i < Ntest; ++i)
+    if (y[i] < 1 || y[i] > C) { set_error("class_eval: labels must be in 1..C"); return false; }
+  return true;
+}
+
+extern "C" int gpt_class_eval_dev(const double* scores_dev, const int32_t* ytest_dev, int64_t Ntest,
+                                  int64_t C, int64_t T, int64_t avg_first, int64_t avg_last,
+                                  double* prop_missed_dev, double* mean_nlp_dev, double* avg_dev,
+                                  double* mean_scores_dev, int32_t* prediction_dev, double* nlp_dev,
+                                  void* hip_stream) {
+  if (!valid_class_eval(scores_dev, ytest_dev, Ntest, C, T, avg_first, avg_last, prop_missed_dev,
+                        mean_nlp_dev, avg_dev))
+    return GPT_ERR_BAD_DIMS;
+  std::vector<int32_t> yh((size_t)Ntest);                     // the labels are checked on the host
+  HIPCHK(hipMemcpyAsync(yh.data(), ytest_dev, 4 * (size_t)Ntest, hipMemcpyDeviceToHost,
+                        (hipStream_t)hip_stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
+  if (!valid_labels(yh.data(), Ntest, C)) return GPT_ERR_BAD_DIMS;
+  return class_eval_core(scores_dev, ytest_dev, Ntest, C, T, avg_first, avg_last, prop_missed_dev,
+                         mean_nlp_dev, avg_dev, mean_scores_dev, prediction_dev, nlp_dev,
+                         (hipStream_t)hip_stream);
+}
+
+// The evaluation of device scores into host outputs (ytest already checked).
+static int class_eval_to_host(const double* dscores, const int32_t* ytest, int64_t Ntest, int64_t C,
+                              int64_t T, int64_t avg_first, int64_t avg_last, double* prop_missed,
+                              double* mean_nlp, double* avg, double* mean_scores,
+                              int32_t* prediction, double* nlp) {
+  DevMem dy, dpm, dnl, davg, dms, dpr, dnp;
+  HIPCHK(dy.alloc(4 * (size_t)Ntest));
+  HIPCHK(dpm.alloc(8 * (size_t)T));
+  HIPCHK(dnl.alloc(8 * (size_t)T));
+  HIPCHK(davg.alloc(16));
+  HIPCHK(dms.alloc(8 * (size_t)Ntest * C));
+  HIPCHK(dpr.alloc(4 * (size_t)Ntest));
+  HIPCHK(dnp.alloc(8 * (size_t)Ntest));
+  HIPCHK(hipMemcpy(dy.p, ytest, 4 * (size_t)Ntest, hipMemcpyHostToDevice));
+  const int rc = class_eval_core(dscores, dy.as<int32_t>(), Ntest, C, T, avg_first, avg_last,
+                                 dpm.as<double>(), dnl.as<double>(), davg.as<double>(),
+                                 dms.as<double>(), dpr.as<int32_t>(), dnp.as<double>(), nullptr);
+  if (rc != GPT_OK) return rc;
+  HIPCHK(hipMemcpy(prop_missed, dpm.p, 8 * (size_t)T, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(mean_nlp, dnl.p, 8 * (size_t)T, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(avg, davg.p, 16, hipMemcpyDeviceToHost));
+  if (mean_scores) HIPCHK(hipMemcpy(mean_scores, dms.p, 8 * (size_t)Ntest * C, hipMemcpyDeviceToHost));
+  if (prediction) HIPCHK(hipMemcpy(prediction, dpr.p, 4 * (size_t)Ntest, hipMemcpyDeviceToHost));
+  if (nlp) HIPCHK(hipMemcpy(nlp, dnp.p, 8 * (size_t)Ntest, hipMemcpyDeviceToHost));
+  return GPT_OK;
+}
+
+extern "C" int gpt_class_eval(const double* scores, const int32_t* ytest, int64_t Ntest, int64_t C,
+                              int64_t T, int64_t avg_first, int64_t avg_last,
+                              double* prop_missed_out, double* mean_nlp_out, double* avg_out,
+                              double* mean_scores_out, int32_t* prediction_out, double* nlp_out) {
+  if (!valid_class_eval(scores, ytest, Ntest, C, T, avg_first, avg_last, prop_missed_out,
+                        mean_nlp_out, avg_out) || !valid_labels(ytest, Ntest, C))
+    return GPT_ERR_BAD_DIMS;
+  DevMem ds;
+  const size_t bytes = 8 * (size_t)Ntest * C * T;
+  HIPCHK(ds.alloc(bytes));
+  HIPCHK(hipMemcpy(ds.p, scores, bytes, hipMemcpyHostToDevice));
+  return class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
+                            prop_missed_out, mean_nlp_out, avg_out, mean_scores_out, prediction_out,
+                            nlp_out);
+}
+
+// ImageNoTensorExperiment.jl:50-75 on T stored full-theta samples: scores = phitestᵀ·theta for
+// every (class, sample) in one launch, then the evaluation.
+extern "C" int gpt_gpnt_pred_class(const double* theta, const double* phitest, const int32_t* ytest,
+                                   int64_t n, int64_t Ntest, int64_t C, int64_t T,
+                                   int64_t avg_first, int64_t avg_last, double* prop_missed_out,
+                                   double* mean_nlp_out, double* avg_out, double* mean_scores_out,
+                                   int32_t* prediction_out, double* nlp_out, double* scores_out) {
+  if (!theta || !phitest || n < 1 || n > (1 << 24)) {
+    set_error("gpt_gpnt_pred_class: bad arguments"); return GPT_ERR_BAD_DIMS;
+  }
+  if (!valid_class_eval(theta, ytest, Ntest, C, T, avg_first, avg_last, prop_missed_out,
+                        mean_nlp_out, avg_out) || !valid_labels(ytest, Ntest, C))
+    return GPT_ERR_BAD_DIMS;
+  if ((C * T + 63) / 64 > 65535) { set_error("gpt_gpnt_pred_class: C*T too large"); return GPT_ERR_BAD_DIMS; }
+  DevMem dth, dphi, ds;
+  const size_t sbytes = 8 * (size_t)Ntest * C * T;
+  HIPCHK(dth.alloc(8 * (size_t)n * C * T));
+  HIPCHK(dphi.alloc(8 * (size_t)n * Ntest));
+  HIPCHK(ds.alloc(sbytes));
+  HIPCHK(hipMemcpy(dth.p, theta, 8 * (size_t)n * C * T, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dphi.p, phitest, 8 * (size_t)n * Ntest, hipMemcpyHostToDevice));
+  {
+    ClsTimer tm(1, nullptr);
+    hipError_t e = launch_nt_scores(dphi.as<double>(), dth.as<double>(), (int)n, Ntest, C * T,
+                                    ds.as<double>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "nt_scores kernel");
+    tm.stop();
+  }
+  const int rc = class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
+                                    prop_missed_out, mean_nlp_out, avg_out, mean_scores_out,
+                                    prediction_out, nlp_out);
+  if (rc != GPT_OK) return rc;
+  if (scores_out) HIPCHK(hipMemcpy(scores_out, ds.p, sbytes, hipMemcpyDeviceToHost));
+  return GPT_OK;
+}
+
+// ImageExperiment.jl:50-72 on T stored samples of GPTclassification: w (Q, C, T) and
+// U (n, r, D, C, T) are S = C·T stacked samples in (c, t) order, so launch_pred's fhat (Ntest, S)
+// is the scores array; phitest is uploaded once.
+extern "C" int gpt_pred_class(const double* w, const double* U, const int32_t* I,
+                              const double* phitest, const int32_t* ytest, int64_t n, int64_t D,
+                              int64_t Ntest, int64_t r, int64_t Q, int64_t C, int64_t T,
+                              int64_t avg_first, int64_t avg_last, double* prop_missed_out,
+                              double* mean_nlp_out, double* avg_out, double* mean_scores_out,
+                              int32_t* prediction_out, double* nlp_out, double* scores_out) {
+  if (!w || !U || !I || !phitest) { set_error("gpt_pred_class: null argument"); return GPT_ERR_BAD_DIMS; }
+  if (!valid_pred(n, D, Ntest, r, Q)) return GPT_ERR_BAD_DIMS;
+  if (!valid_class_eval(w, ytest, Ntest, C, T, avg_first, avg_last, prop_missed_out, mean_nlp_out,
+                        avg_out) || !valid_labels(ytest, Ntest, C))
+    return GPT_ERR_BAD_DIMS;
+  if (C * T > (1LL << 30)) { set_error("gpt_pred_class: C*T too large"); return GPT_ERR_BAD_DIMS; }
+  const int64_t S = C * T;
+  std::vector<int32_t> I0((size_t)Q * D);
+  for (size_t x = 0; x < I0.size(); ++x) {
+    if (I[x] < 1 || I[x] > r) { set_error("I entries must be in 1..r"); return GPT_ERR_BAD_DIMS; }
+    I0[x] = I[x] - 1;
+  }
+  DevMem dw, dU, dI, dphi, ds;
+  const size_t sbytes = 8 * (size_t)Ntest * S;
+  HIPCHK(dw.alloc(8 * (size_t)Q * S));
+  HIPCHK(dU.alloc(8 * (size_t)n * r * D * S));
+  HIPCHK(dI.alloc(4 * I0.size()));
+  HIPCHK(dphi.alloc(8 * (size_t)n * D * Ntest));
+  HIPCHK(ds.alloc(sbytes));
+  HIPCHK(hipMemcpy(dw.p, w, 8 * (size_t)Q * S, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dU.p, U, 8 * (size_t)n * r * D * S, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dI.p, I0.data(), 4 * I0.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dphi.p, phitest, 8 * (size_t)n * D * Ntest, hipMemcpyHostToDevice));
+  int rc;
+  {
+    ClsTimer tm(1, nullptr);
+    rc = gpt_pred_dev(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(), n, D,
+                      Ntest, r, Q, S, ds.as<double>(), nullptr);
+    if (rc != GPT_OK) return rc;
+    tm.stop();
+  }
+  rc = class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last, prop_missed_out,
+                          mean_nlp_out, avg_out, mean_scores_out, prediction_out, nlp_out);
+  if (rc != GPT_OK) return rc;
+  if (scores_out) HIPCHK(hipMemcpy(scores_out, ds.p, sbytes, hipMemcpyDeviceToHost));
+  return GPT_OK;
+}
+
 extern "C" int gpt_tgp_gibbs(const double* b, const double* y, int64_t n, int64_t D, int64_t N,
                              int64_t r, int64_t q, double sigma, int64_t num_iterations,
                              int64_t burnin, uint64_t seed, const int32_t* I, double* W_out,

@@ -351,6 +351,39 @@ hipError_t launch_gpnt(const double* phi, const double* y, const int32_t* order,
                        double* theta_store, int32_t* status, const long long* tbase, int t_local,
                        hipStream_t st);
 
+// Classification (cls.hip).  GPNT_SGLDclass: one workgroup per chain, theta (n x C) in LDS for a
+// launch of up to one epoch's steps.
+struct NtcChain {
+  const int32_t* order;  // epochs*N cumulative epoch orders of the chain's seed (0-based rows)
+  double* theta;         // n*C     current theta
+  double* store;         // n*C*kept
+  int32_t* status;       // 0 ok, GPT_ERR_NAN_THETA
+  uint64_t seed;
+  double eps_theta;
+};
+struct NtcLayout {
+  int CC, stage;         // CC: C rounded up to 2, 4, 8, 16, 32; stage: the batch's phi is in LDS
+  size_t o_theta, o_idx, o_yb, o_P, o_flag, o_phi, base, bytes;   // base: bytes without the staged phi
+};
+NtcLayout ntc_layout(int n, int C, int m);
+// steps t0 .. t0+nsteps-1 (0-based, those below total) of every chain; y0: N 0-based labels
+hipError_t launch_ntc_chain(const double* phi, const int32_t* y0, const NtcChain* chains,
+                            int nchains, int n, int N, int C, int m, int nb, long long total,
+                            double decay_rate, int store_every, long long t0, int nsteps,
+                            hipStream_t st);
+// scores (Ntest, S) = phitestᵀ (n, Ntest) · theta (n, S)
+hipError_t launch_nt_scores(const double* phitest, const double* theta, int n, long long Ntest,
+                            long long S, double* scores, hipStream_t st);
+// Evaluation of scores (Ntest, C, T) against labels y in 1..C: part_nlp / part_miss hold
+// class_eval_tiles(Ntest)*T partial sums; prop_missed, mean_nlp (T); pred_out, nlp_out
+// (Ntest*T, optional).
+size_t class_eval_tiles(long long Ntest);
+hipError_t launch_class_eval(const double* scores, const int32_t* y, long long Ntest, int C, int T,
+                             double* part_nlp, int32_t* part_miss, double* prop_missed,
+                             double* mean_nlp, int32_t* pred_out, double* nlp_out, hipStream_t st);
+hipError_t launch_class_mean(const double* scores, long long Ntest, int C, int first, int last,
+                             double* mean_out, hipStream_t st);
+
 // Host-side Philox consumers (init / permutations / samplenz)
 void host_init_state(int n, int r, int D, int Q, uint64_t seed, bool stiefel, double sigma_w,
                      double* w, double* U, int cls = 0, bool cls_init = false);

@@ -343,6 +343,71 @@ int gpt_gpnt_sgld(const double* phi, const double* y, int64_t n, int64_t N, doub
                   double sigma_theta, int64_t m, double eps_theta, double decay_rate,
                   int64_t burnin, int64_t maxepoch, uint64_t seed, double* theta_store);
 
+/* ---- classification: the full-theta softmax sampler and the evaluation of scores ------ */
+/* GPNT_SGLDclass(phi,y,sigma_theta,m,eps_theta,decay_rate,burnin,maxepoch,param_seed)
+ * GPT_SGLD.jl:851-901.  phi (n, N); y (N) integer labels in 1..C, C = max(y) - min(y) + 1 <= 32
+ * (anything else is GPT_ERR_BAD_DIMS); theta_store (n, C, (burnin+maxepoch)*numbatches).
+ * RNG: theta[:, c] = sigma_theta*normals(n, seed, 0, THETA_INIT, c); the noise of 1-based step t
+ * and class c is normals(n, seed, t-1, THETA_NOISE, c); epoch orders as GPNT_SGLD.  As the
+ * reference, the prior term of the gradient is +theta (sigma_theta scales the initial draw only).
+ * A NaN in theta returns GPT_ERR_NAN_THETA with a zero-filled store (:894-897). */
+int gpt_gpnt_sgld_class(const double* phi, const double* y, int64_t n, int64_t N,
+                        double sigma_theta, int64_t m, double eps_theta, double decay_rate,
+                        int64_t burnin, int64_t maxepoch, uint64_t seed, double* theta_store);
+/* Sibling chains of one launch on a shared phi / y (step-size and seed sweeps,
+ * ImageNoTensorExperiment.jl:36-38): chain k runs GPNT_SGLDclass with eps_theta[k] and seeds[k],
+ * labels in 1..ncls.  store_every >= 1 keeps the 1-based steps divisible by it (1: every step, as
+ * the reference; numbatches: the epoch ends); theta_store (n, ncls, kept, nchains), kept =
+ * total steps / store_every.  status[k] = GPT_ERR_NAN_THETA and a zero-filled store for a chain
+ * that met a NaN; the other chains are untouched and the call returns GPT_OK. */
+int gpt_gpnt_sgld_class_chains(const double* phi, const double* y, int64_t n, int64_t N,
+                               int64_t ncls, double sigma_theta, int64_t m, const double* eps_theta,
+                               double decay_rate, int64_t burnin, int64_t maxepoch,
+                               const uint64_t* seeds, int32_t nchains, int64_t store_every,
+                               double* theta_store, int32_t* status);
+/* Evaluation of class scores (ImageExperiment.jl:50-72, ImageNoTensorExperiment.jl:50-75).
+ * scores (Ntest, C, T) column-major, ytest (Ntest) labels in 1..C.  Per sample t:
+ *   prop_missed_out[t] = 1 - #(indmax(scores[i,:,t]) == ytest[i])/Ntest (ties: the first index),
+ *   mean_nlp_out[t] = mean_i (logsumexp(scores[i,:,t]) - scores[i,ytest[i],t]),
+ * and the same two figures, avg_out[0] and avg_out[1], on mean_scores (Ntest, C), the mean of
+ * the samples avg_first <= t < avg_last (0-based, half open).  Optional outputs (may be NULL):
+ * mean_scores_out (Ntest, C), prediction_out (Ntest, 1-based) and nlp_out (Ntest) of the
+ * averaged scores.  A null required pointer, an empty window or one outside [0, T], or a label
+ * outside 1..C is GPT_ERR_BAD_DIMS before any kernel runs. */
+int gpt_class_eval(const double* scores, const int32_t* ytest, int64_t Ntest, int64_t C, int64_t T,
+                   int64_t avg_first, int64_t avg_last, double* prop_missed_out,
+                   double* mean_nlp_out, double* avg_out, double* mean_scores_out,
+                   int32_t* prediction_out, double* nlp_out);
+/* The same on device pointers (the labels are read back once to be checked); synchronises
+ * hip_stream. */
+int gpt_class_eval_dev(const double* scores_dev, const int32_t* ytest_dev, int64_t Ntest, int64_t C,
+                       int64_t T, int64_t avg_first, int64_t avg_last, double* prop_missed_dev,
+                       double* mean_nlp_dev, double* avg_dev, double* mean_scores_dev,
+                       int32_t* prediction_dev, double* nlp_dev, void* hip_stream);
+/* Full-theta evaluation: scores[i, c, t] = sum_j phitest[j, i]*theta[j, c, t] for theta (n, C, T)
+ * and phitest (n, Ntest) in one launch, then gpt_class_eval on them; scores_out (Ntest, C, T)
+ * optional. */
+int gpt_gpnt_pred_class(const double* theta, const double* phitest, const int32_t* ytest, int64_t n,
+                        int64_t Ntest, int64_t C, int64_t T, int64_t avg_first, int64_t avg_last,
+                        double* prop_missed_out, double* mean_nlp_out, double* avg_out,
+                        double* mean_scores_out, int32_t* prediction_out, double* nlp_out,
+                        double* scores_out);
+/* Tensor evaluation of GPTclassification's stores: w (Q, C, T), U (n, r, D, C, T), I (Q, D)
+ * 1-based, phitest (n, D, Ntest) uploaded once; the scores are gpt_pred_dev's on the S = C*T
+ * stacked samples (same routes, passes and environment switches, and the same shape limits),
+ * then gpt_class_eval on them; scores_out (Ntest, C, T) optional. */
+int gpt_pred_class(const double* w, const double* U, const int32_t* I, const double* phitest,
+                   const int32_t* ytest, int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q,
+                   int64_t C, int64_t T, int64_t avg_first, int64_t avg_last,
+                   double* prop_missed_out, double* mean_nlp_out, double* avg_out,
+                   double* mean_scores_out, int32_t* prediction_out, double* nlp_out,
+                   double* scores_out);
+
+/* Device-event times in ms of the last classification calls on this thread (measurement,
+ * scripts/time_class.py): ms_out[0] the sampler's launches, [1] the scores (nt_scores_kernel, or
+ * the stacked-sample prediction of gpt_pred_class), [2] the evaluation kernels. */
+int gpt_class_last_timing(double* ms_out);
+
 /* ---- full-theta model: hyper-parameter learning -------------------------------------- */
 /* GPNT_nlogmarginal / GPNT_gradnlogmarginal (GPT_SGLD.jl:921-962) with featureNotensor and
  * gradfeatureNotensor (:109-120, :142-177) as the feature closures: the negative log marginal

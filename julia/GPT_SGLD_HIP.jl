@@ -12,7 +12,8 @@ module GPT_SGLD_HIP
 export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTregression, GPTregression_chains,
        GPTregression_chains_x, GPT_SGLDERM, pred, RMSE,
        GPNT_SGLD, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
-       init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal
+       init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal,
+       GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class
 
 const LIB = get(ENV, "GPTSGLD_LIB", joinpath(@__DIR__, "..", "gpt_amd", "libgptsgld.so"))
 
@@ -378,6 +379,105 @@ function GPNT_SGLD(phi::Array{Float64,2}, y::Array{Float64}, signal_var::Real, s
     end
     check(rc)
     return store
+end
+
+# GPNT_SGLDclass(phi,y,sigma_theta,m,eps_theta,decay_rate,burnin,maxepoch,param_seed)
+# GPT_SGLD.jl:851 -> theta_store (n, C, (maxepoch+burnin)*numbatches); y holds labels in 1..C
+function GPNT_SGLDclass(phi::Array{Float64,2}, y::Array, sigma_theta::Real, m::Integer,
+                        eps_theta::Real, decay_rate::Real, burnin::Integer, maxepoch::Integer,
+                        param_seed::Integer)
+    n, N = size(phi)
+    yf = collect(Float64, vec(y))
+    ncls = Int(maximum(yf) - minimum(yf) + 1)
+    store = Array{Float64}(undef, n, ncls, (maxepoch + burnin) * cld(N, m))
+    rc = ccall((:gpt_gpnt_sgld_class, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Float64, Int64, Float64, Float64, Int64,
+                Int64, UInt64, Ptr{Float64}),
+               phi, yf, n, N, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch, param_seed,
+               store)
+    if rc == 4
+        println("Get NaN in theta. Try smaller epsilon")
+        return zeros(n)
+    end
+    check(rc)
+    return store
+end
+
+# Sibling GPNT_SGLDclass chains on one phi / y (step-size and seed sweeps,
+# ImageNoTensorExperiment.jl:36-38): (theta_store (n, C, kept, nchains), status (nchains));
+# store_every keeps the 1-based steps divisible by it (cld(N, m): the epoch ends)
+function GPNT_SGLDclass_chains(phi::Array{Float64,2}, y::Array, sigma_theta::Real, m::Integer,
+                               eps_thetas::Vector{Float64}, decay_rate::Real, burnin::Integer,
+                               maxepoch::Integer, seeds::Vector{UInt64}; store_every::Integer=1)
+    n, N = size(phi); nch = length(seeds)
+    yf = collect(Float64, vec(y))
+    ncls = Int(maximum(yf) - minimum(yf) + 1)
+    kept = div((maxepoch + burnin) * cld(N, m), store_every)
+    store = zeros(Float64, n, ncls, kept, nch); status = zeros(Int32, nch)
+    check(ccall((:gpt_gpnt_sgld_class_chains, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Float64, Int64, Ptr{Float64},
+                 Float64, Int64, Int64, Ptr{UInt64}, Int32, Int64, Ptr{Float64}, Ptr{Int32}),
+                phi, yf, n, N, ncls, sigma_theta, m, eps_thetas, decay_rate, burnin, maxepoch,
+                seeds, nch, store_every, store, status))
+    return store, status
+end
+
+# The result of the evaluation functions (ImageExperiment.jl:50-72): per-sample prop_missed and
+# mean_nlp, the same on the scores averaged over `window` (1-based, inclusive, as 60:100 there),
+# those averaged scores, and the prediction and nlp of every test row on them
+struct ClassEval
+    prop_missed::Vector{Float64}; mean_nlp::Vector{Float64}
+    avg_prop_missed::Float64; avg_mean_nlp::Float64
+    mean_fhat::Array{Float64,2}; prediction::Vector{Int32}; nlp::Vector{Float64}
+    scores::Array{Float64,3}
+end
+class_window(window, T) = window === nothing ? (0, T) : (first(window) - 1, last(window))
+
+function class_eval(scores::Array{Float64,3}, ytest::Array; window=nothing)
+    Nt, ncls, T = size(scores); a, b = class_window(window, T)
+    yi = collect(Int32, vec(ytest))
+    pm = Array{Float64}(undef, T); nl = Array{Float64}(undef, T); avg = Array{Float64}(undef, 2)
+    mf = Array{Float64}(undef, Nt, ncls); pr = Array{Int32}(undef, Nt); np = Array{Float64}(undef, Nt)
+    check(ccall((:gpt_class_eval, LIB), Cint,
+                (Ptr{Float64}, Ptr{Int32}, Int64, Int64, Int64, Int64, Int64, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                scores, yi, Nt, ncls, T, a, b, pm, nl, avg, mf, pr, np))
+    return ClassEval(pm, nl, avg[1], avg[2], mf, pr, np, scores)
+end
+
+# theta_store (n, C, T) full-theta samples, phitest (n, Ntest): ImageNoTensorExperiment.jl:50-75
+function GPNT_pred_class(theta_store::Array{Float64,3}, phitest::Array{Float64,2}, ytest::Array;
+                         window=nothing)
+    n, ncls, T = size(theta_store); Nt = size(phitest, 2); a, b = class_window(window, T)
+    yi = collect(Int32, vec(ytest))
+    pm = Array{Float64}(undef, T); nl = Array{Float64}(undef, T); avg = Array{Float64}(undef, 2)
+    mf = Array{Float64}(undef, Nt, ncls); pr = Array{Int32}(undef, Nt); np = Array{Float64}(undef, Nt)
+    sc = Array{Float64}(undef, Nt, ncls, T)
+    check(ccall((:gpt_gpnt_pred_class, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Int64, Int64, Int64, Int64, Int64, Int64,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64},
+                 Ptr{Float64}),
+                theta_store, phitest, yi, n, Nt, ncls, T, a, b, pm, nl, avg, mf, pr, np, sc))
+    return ClassEval(pm, nl, avg[1], avg[2], mf, pr, np, sc)
+end
+
+# GPTclassification's stores w (Q, C, T), U (n, r, D, C, T), phitest (n, D, Ntest):
+# ImageExperiment.jl:50-72 with one upload of phitest
+function pred_class(w_store::Array{Float64,3}, U_store::Array{Float64,5}, I::Array{Int32,2},
+                    phitest::Array{Float64,3}, ytest::Array; window=nothing)
+    n, D, Nt = size(phitest); Q, ncls, T = size(w_store); r = size(U_store, 2)
+    a, b = class_window(window, T)
+    yi = collect(Int32, vec(ytest))
+    pm = Array{Float64}(undef, T); nl = Array{Float64}(undef, T); avg = Array{Float64}(undef, 2)
+    mf = Array{Float64}(undef, Nt, ncls); pr = Array{Int32}(undef, Nt); np = Array{Float64}(undef, Nt)
+    sc = Array{Float64}(undef, Nt, ncls, T)
+    check(ccall((:gpt_pred_class, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Int64, Int64,
+                 Int64, Int64, Int64, Int64, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                w_store, U_store, I, phitest, yi, n, D, Nt, r, Q, ncls, T, a, b, pm, nl, avg, mf,
+                pr, np, sc))
+    return ClassEval(pm, nl, avg[1], avg[2], mf, pr, np, sc)
 end
 
 # GPNT_nlogmarginal / GPNT_gradnlogmarginal (GPT_SGLD.jl:921-962) with featureNotensor /
