@@ -30,6 +30,9 @@ Same function names, argument meaning, return values and error behaviour as the 
                                                               ImageExperiment.jl:50-72
     NoTensorMarginal(X, y, Z, b), GPNT_nlogmarginal, GPNT_gradnlogmarginal, GPNT_hyperparameters,
     GPNT_hyperparameters_optim                                GPT_SGLD.jl:921-1002
+    GP_nlogmarginal(X, y, signal_var, sigma_RBF2, length_scale)   GPT_SGLD.jl:905
+    ExactGP(X, y): nlogmarginal, gradnlogmarginal, value_and_grad, alpha, predict
+                                                              GPkit InfExact / prediction
     datawhitening(X), proj, geod are not on the device path (host prep / inside the kernel).
 
 Arrays follow Julia's column-major layout: ``phi`` is (n, D, N) Fortran-ordered, ``U`` is
@@ -40,6 +43,7 @@ Arrays follow Julia's column-major layout: ``phi`` is (n, D, N) Fortran-ordered,
 RNG: Julia's MersenneTwister stream is replaced by the framework's Philox contract
 (oracle/philox.py documents it); seeds play the same role (``srand(param_seed)``).
 """
+import collections
 import contextlib
 import math
 import os
@@ -832,6 +836,137 @@ def gpnt_nlogmarginal_oneshot(X, y, Z, b, hyperparams, want_grad=True):
     check(lib().gpt_gpnt_nlogmarginal(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), Z.shape[0], _ptr(h),
                                       h.size, 1 if want_grad else 0, C.byref(val), _ptr(grad)))
     return (val.value, grad) if want_grad else val.value
+
+
+# ------------------------------------------------------------------ exact GP regression
+GPPrediction = collections.namedtuple("GPPrediction", "ymu ys2 fmu fs2 lp")
+
+
+class ExactGP:
+    """Device-resident exact GP regression: squared-exponential kernel (iso or ARD), Gaussian
+    noise, zero mean — GP_nlogmarginal (GPT_SGLD.jl:905-915) and GPkit's InfExact / prediction
+    with CovSEiso or CovSEard and LikGauss, the reference's quality ceiling.
+
+    ``X`` (N, D) and ``y`` (N) are uploaded once; every method takes
+    ``h = [length_scale (D entries, or one: the iso form); sigma_RBF; signal_var]``, the vector of
+    NoTensorMarginal.  N <= 16384, D <= 16.  A failed Cholesky raises ``GPTError``
+    (GPT_ERR_NOT_SPD) and leaves the object usable.
+
+    ``nlogmarginal`` and ``gradnlogmarginal`` are the callables ``GPNT_hyperparameters`` and
+    ``GPNT_hyperparameters_optim`` take (the counterpart of GPkit's ``optinf``):
+    ``GPNT_hyperparameters(gp.nlogmarginal, gp.gradnlogmarginal, init, lbounds)``.  GPkit's
+    ``dnlZ`` (with respect to log l, log sigma_RBF, log sqrt(signal_var)) is the gradient times
+    ``[l..., sigma_RBF, 2 signal_var]``."""
+
+    def __init__(self, X, y):
+        X = _f64(X)
+        if X.ndim != 2:
+            raise ValueError("X must be (N, D)")
+        N, D = X.shape
+        y = _f64(np.asarray(y, dtype=np.float64).ravel())
+        if y.size != N:
+            raise ValueError("y must have length N")
+        self.N, self.D = N, D
+        self._h = C.c_void_p()
+        check(lib().gpt_egp_create(_ptr(X), N, D, _ptr(y), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gpt_egp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # interpreter shutdown: the library may be gone already
+            pass
+
+    def _eval(self, h, want_grad, want_alpha=False):
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        val = C.c_double()
+        grad = np.empty(h.size) if want_grad else None
+        alpha = np.empty(self.N) if want_alpha else None
+        check(lib().gpt_egp_eval(self._h, _ptr(h), h.size, 1 if want_grad else 0, C.byref(val),
+                                 _ptr(grad) if want_grad else None,
+                                 _ptr(alpha) if want_alpha else None))
+        return val.value, grad, alpha
+
+    def nlogmarginal(self, h):
+        return self._eval(h, False)[0]
+
+    def gradnlogmarginal(self, h):
+        return self._eval(h, True)[1]
+
+    def value_and_grad(self, h):
+        return self._eval(h, True)[:2]
+
+    def alpha(self, h):
+        """(K + signal_var I)^-1 y at h."""
+        return self._eval(h, False, True)[2]
+
+    def predict(self, h, Xtest, ytest=None, chunk=None):
+        """GPkit's ``prediction``: the named tuple (ymu, ys2, fmu, fs2, lp) for ``Xtest``
+        (Ntest, D); lp is None without ``ytest``.  The factor of the last evaluation is reused
+        when ``h`` equals its hyper-parameters bit for bit.  ``chunk`` test rows go through the
+        device at a time (None: the library's choice); the results do not depend on it."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        Xtest = _f64(Xtest)
+        if Xtest.ndim != 2 or Xtest.shape[1] != self.D:
+            raise ValueError("Xtest must be (Ntest, D)")
+        Nt = Xtest.shape[0]
+        yt = None
+        if ytest is not None:
+            yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+            if yt.size != Nt:
+                raise ValueError("ytest must have length Ntest")
+        fmu, fs2 = np.empty(Nt), np.empty(Nt)
+        lp = np.empty(Nt) if yt is not None else None
+        check(lib().gpt_egp_predict(self._h, _ptr(h), h.size, _ptr(Xtest), Nt,
+                                    _ptr(yt) if yt is not None else None,
+                                    0 if chunk is None else int(chunk), _ptr(fmu), _ptr(fs2),
+                                    _ptr(lp) if lp is not None else None))
+        return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+
+
+def _gp_hyper(signal_var, sigma_RBF2, length_scale):
+    ls = np.atleast_1d(np.asarray(length_scale, dtype=np.float64)).ravel()
+    return _f64(np.concatenate([ls, [math.sqrt(sigma_RBF2), signal_var]]))
+
+
+def gp_nlogmarginal_oneshot(X, y, hyperparams, want_grad=True):
+    """The one-shot host-pointer entry the Julia shim binds (gpt_gp_nlogmarginal)."""
+    X = _f64(X)
+    N, D = X.shape
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    val = C.c_double()
+    grad = np.empty(h.size)
+    check(lib().gpt_gp_nlogmarginal(_ptr(X), N, D, _ptr(y), _ptr(h), h.size,
+                                    1 if want_grad else 0, C.byref(val), _ptr(grad)))
+    return (val.value, grad) if want_grad else val.value
+
+
+def gp_predict_oneshot(X, y, hyperparams, Xtest, ytest=None):
+    """The one-shot host-pointer prediction the Julia shim binds (gpt_gp_predict)."""
+    X, Xtest = _f64(X), _f64(Xtest)
+    N, D = X.shape
+    Nt = Xtest.shape[0]
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel()) if ytest is not None else None
+    fmu, fs2 = np.empty(Nt), np.empty(Nt)
+    lp = np.empty(Nt) if yt is not None else None
+    check(lib().gpt_gp_predict(_ptr(X), N, D, _ptr(y), _ptr(h), h.size, _ptr(Xtest), Nt,
+                               _ptr(yt) if yt is not None else None, _ptr(fmu), _ptr(fs2),
+                               _ptr(lp) if lp is not None else None))
+    return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+
+
+def GP_nlogmarginal(X, y, signal_var, sigma_RBF2, length_scale):
+    """GPT_SGLD.jl:905-915: the exact GP's negative log marginal likelihood; ``sigma_RBF2`` is
+    sigma_RBF squared, ``length_scale`` a scalar or D entries.  It does not print."""
+    return gp_nlogmarginal_oneshot(X, y, _gp_hyper(signal_var, sigma_RBF2, length_scale),
+                                   want_grad=False)
 
 
 def _log_space_minimize(nlogmarginal, gradnlogmarginal, init_hyperparams, bounds, xtol, ftol):

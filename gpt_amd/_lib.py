@@ -133,6 +133,16 @@ SIGNATURES = {
     "gpt_nlml_destroy": (C.c_int, [C.c_void_p]),
     "gpt_gpnt_nlogmarginal": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_int64, P_D,
                                         C.c_int64, C.c_int64, P_D, P_D]),
+    "gpt_egp_create": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, C.POINTER(C.c_void_p)]),
+    "gpt_egp_eval": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int32, P_D, P_D, P_D]),
+    "gpt_egp_eval_timed": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int32, P_D, P_D, P_D]),
+    "gpt_egp_predict": (C.c_int, [C.c_void_p, P_D, C.c_int64, P_D, C.c_int64, P_D, C.c_int64,
+                                  P_D, P_D, P_D]),
+    "gpt_egp_destroy": (C.c_int, [C.c_void_p]),
+    "gpt_gp_nlogmarginal": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, C.c_int64, C.c_int64,
+                                      P_D, P_D]),
+    "gpt_gp_predict": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, C.c_int64, P_D, C.c_int64,
+                                 P_D, P_D, P_D, P_D]),
     "gpt_sgld_wonly": (C.c_int, [C.POINTER(SGLDConfig), P_D, P_D, P_I32, P_D, P_D, P_D, P_D, P_D]),
     "gpt_pred_mean_x": (C.c_int, [P_D, P_D, P_I32, P_D, P_D, C.c_int64, C.c_int64, P_D, C.c_int64,
                                   C.c_double, C.c_double, P_D, P_D, C.c_int64, C.c_int64, C.c_int64,

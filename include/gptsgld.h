@@ -441,6 +441,49 @@ int gpt_gpnt_nlogmarginal(const double* X, int64_t N, int64_t D, const double* y
                           const double* b, int64_t n, const double* hyper, int64_t Lh,
                           int64_t want_grad, double* nlml_out, double* grad_out);
 
+/* ---- exact GP regression (the reference's quality ceiling) ------------------------------ */
+/* GP_nlogmarginal (GPT_SGLD.jl:905-915) and GPkit's InfExact / prediction with CovSEiso or
+ * CovSEard, LikGauss and a zero mean: K_ij = sigma_RBF^2 exp(-1/2 sum_k ((x_ik - x_jk)/l_k)^2),
+ * A = K + signal_var*I = L*L', alpha = A^-1 y,
+ *   nlml = sum log L_ii + y'alpha/2 + (N/2) log 2 pi,
+ * and its gradient with respect to
+ *   hyper = [length_scale (D entries, or 1: the iso form); sigma_RBF; signal_var],
+ * Lh = D + 2 or 3 (GPkit's dnlZ is this gradient times l_k, sigma_RBF and 2*signal_var).
+ * X (N, D) column-major, y (N); N <= 16384, D <= 16.  A hyper-parameter that is not positive and
+ * finite, a dimension out of range or a NULL array is GPT_ERR_BAD_DIMS before any device call or
+ * allocation.  When the blocked Cholesky meets a pivot that is not positive the call returns
+ * GPT_ERR_NOT_SPD with NaN-filled outputs and the handle stays usable.
+ *
+ * The evaluator keeps X, y, the factor and its scratch on the device (N*N doubles, and two more
+ * N*N buffers from the first gradient on).  grad (Lh) may be NULL when want_grad = 0; alpha (N,
+ * optional) receives A^-1 y. */
+typedef struct gpt_egp gpt_egp;
+int gpt_egp_create(const double* X, int64_t N, int64_t D, const double* y, gpt_egp** out);
+int gpt_egp_eval(gpt_egp* h, const double* hyper, int64_t Lh, int32_t want_grad, double* nlml,
+                 double* grad, double* alpha);
+/* Diagnostics (scripts/time_exactgp.py): gpt_egp_eval with device-event times in ms of its 6
+ * phases: kernel matrix, Cholesky, the vector solves, L^-1, P = A^-1, the gradient pass (the last
+ * three are 0 when want_grad = 0). */
+int gpt_egp_eval_timed(gpt_egp* h, const double* hyper, int64_t Lh, int32_t want_grad,
+                       double* nlml, double* grad, double* phase_ms);
+/* GPkit prediction at hyper for Xtest (Ntest, D) column-major: fmu = Ks'alpha, fs2 =
+ * max(sigma_RBF^2 - colsum((L^-1 Ks)^2), 0) (ymu = fmu, ys2 = fs2 + signal_var) and, with ytest
+ * and lp, lp = -(ytest - fmu)^2/(2 ys2) - log(2 pi ys2)/2.  The test rows go through the device in
+ * chunks of `chunk` columns (0: the library's choice; at most 4096); a row's results do not depend
+ * on the chunking.  The factor of the last successful evaluation is reused when hyper equals its
+ * hyper bit for bit, otherwise the call fits first. */
+int gpt_egp_predict(gpt_egp* h, const double* hyper, int64_t Lh, const double* Xtest,
+                    int64_t Ntest, const double* ytest, int64_t chunk, double* fmu, double* fs2,
+                    double* lp);
+int gpt_egp_destroy(gpt_egp* h);
+/* One-shot host-pointer forms (create, one call, destroy). */
+int gpt_gp_nlogmarginal(const double* X, int64_t N, int64_t D, const double* y,
+                        const double* hyper, int64_t Lh, int64_t want_grad, double* nlml_out,
+                        double* grad_out);
+int gpt_gp_predict(const double* X, int64_t N, int64_t D, const double* y, const double* hyper,
+                   int64_t Lh, const double* Xtest, int64_t Ntest, const double* ytest,
+                   double* fmu, double* fs2, double* lp);
+
 /* ---- tensor-GP Gibbs sampler (§8 a25) ----------------------------------------------- */
 /* GPT_inf(b,y,sigma,n,r,q,num_iterations,burnin) TGP.jl:37-86 on whitened data.
  * b (n, D, N) column-major feature array (TGP.feature, TGP.jl:6-14), y (N).

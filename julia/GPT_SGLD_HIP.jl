@@ -12,7 +12,7 @@ module GPT_SGLD_HIP
 export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTregression, GPTregression_chains,
        GPTregression_chains_x, GPT_SGLDERM, pred, RMSE,
        GPNT_SGLD, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
-       init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal,
+       init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal, GP_nlogmarginal, GP_gradnlogmarginal, GP_predict,
        GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class
 
 const LIB = get(ENV, "GPTSGLD_LIB", joinpath(@__DIR__, "..", "gpt_amd", "libgptsgld.so"))
@@ -498,5 +498,45 @@ function gpnt_marginal(X::Array{Float64,2}, y::Array{Float64}, Z::Array{Float64,
 end
 GPNT_nlogmarginal(X, y, Z, b, hyperparams) = gpnt_marginal(X, y, Z, b, hyperparams, false)[1]
 GPNT_gradnlogmarginal(X, y, Z, b, hyperparams) = gpnt_marginal(X, y, Z, b, hyperparams, true)[2]
+
+# Exact GP regression (GP_nlogmarginal GPT_SGLD.jl:905-915; GPkit InfExact / prediction with
+# CovSEiso or CovSEard, LikGauss, zero mean).  hyperparams = [length_scale (D entries, or one);
+# sigma_RBF; signal_var]; GPkit's dnlZ is GP_gradnlogmarginal .* [l...; sigma_RBF; 2 signal_var].
+function gp_marginal(X::Array{Float64,2}, y::Array{Float64}, hyperparams::Vector{Float64},
+                     want_grad::Bool)
+    N, D = size(X)
+    nlml = Array{Float64}(undef, 1)
+    grad = Array{Float64}(undef, length(hyperparams))
+    check(ccall((:gpt_gp_nlogmarginal, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+                 Ptr{Float64}, Ptr{Float64}),
+                X, N, D, vec(y), hyperparams, length(hyperparams), Int64(want_grad), nlml, grad))
+    return nlml[1], grad
+end
+# the reference's signature: sigma_RBF2 is sigma_RBF squared, length_scale a scalar or D entries
+GP_nlogmarginal(X, y, signal_var, sigma_RBF2, length_scale) =
+    gp_marginal(X, y, Float64[length_scale...; sqrt(sigma_RBF2); signal_var], false)[1]
+GP_gradnlogmarginal(X, y, hyperparams) = gp_marginal(X, y, hyperparams, true)[2]
+
+# GPkit's prediction: (ymu, ys2, fmu, fs2, lp); lp is nothing without ytest
+function GP_predict(X::Array{Float64,2}, y::Array{Float64}, hyperparams::Vector{Float64},
+                    Xtest::Array{Float64,2}, ytest=nothing)
+    N, D = size(X); Ntest = size(Xtest, 1)
+    size(Xtest, 2) == D || error("Xtest must be (Ntest, D)")
+    fmu = Array{Float64}(undef, Ntest); fs2 = Array{Float64}(undef, Ntest)
+    yt = ytest === nothing ? Float64[] : Vector{Float64}(vec(ytest))
+    lpv = Array{Float64}(undef, ytest === nothing ? 0 : Ntest)
+    GC.@preserve yt lpv begin
+        yp = ytest === nothing ? Ptr{Float64}(C_NULL) : pointer(yt)
+        lpp = ytest === nothing ? Ptr{Float64}(C_NULL) : pointer(lpv)
+        check(ccall((:gpt_gp_predict, LIB), Cint,
+                    (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64},
+                     Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    X, N, D, vec(y), hyperparams, length(hyperparams), Xtest, Ntest, yp, fmu, fs2,
+                    lpp))
+    end
+    lp = ytest === nothing ? nothing : lpv
+    return fmu, fs2 .+ hyperparams[end], fmu, fs2, lp
+end
 
 end # module
