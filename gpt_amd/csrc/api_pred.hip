@@ -1,0 +1,234 @@
+// Features and predictions from host arrays (gpt_feature*, gpt_pred*), the device-pointer
+// prediction entries and the prediction route queries.
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "host_util.h"
+
+using namespace gpt;
+
+static int feature_common(bool tensor, const double* X, int64_t N, int64_t D, const double* ls,
+                          int64_t ls_len, double sigma_rbf, double phi_scale, const double* Z,
+                          const double* b, int64_t n, double* phi_out) {
+  if (!X || !ls || !Z || !b || !phi_out || N < 1 || D < 1 || n < 1) {
+    set_error("bad feature arguments"); return GPT_ERR_BAD_DIMS;
+  }
+  if (ls_len != 1 && ls_len != D) {
+    set_error("dimensions of X and length_scale do not match"); return GPT_ERR_BAD_DIMS;
+  }
+  std::vector<double> lsv(D);
+  for (int64_t k = 0; k < D; ++k) lsv[k] = ls[ls_len == 1 ? 0 : k];
+  const size_t nphi = tensor ? (size_t)n * D * N : (size_t)n * N;
+  DevMem dX, dls, dZ, db, dphi;
+  GPT_HIPCHK(dX.upload(X, (size_t)N * D));
+  GPT_HIPCHK(dls.upload(lsv.data(), lsv.size()));
+  GPT_HIPCHK(dZ.upload(Z, (size_t)n * D));
+  GPT_HIPCHK(db.upload(b, tensor ? (size_t)n * D : (size_t)n));
+  GPT_HIPCHK(dphi.alloc<double>(nphi));
+  hipError_t e;
+  if (tensor) {
+    const double c = phi_scale * std::pow(sigma_rbf, 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
+    e = launch_feature(dX.as<double>(), N, (int)D, dls.as<double>(), c, dZ.as<double>(),
+                       db.as<double>(), (int)n, dphi.as<double>(), nullptr);
+  } else {
+    const double c = std::sqrt(2.0 / (double)n) * sigma_rbf;
+    e = launch_feature_notensor(dX.as<double>(), N, (int)D, dls.as<double>(), c, dZ.as<double>(),
+                                db.as<double>(), (int)n, dphi.as<double>(), nullptr);
+  }
+  if (e != hipSuccess) return hip_fail(e, "feature kernel");
+  GPT_HIPCHK(dphi.download(phi_out, nphi));
+  return GPT_OK;
+}
+
+extern "C" int gpt_feature_dev(const double* X_dev, int64_t N, int64_t D, const double* ls_dev,
+                               int64_t ls_len, double sigma_rbf, double phi_scale,
+                               const double* Z_dev, const double* b_dev, int64_t n, double* phi_dev,
+                               void* hip_stream) {
+  if (!X_dev || !ls_dev || !Z_dev || !b_dev || !phi_dev || N < 1 || D < 1 || n < 1 || ls_len != D) {
+    set_error("bad gpt_feature_dev arguments (ls_len must equal D)"); return GPT_ERR_BAD_DIMS;
+  }
+  const double c = phi_scale * std::pow(sigma_rbf, 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
+  hipError_t e = launch_feature(X_dev, N, (int)D, ls_dev, c, Z_dev, b_dev, (int)n, phi_dev,
+                                (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_fail(e, "feature kernel");
+  return GPT_OK;
+}
+
+extern "C" int gpt_feature(const double* X, int64_t N, int64_t D, const double* length_scale,
+                           int64_t ls_len, double sigma_rbf, double phi_scale, const double* Z,
+                           const double* b, int64_t n, double* phi_out) {
+  return feature_common(true, X, N, D, length_scale, ls_len, sigma_rbf, phi_scale, Z, b, n, phi_out);
+}
+
+extern "C" int gpt_feature_notensor(const double* X, int64_t N, int64_t D, const double* length_scale,
+                                    int64_t ls_len, double sigma_rbf, const double* Z,
+                                    const double* b, int64_t n, double* phi_out) {
+  return feature_common(false, X, N, D, length_scale, ls_len, sigma_rbf, 1.0, Z, b, n, phi_out);
+}
+
+bool gpt::valid_pred(int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q) {
+  if (n < 1 || D < 1 || Ntest < 0 || r < 1 || Q < 1) { set_error("bad pred dims"); return false; }
+  if (D > kDMax) { set_error("D > 16 unsupported"); return false; }
+  if (!rank_supported((int)r)) { set_error("rank not instantiated"); return false; }
+  if (pred_lds_bytes((int)n, (int)D, (int)r, (int)Q) > 160 * 1024) { set_error("pred LDS too large"); return false; }
+  return true;
+}
+
+extern "C" int gpt_pred_dev(const double* w_dev, const double* U_dev, const int32_t* I0_dev,
+                            const double* phitest_dev, int64_t n, int64_t D, int64_t Ntest,
+                            int64_t r, int64_t Q, int64_t S, double* fhat_dev, void* hip_stream) {
+  if (!valid_pred(n, D, Ntest, r, Q)) return GPT_ERR_BAD_DIMS;
+  hipError_t e = launch_pred(w_dev, U_dev, I0_dev, phitest_dev, (int)n, (int)D, Ntest, (int)r,
+                             (int)Q, (int)S, fhat_dev, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_fail(e, "pred kernel");
+  return GPT_OK;
+}
+
+extern "C" int gpt_pred_trim_pool(void) {
+  GPT_HIPCHK(pred_trim_pools());
+  return GPT_OK;
+}
+
+extern "C" int gpt_pred_dev_timed(const double* w_dev, const double* U_dev, const int32_t* I0_dev,
+                                  const double* phitest_dev, int64_t n, int64_t D, int64_t Ntest,
+                                  int64_t r, int64_t Q, int64_t S, double* fhat_dev,
+                                  void* hip_stream, double* ms_out) {
+  if (!valid_pred(n, D, Ntest, r, Q)) return GPT_ERR_BAD_DIMS;
+  if (!ms_out) { set_error("gpt_pred_dev_timed: ms_out is null"); return GPT_ERR_BAD_DIMS; }
+  PredPhaseTiming tm;
+  hipError_t e = launch_pred(w_dev, U_dev, I0_dev, phitest_dev, (int)n, (int)D, Ntest, (int)r,
+                             (int)Q, (int)S, fhat_dev, (hipStream_t)hip_stream, &tm);
+  if (e != hipSuccess) return hip_fail(e, "pred kernel");
+  GPT_HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
+  ms_out[0] = tm.gemm_ms;
+  ms_out[1] = tm.vphase_ms;
+  return GPT_OK;
+}
+
+static int pred_host(const double* w, const double* U, const int32_t* I, const double* phitest,
+                     const double* ytest, int64_t n, int64_t D, int64_t Ntest, int64_t r,
+                     int64_t Q, int64_t S, double scale, double* fhat_out, double* mean_out,
+                     double* rmse_out) {
+  if (!valid_pred(n, D, Ntest, r, Q) || S < 1) return GPT_ERR_BAD_DIMS;
+  std::vector<int32_t> I0;
+  if (!zero_based_I(I, Q, D, r, I0)) return GPT_ERR_BAD_DIMS;
+  DevMem dw, dU, dI, dphi, df, dy, dmean, dsse;
+  GPT_HIPCHK(dw.upload(w, (size_t)Q * S));
+  GPT_HIPCHK(dU.upload(U, (size_t)n * r * D * S));
+  GPT_HIPCHK(dI.upload(I0.data(), I0.size()));
+  GPT_HIPCHK(dphi.upload(phitest, (size_t)n * D * Ntest));
+  GPT_HIPCHK(df.alloc<double>((size_t)Ntest * S));
+  int rc = gpt_pred_dev(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(), n,
+                        D, Ntest, r, Q, S, df.as<double>(), nullptr);
+  if (rc != GPT_OK) return rc;
+  if (fhat_out) GPT_HIPCHK(df.download(fhat_out, (size_t)Ntest * S));
+  if (ytest) {
+    GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
+    GPT_HIPCHK(dmean.alloc<double>((size_t)Ntest));
+    GPT_HIPCHK(dsse.alloc<double>((size_t)(S + 1)));
+    hipError_t e = launch_mean_rmse(df.as<double>(), dy.as<double>(), Ntest, (int)S,
+                                    dmean.as<double>(), dsse.as<double>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
+    double sse = 0.0;
+    GPT_HIPCHK(dsse.download(&sse, 1));
+    if (mean_out) GPT_HIPCHK(dmean.download(mean_out, (size_t)Ntest));
+    if (rmse_out) *rmse_out = scale * std::sqrt(sse / (double)Ntest);
+  }
+  GPT_HIPCHK(hipDeviceSynchronize());
+  return GPT_OK;
+}
+
+extern "C" int gpt_pred(const double* w, const double* U, const int32_t* I, const double* phitest,
+                        int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q, double* fhat_out) {
+  return pred_host(w, U, I, phitest, nullptr, n, D, Ntest, r, Q, 1, 1.0, fhat_out, nullptr, nullptr);
+}
+
+extern "C" int gpt_pred_mean(const double* w_store, const double* U_store, const int32_t* I,
+                             const double* phitest, const double* ytest, int64_t n, int64_t D,
+                             int64_t Ntest, int64_t r, int64_t Q, int64_t S, double scale,
+                             double* mean_out, double* rmse_out) {
+  if (!ytest) { set_error("ytest required"); return GPT_ERR_BAD_DIMS; }
+  return pred_host(w_store, U_store, I, phitest, ytest, n, D, Ntest, r, Q, S, scale, nullptr,
+                   mean_out, rmse_out);
+}
+
+extern "C" int gpt_pred_mean_x(const double* w_store, const double* U_store, const int32_t* I,
+                               const double* Xtest, const double* ytest, int64_t Ntest, int64_t D,
+                               const double* length_scale, int64_t ls_len, double sigma_rbf,
+                               double phi_scale, const double* Z, const double* b, int64_t n,
+                               int64_t r, int64_t Q, int64_t S, double scale, double* mean_out,
+                               double* rmse_out, double* sample_rmse_out) {
+  if (!w_store || !U_store || !I || !Xtest || !ytest || !length_scale || !Z || !b || S < 1) {
+    set_error("bad pred_mean_x arguments"); return GPT_ERR_BAD_DIMS;
+  }
+  if (ls_len != 1 && ls_len != D) {
+    set_error("dimensions of X and length_scale do not match"); return GPT_ERR_BAD_DIMS;
+  }
+  if (!valid_pred(n, D, Ntest, r, Q)) return GPT_ERR_BAD_DIMS;
+  if (pred_x_lds_bytes((int)n, (int)D, (int)r, (int)Q) > 160 * 1024) {
+    set_error("pred LDS too large"); return GPT_ERR_BAD_DIMS;
+  }
+  std::vector<int32_t> I0;
+  if (!zero_based_I(I, Q, D, r, I0)) return GPT_ERR_BAD_DIMS;
+  std::vector<double> lsv(D);
+  for (int64_t k = 0; k < D; ++k) lsv[k] = length_scale[ls_len == 1 ? 0 : k];
+  const double c = phi_scale * std::pow(sigma_rbf, 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
+  DevMem dw, dU, dI, dX, dls, dZ, db, df, dy, dmean, dsse;
+  GPT_HIPCHK(dw.upload(w_store, (size_t)Q * S));
+  GPT_HIPCHK(dU.upload(U_store, (size_t)n * r * D * S));
+  GPT_HIPCHK(dI.upload(I0.data(), I0.size()));
+  GPT_HIPCHK(dX.upload(Xtest, (size_t)Ntest * D));
+  GPT_HIPCHK(dls.upload(lsv.data(), lsv.size()));
+  GPT_HIPCHK(dZ.upload(Z, (size_t)n * D));
+  GPT_HIPCHK(db.upload(b, (size_t)n * D));
+  GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
+  GPT_HIPCHK(df.alloc<double>((size_t)Ntest * S));
+  GPT_HIPCHK(dmean.alloc<double>((size_t)Ntest));
+  GPT_HIPCHK(dsse.alloc<double>((size_t)(S + 1)));
+  // Default: the test features are formed once on the device (feature_kernel, the same doubles
+  // as gpt_feature) and every sample is predicted by the stacked-sample MFMA path, which reads
+  // them through L2 per group of samples.  GPTSGLD_PRED=direct: pred_x_kernel, which forms the
+  // features inside every sample's prediction tile (no phitest array).
+  const char* pev = std::getenv("GPTSGLD_PRED");
+  hipError_t e;
+  DevMem dphi;
+  if (pev && std::strcmp(pev, "direct") == 0) {
+    e = launch_pred_x(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dX.as<double>(),
+                      dls.as<double>(), dZ.as<double>(), db.as<double>(), c, (int)n, (int)D,
+                      Ntest, (int)r, (int)Q, (int)S, df.as<double>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "pred_x kernel");
+  } else {
+    GPT_HIPCHK(dphi.alloc<double>((size_t)n * D * Ntest));
+    e = launch_feature(dX.as<double>(), Ntest, (int)D, dls.as<double>(), c, dZ.as<double>(),
+                       db.as<double>(), (int)n, dphi.as<double>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "feature kernel");
+    e = launch_pred(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(), (int)n,
+                    (int)D, Ntest, (int)r, (int)Q, (int)S, df.as<double>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "pred kernels");
+  }
+  e = launch_mean_rmse(df.as<double>(), dy.as<double>(), Ntest, (int)S, dmean.as<double>(),
+                       dsse.as<double>(), nullptr);
+  if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
+  std::vector<double> sse((size_t)S + 1);
+  GPT_HIPCHK(dsse.download(sse.data(), sse.size()));
+  if (mean_out) GPT_HIPCHK(dmean.download(mean_out, (size_t)Ntest));
+  if (rmse_out) *rmse_out = scale * std::sqrt(sse[0] / (double)Ntest);
+  if (sample_rmse_out)
+    for (int64_t z = 0; z < S; ++z) sample_rmse_out[z] = scale * std::sqrt(sse[1 + z] / (double)Ntest);
+  return GPT_OK;
+}
+
+extern "C" int gpt_pred_last_vphase(int32_t* kind) {
+  if (!kind) { set_error("gpt_pred_last_vphase: null output"); return GPT_ERR_BAD_DIMS; }
+  *kind = pred_last_vphase();
+  return GPT_OK;
+}
+
+extern "C" int gpt_pred_last_route(int32_t* out, int32_t len) {
+  if (!out || len < 0) { set_error("gpt_pred_last_route: bad output"); return GPT_ERR_BAD_DIMS; }
+  pred_last_route(out, (int)len);
+  for (int32_t x = kPredRouteLen; x < len; ++x) out[x] = 0;
+  return GPT_OK;
+}

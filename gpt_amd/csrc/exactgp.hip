@@ -20,10 +20,10 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <type_traits>
 #include <vector>
 
 #include "device_util.h"
+#include "host_util.h"
 
 namespace gpt {
 
@@ -554,20 +554,11 @@ struct gpt_egp {
   bool have_factor = false;            // A holds L and alpha the weights of hyper `last`
   double last[kDMax + 2];
   int64_t last_Lh = 0;
-  std::vector<void*> mem;
+  DevSet mem;
+  DevMem ks_mem;                       // Ks: regrown when a call asks for more columns
   std::vector<hipEvent_t> ev;
-  ~gpt_egp() {
-    for (void* p : mem) (void)hipFree(p);
-    if (Ks) (void)hipFree(Ks);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
+  ~gpt_egp() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
 };
-
-#define EGCHK(call)                                    \
-  do {                                                 \
-    hipError_t _e = (call);                            \
-    if (_e != hipSuccess) return hip_fail(_e, #call);  \
-  } while (0)
 
 static bool egp_dims_ok(const void* X, int64_t N, int64_t D, const void* y) {
   if (!X || !y) { set_error("exact GP: null input array"); return false; }
@@ -598,14 +589,6 @@ static bool egp_test_ok(const void* Xtest, int64_t Ntest, const void* ytest, int
   return true;
 }
 
-template <class T>
-static hipError_t egp_alloc(gpt_egp* h, T** p, size_t bytes) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-  if (e == hipSuccess) { h->mem.push_back(q); *p = (T*)q; }
-  return e;
-}
-
 extern "C" int gpt_egp_create(const double* X, int64_t N, int64_t D, const double* y,
                               gpt_egp** out) {
   if (!out) { set_error("exact GP: null handle pointer"); return GPT_ERR_BAD_DIMS; }
@@ -614,18 +597,17 @@ extern "C" int gpt_egp_create(const double* X, int64_t N, int64_t D, const doubl
   std::unique_ptr<gpt_egp> h(new gpt_egp);
   h->N = (int)N; h->D = (int)D;
   const size_t nblk = (size_t)((N + 63) / 64);
-  EGCHK(egp_alloc(h.get(), &h->X, 8 * (size_t)N * D));
-  EGCHK(egp_alloc(h.get(), &h->y, 8 * (size_t)N));
-  EGCHK(egp_alloc(h.get(), &h->A, 8 * (size_t)N * N));
-  EGCHK(egp_alloc(h.get(), &h->r, 8 * (size_t)N));
-  EGCHK(egp_alloc(h.get(), &h->z, 8 * (size_t)N));
-  EGCHK(egp_alloc(h.get(), &h->alpha, 8 * (size_t)N));
-  EGCHK(egp_alloc(h.get(), &h->part, 8 * nblk * (nblk + 1) / 2 * kEgpPart));
-  EGCHK(egp_alloc(h.get(), &h->sums, 8 * (size_t)kEgpPart));
-  EGCHK(egp_alloc(h.get(), &h->scal, 8 * 2));
-  EGCHK(egp_alloc(h.get(), &h->status, 16));
-  EGCHK(hipMemcpy(h->X, X, 8 * (size_t)N * D, hipMemcpyHostToDevice));
-  EGCHK(hipMemcpy(h->y, y, 8 * (size_t)N, hipMemcpyHostToDevice));
+  DevSet& M = h->mem;
+  GPT_HIPCHK(M.upload(&h->X, X, (size_t)N * D));
+  GPT_HIPCHK(M.upload(&h->y, y, (size_t)N));
+  GPT_HIPCHK(M.alloc(&h->A, (size_t)N * N));
+  GPT_HIPCHK(M.alloc(&h->r, (size_t)N));
+  GPT_HIPCHK(M.alloc(&h->z, (size_t)N));
+  GPT_HIPCHK(M.alloc(&h->alpha, (size_t)N));
+  GPT_HIPCHK(M.alloc(&h->part, nblk * (nblk + 1) / 2 * kEgpPart));
+  GPT_HIPCHK(M.alloc(&h->sums, (size_t)kEgpPart));
+  GPT_HIPCHK(M.alloc(&h->scal, 2));
+  GPT_HIPCHK(M.alloc(&h->status, 4));
   *out = h.release();
   return GPT_OK;
 }
@@ -678,12 +660,12 @@ static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t wa
   hipStream_t st = nullptr;
   h->have_factor = false;
   if (want_grad && !h->W) {
-    EGCHK(egp_alloc(h, &h->W, 8 * (size_t)N * N));
-    EGCHK(egp_alloc(h, &h->P, 8 * (size_t)N * N));
+    GPT_HIPCHK(h->mem.alloc(&h->W, (size_t)N * N));
+    GPT_HIPCHK(h->mem.alloc(&h->P, (size_t)N * N));
   }
   if (phase_ms && h->ev.empty()) {
     h->ev.resize(kEgpPhases + 1);
-    for (auto& e : h->ev) EGCHK(hipEventCreate(&e));
+    for (auto& e : h->ev) GPT_HIPCHK(hipEventCreate(&e));
   }
   int marks = 0;
   auto mark = [&]() {
@@ -692,10 +674,10 @@ static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t wa
   };
   const int nblk = (N + 63) / 64;
   const long long npair = (long long)nblk * (nblk + 1) / 2;
-  EGCHK(hipMemsetAsync(h->status, 0, 16, st));
+  GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
   mark();
   hipLaunchKernelGGL(egp_build_kernel, dim3(nblk, nblk), dim3(256), 0, st, h->X, N, H, h->A);
-  EGCHK(hipGetLastError());
+  GPT_HIPCHK(hipGetLastError());
   mark();
   for (int j0 = 0; j0 < N; j0 += kEgpNB) {
     hipLaunchKernelGGL(egp_potf2_kernel, dim3(1), dim3(256), 0, st, h->A, N, j0, h->status);
@@ -707,29 +689,29 @@ static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t wa
                          h->A, N, j0);
     }
   }
-  EGCHK(hipGetLastError());
+  GPT_HIPCHK(hipGetLastError());
   mark();
-  EGCHK(hipMemcpyAsync(h->r, h->y, 8 * (size_t)N, hipMemcpyDeviceToDevice, st));
+  GPT_HIPCHK(hipMemcpyAsync(h->r, h->y, 8 * (size_t)N, hipMemcpyDeviceToDevice, st));
   for (int j0 = 0; j0 < N; j0 += kEgpNB) {
     const int rem = std::max(N - j0 - kEgpNB, 1);
     hipLaunchKernelGGL(egp_trsv_kernel<0>, dim3((rem + 255) / 256), dim3(256), 0, st, h->A, N, j0,
                        h->r, h->z);
   }
-  EGCHK(hipMemcpyAsync(h->r, h->z, 8 * (size_t)N, hipMemcpyDeviceToDevice, st));
+  GPT_HIPCHK(hipMemcpyAsync(h->r, h->z, 8 * (size_t)N, hipMemcpyDeviceToDevice, st));
   for (int j0 = (N - 1) / kEgpNB * kEgpNB; j0 >= 0; j0 -= kEgpNB)
     hipLaunchKernelGGL(egp_trsv_kernel<1>, dim3((std::max(j0, 1) + 255) / 256), dim3(256), 0, st,
                        h->A, N, j0, h->r, h->alpha);
   hipLaunchKernelGGL(egp_scalars_kernel, dim3(1), dim3(kNT), 0, st, h->A, h->z, N, h->scal);
-  EGCHK(hipGetLastError());
+  GPT_HIPCHK(hipGetLastError());
   mark();
   if (want_grad) {
-    EGCHK(hipMemsetAsync(h->W, 0, 8 * (size_t)N * N, st));
-    EGCHK(egp_trsm(h->A, N, h->W, N, true, st));
+    GPT_HIPCHK(hipMemsetAsync(h->W, 0, 8 * (size_t)N * N, st));
+    GPT_HIPCHK(egp_trsm(h->A, N, h->W, N, true, st));
     mark();
     const long long T = (N + 31) / 32;
     hipLaunchKernelGGL(egp_ptp_kernel, dim3((unsigned)((T * (T + 1) / 2 + 3) / 4)), dim3(256), 0,
                        st, h->W, N, h->P);
-    EGCHK(hipGetLastError());
+    GPT_HIPCHK(hipGetLastError());
     mark();
 #define EGP_GRAD(DP)                                                                            \
   hipLaunchKernelGGL((egp_grad_kernel<DP>), dim3((unsigned)npair), dim3(kNT), 0, st, h->P, \
@@ -741,7 +723,7 @@ static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t wa
     else EGP_GRAD(16);
 #undef EGP_GRAD
     hipLaunchKernelGGL(egp_finish_kernel, dim3(1), dim3(kNT), 0, st, h->part, npair, D, h->sums);
-    EGCHK(hipGetLastError());
+    GPT_HIPCHK(hipGetLastError());
     mark();
   } else {
     for (int q = 0; q < 3; ++q) mark();
@@ -749,15 +731,15 @@ static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t wa
   double sc[2], sums[kEgpPart];
   int32_t bad = 0;
   std::vector<double> ah(alpha_out ? N : 0);
-  EGCHK(hipMemcpyAsync(sc, h->scal, 8 * 2, hipMemcpyDeviceToHost, st));
-  EGCHK(hipMemcpyAsync(&bad, h->status, 4, hipMemcpyDeviceToHost, st));
-  if (alpha_out) EGCHK(hipMemcpyAsync(ah.data(), h->alpha, 8 * (size_t)N, hipMemcpyDeviceToHost, st));
-  if (want_grad) EGCHK(hipMemcpyAsync(sums, h->sums, 8 * kEgpPart, hipMemcpyDeviceToHost, st));
-  EGCHK(hipStreamSynchronize(st));
+  GPT_HIPCHK(hipMemcpyAsync(sc, h->scal, 8 * 2, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipMemcpyAsync(&bad, h->status, 4, hipMemcpyDeviceToHost, st));
+  if (alpha_out) GPT_HIPCHK(hipMemcpyAsync(ah.data(), h->alpha, 8 * (size_t)N, hipMemcpyDeviceToHost, st));
+  if (want_grad) GPT_HIPCHK(hipMemcpyAsync(sums, h->sums, 8 * kEgpPart, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipStreamSynchronize(st));
   if (phase_ms)
     for (int q = 0; q < kEgpPhases; ++q) {
       float ms = 0.f;
-      EGCHK(hipEventElapsedTime(&ms, h->ev[q], h->ev[q + 1]));
+      GPT_HIPCHK(hipEventElapsedTime(&ms, h->ev[q], h->ev[q + 1]));
       phase_ms[q] = ms;
     }
   if (bad) {
@@ -825,32 +807,24 @@ extern "C" int gpt_egp_predict(gpt_egp* h, const double* hyper, int64_t Lh, cons
   const int64_t want = chunk == 0 ? kEgpChunk : std::min<int64_t>(chunk, kEgpChunkMax);
   const int cw = (int)std::min<int64_t>(want, Ntest);
   if (h->ks_cols < (size_t)cw) {
-    if (h->Ks) EGCHK(hipFree(h->Ks));
     h->Ks = nullptr;
     h->ks_cols = 0;
-    EGCHK(hipMalloc((void**)&h->Ks, 8 * (size_t)N * cw));
+    h->ks_mem = DevMem();                // the old block is freed before the larger one is taken
+    GPT_HIPCHK(h->ks_mem.alloc<double>((size_t)N * cw));
+    h->Ks = h->ks_mem.as<double>();
     h->ks_cols = (size_t)cw;
   }
   // test inputs, targets and the three outputs on the device for the call
-  struct Tmp {
-    std::vector<void*> p;
-    ~Tmp() { for (void* q : p) (void)hipFree(q); }
-  } tmp;
-  auto dev = [&](double** p, size_t n) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, 8 * n);
-    if (e == hipSuccess) { tmp.p.push_back(q); *p = (double*)q; }
-    return e;
-  };
+  DevSet tmp;
   double *dX = nullptr, *dy = nullptr, *dmu = nullptr, *dv = nullptr, *dlp = nullptr;
-  EGCHK(dev(&dX, (size_t)Ntest * D));
-  EGCHK(dev(&dmu, (size_t)Ntest));
-  EGCHK(dev(&dv, (size_t)Ntest));
-  EGCHK(hipMemcpyAsync(dX, Xtest, 8 * (size_t)Ntest * D, hipMemcpyHostToDevice, st));
+  GPT_HIPCHK(tmp.alloc(&dX, (size_t)Ntest * D));
+  GPT_HIPCHK(tmp.alloc(&dmu, (size_t)Ntest));
+  GPT_HIPCHK(tmp.alloc(&dv, (size_t)Ntest));
+  GPT_HIPCHK(hipMemcpyAsync(dX, Xtest, 8 * (size_t)Ntest * D, hipMemcpyHostToDevice, st));
   if (lp) {
-    EGCHK(dev(&dy, (size_t)Ntest));
-    EGCHK(dev(&dlp, (size_t)Ntest));
-    EGCHK(hipMemcpyAsync(dy, ytest, 8 * (size_t)Ntest, hipMemcpyHostToDevice, st));
+    GPT_HIPCHK(tmp.alloc(&dy, (size_t)Ntest));
+    GPT_HIPCHK(tmp.alloc(&dlp, (size_t)Ntest));
+    GPT_HIPCHK(hipMemcpyAsync(dy, ytest, 8 * (size_t)Ntest, hipMemcpyHostToDevice, st));
   }
   for (int64_t c0 = 0; c0 < Ntest; c0 += cw) {
     const int nc = (int)std::min<int64_t>(cw, Ntest - c0);
@@ -859,16 +833,16 @@ extern "C" int gpt_egp_predict(gpt_egp* h, const double* hyper, int64_t Lh, cons
     hipLaunchKernelGGL(egp_pred_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->Ks, N, nc,
                        h->alpha, 0, H.sig2, H.s2, (const double*)nullptr, dmu + c0, dv + c0,
                        (double*)nullptr);
-    EGCHK(egp_trsm(h->A, N, h->Ks, nc, false, st));
+    GPT_HIPCHK(egp_trsm(h->A, N, h->Ks, nc, false, st));
     hipLaunchKernelGGL(egp_pred_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->Ks, N, nc,
                        h->alpha, 1, H.sig2, H.s2, lp ? dy + c0 : (const double*)nullptr, dmu + c0,
                        dv + c0, lp ? dlp + c0 : (double*)nullptr);
-    EGCHK(hipGetLastError());
+    GPT_HIPCHK(hipGetLastError());
   }
-  EGCHK(hipMemcpyAsync(fmu, dmu, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
-  EGCHK(hipMemcpyAsync(fs2, dv, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
-  if (lp) EGCHK(hipMemcpyAsync(lp, dlp, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
-  EGCHK(hipStreamSynchronize(st));
+  GPT_HIPCHK(hipMemcpyAsync(fmu, dmu, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipMemcpyAsync(fs2, dv, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
+  if (lp) GPT_HIPCHK(hipMemcpyAsync(lp, dlp, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipStreamSynchronize(st));
   return GPT_OK;
 }
 

@@ -3,7 +3,7 @@
 // engines call them — the coefficient table through fm_coef(), the two 16-entry sin/cos tables
 // filled in LDS by sincos_tab_fill — and compiled with the flags of the engines.  Nothing is
 // restated here; tests/test_gpu_fastmath.py holds the results to mpmath.
-#include "gpt_internal.h"
+#include "host_util.h"
 
 namespace gpt {
 
@@ -85,22 +85,6 @@ __global__ __launch_bounds__(kFmNT) void normals_check_kernel(uint64_t seed, uin
 
 namespace {
 
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <class T> T* as() const { return (T*)p; }
-};
-
-#define FMCHK(call)                                    \
-  do {                                                 \
-    hipError_t _e = (call);                            \
-    if (_e != hipSuccess) return hip_fail(_e, #call);  \
-  } while (0)
-
 template <int FN>
 void fm_launch(long long count, const double* x, const uint32_t* xi, double* o0, double* o1) {
   hipLaunchKernelGGL(fm_check_kernel<FN>, dim3((unsigned)((count + kFmNT - 1) / kFmNT)),
@@ -128,12 +112,12 @@ extern "C" int gpt_debug_fastmath(int32_t fn, int64_t count, const double* x, co
   const bool ok = count >= 1 && count <= kFmMaxCount && out0 && (!two || out1) &&
                   (fn == kFmTable ? count == 64 : (words ? xi != nullptr : x != nullptr));
   if (!ok) { set_error("gpt_debug_fastmath: bad arguments"); return GPT_ERR_BAD_DIMS; }
-  const size_t nin = fn == kFmTable ? 0 : (size_t)count * (words ? (fn == kFmU53 ? 8 : 4) : 8);
-  DevBuf din, d0, d1;
-  FMCHK(din.alloc(nin));
-  FMCHK(d0.alloc(8 * (size_t)count));
-  FMCHK(d1.alloc(8 * (size_t)count));
-  if (nin) FMCHK(hipMemcpy(din.p, words ? (const void*)xi : (const void*)x, nin, hipMemcpyHostToDevice));
+  DevMem din, d0, d1;
+  if (fn == kFmTable) GPT_HIPCHK(din.alloc<double>(0));
+  else if (words) GPT_HIPCHK(din.upload(xi, (size_t)count * (fn == kFmU53 ? 2 : 1)));
+  else GPT_HIPCHK(din.upload(x, (size_t)count));
+  GPT_HIPCHK(d0.alloc<double>(count));
+  GPT_HIPCHK(d1.alloc<double>(count));
   const double* dx = din.as<double>();
   const uint32_t* dxi = din.as<uint32_t>();
   double *o0 = d0.as<double>(), *o1 = d1.as<double>();
@@ -148,10 +132,10 @@ extern "C" int gpt_debug_fastmath(int32_t fn, int64_t count, const double* x, co
     case kFmU32: fm_launch<kFmU32>(count, dx, dxi, o0, o1); break;
     default: fm_launch<kFmRadius>(count, dx, dxi, o0, o1); break;
   }
-  FMCHK(hipGetLastError());
-  FMCHK(hipDeviceSynchronize());
-  FMCHK(hipMemcpy(out0, d0.p, 8 * (size_t)count, hipMemcpyDeviceToHost));
-  if (two) FMCHK(hipMemcpy(out1, d1.p, 8 * (size_t)count, hipMemcpyDeviceToHost));
+  GPT_HIPCHK(hipGetLastError());
+  GPT_HIPCHK(hipDeviceSynchronize());
+  GPT_HIPCHK(d0.download(out0, count));
+  if (two) GPT_HIPCHK(d1.download(out1, count));
   return GPT_OK;
 }
 
@@ -178,9 +162,9 @@ extern "C" int gpt_debug_normals(int32_t gen, uint64_t seed, uint32_t c0_first, 
     return GPT_OK;
   }
   const size_t per = (gen == kGenQuad4 || gen == kGenQuadTab4) ? 4 : 2;
-  DevBuf dz, dw;
-  FMCHK(dz.alloc(8 * per * (size_t)nblocks));
-  FMCHK(dw.alloc(16 * (size_t)nblocks));
+  DevMem dz, dw;
+  GPT_HIPCHK(dz.alloc<double>(per * (size_t)nblocks));
+  GPT_HIPCHK(dw.alloc<uint32_t>(4 * (size_t)nblocks));
   double* pz = dz.as<double>();
   uint32_t* pw = dw.as<uint32_t>();
   switch (gen) {
@@ -191,9 +175,9 @@ extern "C" int gpt_debug_normals(int32_t gen, uint64_t seed, uint32_t c0_first, 
     case kGenQuadTab4: normals_launch<kGenQuadTab4>(seed, c0_first, nblocks, c1, c2, c3, pz, pw); break;
     default: normals_launch<kGenQuadTab2>(seed, c0_first, nblocks, c1, c2, c3, pz, pw); break;
   }
-  FMCHK(hipGetLastError());
-  FMCHK(hipDeviceSynchronize());
-  FMCHK(hipMemcpy(z, dz.p, 8 * per * (size_t)nblocks, hipMemcpyDeviceToHost));
-  FMCHK(hipMemcpy(words, dw.p, 16 * (size_t)nblocks, hipMemcpyDeviceToHost));
+  GPT_HIPCHK(hipGetLastError());
+  GPT_HIPCHK(hipDeviceSynchronize());
+  GPT_HIPCHK(dz.download(z, per * (size_t)nblocks));
+  GPT_HIPCHK(dw.download(words, 4 * (size_t)nblocks));
   return GPT_OK;
 }

@@ -73,7 +73,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) double* fm_co
 }
 
 // Element e of normal stream (c1, c2, c3): Box–Muller on the block at c0 = e>>1.
-// (log / sincos(2πu) from fastmath.h; host-side draws use libm in capi.hip.)
+// (log / sincos(2πu) from fastmath.h; host-side draws use libm in api_core.hip.)
 __device__ __forceinline__ double normal_at(uint64_t seed, uint32_t e, uint32_t c1, uint32_t c2,
                                             uint32_t c3) {
   const U4 x = philox4x32(e >> 1, c1, c2, c3, seed);

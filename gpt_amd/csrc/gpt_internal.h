@@ -157,9 +157,25 @@ inline hipError_t set_max_lds_once(const void* fn, int bytes, std::atomic<uint64
   return e;
 }
 
-// Host helpers (capi.hip / sgld.hip)
+// Host helpers (api_core.hip / api_session.hip / api_pred.hip; sgld.hip, pred.hip)
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
+hipError_t set_lds_limits();
+size_t pred_lds_bytes(int n, int D, int r, int Q);
+bool valid_cfg(const gpt_sgld_config* c);
+bool valid_pred(int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q);
+bool valid_x_args(const gpt_sgld_config* cfg, int32_t nchains, const uint64_t* seeds,
+                  const double* X, const double* const* y, const double* ls, int64_t ls_len,
+                  const double* sigma_rbf, const double* Z, const double* b, const int32_t* I,
+                  int32_t store_flags);
+double host_normal(uint64_t seed, uint32_t e, uint32_t c1, uint32_t c2, uint32_t c3);
+void host_stiefel_polar(const double* Z, int r, int n, double* Uk);   // Uk = Zᵀ(ZZᵀ)^(-1/2)
+// The session's internals that the host-pointer samplers and classification use next to its C
+// entries: chain c's initial state, the per-chain gw | gU | res buffers, and what they read of it.
+int session_set_state(gpt_sgld_session* s, int c, const double* w, const double* U);
+int session_alloc_aux(gpt_sgld_session* s);
+struct SessionRun { long long total_steps, nstore; const double* U0; };   // U0: chain 0's U (device)
+SessionRun session_run_info(const gpt_sgld_session* s);
 
 // Launch wrappers implemented in sgld.hip / pred.hip / feature.hip
 hipError_t launch_temp_init(const StepParams& P, const ChainDesc* chains, int nchains,

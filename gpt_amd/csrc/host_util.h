@@ -1,0 +1,104 @@
+// Host-only helpers of the libgptsgld translation units: the HIP error check, the owners of device
+// allocations and the argument idioms the C entries share.  No device code.
+#pragma once
+#include <unordered_map>
+#include <utility>
+#include <vector>
+#include "gpt_internal.h"
+
+namespace gpt {
+
+#define GPT_HIPCHK(call)                               \
+  do {                                                 \
+    hipError_t _e = (call);                            \
+    if (_e != hipSuccess) return hip_fail(_e, #call);  \
+  } while (0)
+
+// Owner of one device allocation.  Sizes are element counts of T: the byte count of a buffer is
+// formed once, in alloc, and zero / download work from it.
+struct DevMem {
+  void* p = nullptr;
+  size_t bytes = 0;
+  DevMem() = default;
+  DevMem(DevMem&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  DevMem& operator=(DevMem&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    return *this;
+  }
+  ~DevMem() { if (p) (void)hipFree(p); }
+  template <class T> hipError_t alloc(size_t count) {
+    bytes = sizeof(T) * count;
+    return hipMalloc(&p, bytes ? bytes : 16);
+  }
+  template <class T> hipError_t upload(const T* host, size_t count) {   // allocate and copy in
+    const hipError_t e = alloc<T>(count);
+    return e != hipSuccess ? e : hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+  }
+  hipError_t zero() { return hipMemset(p, 0, bytes); }
+  template <class T> hipError_t download(T* host, size_t count) const {
+    if (sizeof(T) * count > bytes) return hipErrorInvalidValue;
+    return hipMemcpy(host, p, sizeof(T) * count, hipMemcpyDeviceToHost);
+  }
+  template <class T> T* as() const { return (T*)p; }
+};
+
+// Owner of the many allocations of a handle object (freed together with it).
+struct DevSet {
+  std::vector<DevMem> mem;
+  template <class T> hipError_t alloc(T** out, size_t count) {
+    DevMem m;
+    const hipError_t e = m.alloc<T>(count);
+    if (e == hipSuccess) {
+      *out = m.as<T>();
+      mem.push_back(std::move(m));
+    }
+    return e;
+  }
+  template <class T> hipError_t upload(T** out, const T* host, size_t count) {
+    const hipError_t e = alloc(out, count);
+    return e != hipSuccess ? e : hipMemcpy(*out, host, sizeof(T) * count, hipMemcpyHostToDevice);
+  }
+};
+
+// One device copy per distinct host array (the host pointers of sibling chains may repeat).
+struct UploadCache {
+  DevSet mem;
+  std::unordered_map<const double*, const double*> dev_of;
+};
+inline hipError_t upload_once(UploadCache& uc, const double* h, size_t count, const double** out) {
+  const auto it = uc.dev_of.find(h);
+  if (it != uc.dev_of.end()) { *out = it->second; return hipSuccess; }
+  double* d = nullptr;
+  const hipError_t e = uc.mem.upload(&d, h, count);
+  if (e == hipSuccess) *out = uc.dev_of[h] = d;
+  return e;
+}
+
+// The 0-based table of the 1-based core index array I (Q × D); false with the error set when an
+// entry is outside 1..r.
+inline bool zero_based_I(const int32_t* I, int64_t Q, int64_t D, int64_t r,
+                         std::vector<int32_t>& out) {
+  out.resize((size_t)(Q * D));
+  for (size_t x = 0; x < out.size(); ++x) {
+    if (I[x] < 1 || I[x] > r) { set_error("I entries must be in 1..r"); return false; }
+    out[x] = I[x] - 1;
+  }
+  return true;
+}
+
+// Events destroyed on every exit path.
+struct ScopedEvents {
+  std::vector<hipEvent_t> e;
+  ~ScopedEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+  hipError_t create(size_t count) {
+    e.assign(count, nullptr);
+    for (auto& x : e) {
+      const hipError_t r = hipEventCreate(&x);
+      if (r != hipSuccess) return r;
+    }
+    return hipSuccess;
+  }
+};
+
+}  // namespace gpt

@@ -15,10 +15,10 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <type_traits>
 #include <vector>
 
 #include "device_util.h"
+#include "host_util.h"
 
 namespace gpt {
 
@@ -339,19 +339,10 @@ struct gpt_nlml {
          *e = nullptr, *part = nullptr, *gl = nullptr, *scal = nullptr;
   int32_t* status = nullptr;
   bool have_features = false, have_sin = false;
-  std::vector<void*> mem;
+  DevSet mem;
   std::vector<hipEvent_t> ev;         // gpt_nlml_eval_timed's phase marks
-  ~gpt_nlml() {
-    for (void* p : mem) (void)hipFree(p);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
+  ~gpt_nlml() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
 };
-
-#define NLCHK(call)                                    \
-  do {                                                 \
-    hipError_t _e = (call);                            \
-    if (_e != hipSuccess) return hip_fail(_e, #call);  \
-  } while (0)
 
 static bool nlml_dims_ok(const void* X, int64_t N, int64_t D, const void* y, const void* Z,
                          const void* b, int64_t n) {
@@ -391,25 +382,25 @@ extern "C" int gpt_nlml_create(const double* X, int64_t N, int64_t D, const doub
   h->n = (int)n; h->D = (int)D; h->N = N;
   h->CB = nlml_col_block((int)n, N);
   h->ncb = (int)((N + h->CB - 1) / h->CB);
-  hipError_t err = hipSuccess;
-  auto al = [&](auto** p, size_t bytes) {
-    if (err != hipSuccess) return;
-    void* q = nullptr;
-    err = hipMalloc(&q, bytes ? bytes : 16);
-    if (err == hipSuccess) { h->mem.push_back(q); *p = (std::remove_reference_t<decltype(*p)>)q; }
-  };
+  DevSet& M = h->mem;
   const size_t nN = (size_t)n * N, nn = (size_t)n * n;
-  al(&h->X, 8 * (size_t)N * D); al(&h->y, 8 * (size_t)N); al(&h->Z, 8 * (size_t)n * D);
-  al(&h->b, 8 * (size_t)n); al(&h->ls, 8 * (size_t)D); al(&h->phi, 8 * nN); al(&h->S, 8 * nN);
-  al(&h->A, 8 * nn); al(&h->Xt, 8 * nn); al(&h->P, 8 * nn); al(&h->bv, 8 * (size_t)n);
-  al(&h->l, 8 * (size_t)n); al(&h->e, 8 * (size_t)N);
-  al(&h->part, 8 * (size_t)h->ncb * n * D); al(&h->gl, 8 * (size_t)D); al(&h->scal, 8 * 8);
-  al(&h->status, 16);
-  if (err != hipSuccess) return hip_fail(err, "nlml: hipMalloc");
-  NLCHK(hipMemcpy(h->X, X, 8 * (size_t)N * D, hipMemcpyHostToDevice));
-  NLCHK(hipMemcpy(h->y, y, 8 * (size_t)N, hipMemcpyHostToDevice));
-  NLCHK(hipMemcpy(h->Z, Z, 8 * (size_t)n * D, hipMemcpyHostToDevice));
-  NLCHK(hipMemcpy(h->b, b, 8 * (size_t)n, hipMemcpyHostToDevice));
+  GPT_HIPCHK(M.upload(&h->X, X, (size_t)N * D));
+  GPT_HIPCHK(M.upload(&h->y, y, (size_t)N));
+  GPT_HIPCHK(M.upload(&h->Z, Z, (size_t)n * D));
+  GPT_HIPCHK(M.upload(&h->b, b, (size_t)n));
+  GPT_HIPCHK(M.alloc(&h->ls, (size_t)D));
+  GPT_HIPCHK(M.alloc(&h->phi, nN));
+  GPT_HIPCHK(M.alloc(&h->S, nN));
+  GPT_HIPCHK(M.alloc(&h->A, nn));
+  GPT_HIPCHK(M.alloc(&h->Xt, nn));
+  GPT_HIPCHK(M.alloc(&h->P, nn));
+  GPT_HIPCHK(M.alloc(&h->bv, (size_t)n));
+  GPT_HIPCHK(M.alloc(&h->l, (size_t)n));
+  GPT_HIPCHK(M.alloc(&h->e, (size_t)N));
+  GPT_HIPCHK(M.alloc(&h->part, (size_t)h->ncb * n * D));
+  GPT_HIPCHK(M.alloc(&h->gl, (size_t)D));
+  GPT_HIPCHK(M.alloc(&h->scal, 8));
+  GPT_HIPCHK(M.alloc(&h->status, 4));
   *out = h.release();
   return GPT_OK;
 }
@@ -443,7 +434,7 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   hipStream_t st = nullptr;
   if (phase_ms && h->ev.empty()) {
     h->ev.resize(kNlmlPhases + 1);
-    for (auto& e : h->ev) NLCHK(hipEventCreate(&e));
+    for (auto& e : h->ev) GPT_HIPCHK(hipEventCreate(&e));
   }
   int marks = 0;
   auto mark = [&]() {
@@ -454,8 +445,8 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   for (int k = 0; k < D; ++k) lsv[k] = hyper[Lh == D + 2 ? k : 0];
   const double sigma = hyper[Lh - 2], s2 = hyper[Lh - 1];
   const double c = std::sqrt(2.0 / (double)n) * sigma;
-  NLCHK(hipMemcpyAsync(h->ls, lsv, 8 * (size_t)D, hipMemcpyHostToDevice, st));
-  NLCHK(hipMemsetAsync(h->status, 0, 16, st));
+  GPT_HIPCHK(hipMemcpyAsync(h->ls, lsv, 8 * (size_t)D, hipMemcpyHostToDevice, st));
+  GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
   h->have_features = h->have_sin = false;
   mark();
   {
@@ -463,39 +454,39 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
     const int blocks = (int)std::min((total + 255) / 256, (long long)256 * 16);
     hipLaunchKernelGGL(nlml_feature_kernel, dim3(blocks), dim3(256), 0, st, h->X, N, D, h->ls, c,
                        h->Z, h->b, n, h->phi, want_grad ? h->S : nullptr);
-    NLCHK(hipGetLastError());
+    GPT_HIPCHK(hipGetLastError());
   }
   mark();
-  NLCHK(dense_syrk(h->phi, n, N, 1.0, s2, h->A, st));
+  GPT_HIPCHK(dense_syrk(h->phi, n, N, 1.0, s2, h->A, st));
   mark();
-  NLCHK(dense_gemv(h->phi, n, N, h->y, 1.0, h->bv, st));
+  GPT_HIPCHK(dense_gemv(h->phi, n, N, h->y, 1.0, h->bv, st));
   mark();
   dense_chol(h->A, n, h->status, st);
   mark();
-  NLCHK(hipMemcpyAsync(h->l, h->bv, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
+  GPT_HIPCHK(hipMemcpyAsync(h->l, h->bv, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
   dense_trsv(h->A, n, h->l, 0, st);
   dense_trsv(h->A, n, h->l, 1, st);
-  NLCHK(hipGetLastError());
+  GPT_HIPCHK(hipGetLastError());
   mark();
   if (want_grad) {
     static std::atomic<uint64_t> attr{0};
-    NLCHK(set_max_lds_once((const void*)nlml_trinv_kernel, 160 * 1024, attr));
-    NLCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
+    GPT_HIPCHK(set_max_lds_once((const void*)nlml_trinv_kernel, 160 * 1024, attr));
+    GPT_HIPCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
     hipLaunchKernelGGL(nlml_trinv_kernel, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
                        trinv_lds_bytes(n), st, h->A, n, h->Xt);
-    NLCHK(hipGetLastError());
+    GPT_HIPCHK(hipGetLastError());
     mark();
-    NLCHK(dense_syrk(h->Xt, n, n, 1.0, 0.0, h->P, st));
+    GPT_HIPCHK(dense_syrk(h->Xt, n, n, 1.0, 0.0, h->P, st));
     hipLaunchKernelGGL(nlml_mirror_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256),
                        0, st, h->P, n);
     mark();
     hipLaunchKernelGGL(nlml_resid_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, h->phi,
                        h->l, h->y, n, N, h->e);
-    NLCHK(hipGetLastError());
+    GPT_HIPCHK(hipGetLastError());
     mark();
     const long long npair = ((n + 15) / 16 + 1) / 2;
     const unsigned grid = (unsigned)((npair * h->ncb + 3) / 4);
-    NLCHK((n % 2 == 0)
+    GPT_HIPCHK((n % 2 == 0)
               ? launch_grad<true>(D, grid, st, h->P, h->phi, h->S, h->l, h->e, h->X, n, N, h->CB,
                                   h->ncb, 1.0 / s2, h->part)
               : launch_grad<false>(D, grid, st, h->P, h->phi, h->S, h->l, h->e, h->X, n, N, h->CB,
@@ -509,20 +500,20 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   }
   hipLaunchKernelGGL(nlml_scalars_kernel, dim3(1), dim3(kNT), 0, st, h->A,
                      want_grad ? h->P : nullptr, h->y, h->bv, h->l, n, N, h->scal);
-  NLCHK(hipGetLastError());
+  GPT_HIPCHK(hipGetLastError());
   mark();
   double sc[5], gl[kDMax];
   int32_t bad = 0;
   std::vector<double> lh(n);
-  NLCHK(hipMemcpyAsync(sc, h->scal, 8 * 5, hipMemcpyDeviceToHost, st));
-  NLCHK(hipMemcpyAsync(&bad, h->status, 4, hipMemcpyDeviceToHost, st));
-  NLCHK(hipMemcpyAsync(lh.data(), h->l, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
-  if (want_grad) NLCHK(hipMemcpyAsync(gl, h->gl, 8 * (size_t)D, hipMemcpyDeviceToHost, st));
-  NLCHK(hipStreamSynchronize(st));
+  GPT_HIPCHK(hipMemcpyAsync(sc, h->scal, 8 * 5, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipMemcpyAsync(&bad, h->status, 4, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipMemcpyAsync(lh.data(), h->l, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (want_grad) GPT_HIPCHK(hipMemcpyAsync(gl, h->gl, 8 * (size_t)D, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipStreamSynchronize(st));
   if (phase_ms)
     for (int q = 0; q < kNlmlPhases; ++q) {
       float ms = 0.f;
-      NLCHK(hipEventElapsedTime(&ms, h->ev[q], h->ev[q + 1]));
+      GPT_HIPCHK(hipEventElapsedTime(&ms, h->ev[q], h->ev[q + 1]));
       phase_ms[q] = ms;
     }
   h->have_features = true;
@@ -569,8 +560,8 @@ extern "C" int gpt_nlml_features(gpt_nlml* h, double* phi_out, double* sin_out) 
     return GPT_ERR_BAD_DIMS;
   }
   const size_t bytes = 8 * (size_t)h->n * h->N;
-  if (phi_out) NLCHK(hipMemcpy(phi_out, h->phi, bytes, hipMemcpyDeviceToHost));
-  if (sin_out) NLCHK(hipMemcpy(sin_out, h->S, bytes, hipMemcpyDeviceToHost));
+  if (phi_out) GPT_HIPCHK(hipMemcpy(phi_out, h->phi, bytes, hipMemcpyDeviceToHost));
+  if (sin_out) GPT_HIPCHK(hipMemcpy(sin_out, h->S, bytes, hipMemcpyDeviceToHost));
   return GPT_OK;
 }
 

@@ -3,6 +3,7 @@
 #include <mutex>
 
 #include "device_util.h"
+#include "host_util.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -780,16 +781,12 @@ static hipError_t launch_pred_mfma(const double* w, const double* U, const int32
                                    const double* phitest, int n, int D, long long Ntest, int r,
                                    int Q, int S, double* fhat, hipStream_t st,
                                    PredPhaseTiming* timing) {
-  struct Events {                          // destroyed on every exit path
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-  } evs;
-  hipEvent_t* ev = evs.e;
-  if (timing)
-    for (int i = 0; i < 3; ++i) {
-      const hipError_t ee = hipEventCreate(&ev[i]);
-      if (ee != hipSuccess) return ee;
-    }
+  ScopedEvents evs;
+  if (timing) {
+    const hipError_t ee = evs.create(3);
+    if (ee != hipSuccess) return ee;
+  }
+  const hipEvent_t* ev = evs.e.data();     // used under `timing` only
   // temp of up to ~8 GiB of samples per pass; a pass of several workgroup tiles takes a multiple of
   // 128 / gcd(128, r) samples, so its S·r columns fill whole 128-column tiles (no MFMA padding)
   // T per sample: (Ntest / 64 tiles) × (D·r rows) × 64 doubles, tile-contiguous, so a V-phase

@@ -17,7 +17,7 @@
 //                     :193-205; fp64 MFMA tiles for even n) for the next step's V-phase
 //
 // The kernel boundary carries the V-phase -> gradU dependency and the temp of the next step; an
-// epoch of launches is one hipGraph (capi.hip).  φ rows are read twice per step (gradU here, the
+// epoch of launches is one hipGraph (api_session.hip).  φ rows are read twice per step (gradU here, the
 // next step's phidotU one launch later): at r = 20 the step is fp64-compute bound (§8(d): ≈42.5
 // MFLOP against 0.9 MB per chain-step), not HBM bound.
 #include "device_util.h"
