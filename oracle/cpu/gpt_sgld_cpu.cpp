@@ -283,9 +283,11 @@ struct Cfg {
 };
 
 // One chain, GPT_SGLD.jl:345-448 (SGLD + Stiefel).  Returns 0, or 1 on the geodesic NaN bail-out
-// (stores zero-filled as :422-424).  w_out/U_out: the final state; stores may be null.
+// (stores zero-filled as :422-424).  w_out/U_out: the final state; stores may be null.  w_init /
+// U_init (nullable): an initial state that replaces the seed's own draw.
 int run_chain(const Cfg& c, const double* phi, const double* y, const int32_t* I1, uint64_t seed,
-              double* w_out, double* U_out, double* w_store, double* U_store, long long* steps) {
+              double* w_out, double* U_out, double* w_store, double* U_store, long long* steps,
+              const double* w_init = nullptr, const double* U_init = nullptr) {
   const int n = (int)c.n, D = (int)c.D, N = (int)c.N, r = (int)c.r, Q = (int)c.Q, m = (int)c.m;
   const long long nb = (N + m - 1) / m;
   const long long nstore = (c.maxepoch * nb) / c.store_every;
@@ -293,6 +295,8 @@ int run_chain(const Cfg& c, const double* phi, const double* y, const int32_t* I
                                           : (c.burnin + c.maxepoch) * nb;
   std::vector<double> w(Q), U((size_t)n * r * D);
   init_state(n, r, D, Q, seed, c.sigma_w, w.data(), U.data());
+  if (w_init) std::memcpy(w.data(), w_init, sizeof(double) * Q);
+  if (U_init) std::memcpy(U.data(), U_init, sizeof(double) * U.size());
   std::vector<int32_t> I0((size_t)Q * D);
   for (size_t x = 0; x < I0.size(); ++x) I0[x] = I1[x] - 1;
   std::vector<int32_t> order(N), perm, nxt(N);
@@ -497,6 +501,20 @@ long long gptcpu_regression(const int64_t* icfg, const double* dcfg, const doubl
   }
   *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return total;
+}
+
+// One chain of gptcpu_regression from an injected initial state (w_init (Q), U_init (n·r·D), either
+// nullable): the stores of that chain; returns its status, or -1 for an unsupported configuration.
+int gptcpu_regression_from(const int64_t* icfg, const double* dcfg, const double* phi,
+                           const double* y, const int32_t* I, uint64_t seed, const double* w_init,
+                           const double* U_init, double* w_store, double* U_store) {
+  Cfg c;
+  c.n = icfg[0]; c.D = icfg[1]; c.N = icfg[2]; c.r = icfg[3]; c.Q = icfg[4]; c.m = icfg[5];
+  c.burnin = icfg[6]; c.maxepoch = icfg[7]; c.store_every = icfg[8]; c.max_steps = icfg[9];
+  c.epsw = dcfg[0]; c.epsU = dcfg[1]; c.signal_var = dcfg[2]; c.sigma_w = dcfg[3];
+  if (c.r > 32 || c.r < 1 || c.store_every < 1) return -1;
+  long long st = 0;
+  return run_chain(c, phi, y, I, seed, nullptr, nullptr, w_store, U_store, &st, w_init, U_init);
 }
 
 // pred (GPT_SGLD.jl:233-243) for S samples over Ntest rows: fhat[s·Ntest + i] =

@@ -25,6 +25,9 @@ def lib():
         L.gptcpu_regression.argtypes = [C.POINTER(C.c_int64), P_D, P_D, P_D, C.POINTER(C.c_int32),
                                         C.c_int, C.POINTER(C.c_uint64), C.c_int, P_D, P_D, P_D, P_D,
                                         C.POINTER(C.c_int32), P_D, C.POINTER(C.c_int64)]
+        L.gptcpu_regression_from.restype = C.c_int
+        L.gptcpu_regression_from.argtypes = [C.POINTER(C.c_int64), P_D, P_D, P_D, C.POINTER(C.c_int32),
+                                             C.c_uint64, P_D, P_D, P_D, P_D]
         L.gptcpu_cf_sgd.restype = C.c_double
         PP_I = C.POINTER(C.POINTER(C.c_int32))
         PP_D = C.POINTER(C.POINTER(C.c_double))
@@ -74,6 +77,28 @@ def GPTregression_chains(phi, y, signal_var, I, r, Q, m, epsw, epsU, burnin, max
     if stores:
         out.update(w_store=ws, U_store=Us)
     return out
+
+
+def GPTregression_from(phi, y, signal_var, I, r, Q, m, epsw, epsU, burnin, maxepoch, seed, w_init,
+                       U_init, sigma_w=1.0, store_every=1, max_steps=0):
+    """One GPTregression chain from an injected initial state (tests/test_step_cases.py).  Returns
+    (w_store, U_store, status) as oracle.gpt_sgld_ref.GPTregression lays them out."""
+    phi = np.asfortranarray(phi, dtype=np.float64)
+    n, D, N = phi.shape
+    y = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
+    I = np.asfortranarray(I, dtype=np.int32)
+    icfg = np.array([n, D, N, r, Q, m, burnin, maxepoch, store_every, max_steps], dtype=np.int64)
+    dcfg = np.array([epsw, epsU, signal_var, sigma_w], dtype=np.float64)
+    wi = np.ascontiguousarray(w_init, dtype=np.float64)
+    Ui = np.asfortranarray(U_init, dtype=np.float64)
+    T = (maxepoch * (-(-N // m))) // store_every
+    ws = np.zeros((Q, T), order="F")
+    Us = np.zeros((n, r, D, T), order="F")
+    st = lib().gptcpu_regression_from(_p(icfg, C.c_int64), _p(dcfg), _p(phi), _p(y), _p(I, C.c_int32),
+                                      int(seed) & (2 ** 64 - 1), _p(wi), _p(Ui), _p(ws), _p(Us))
+    if st < 0:
+        raise ValueError("gptcpu_regression_from: unsupported configuration")
+    return ws, Us, int(st)
 
 
 def pred(w, U, I, phitest, threads=1):

@@ -210,13 +210,20 @@ MP_DIGITS = 60
 GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
+def expm_mpf(X):
+    """exp(X) by mpmath.expm at MP_DIGITS digits as an mpmath matrix; X holds doubles or mpf."""
+    import mpmath
+    with mpmath.workdps(MP_DIGITS):
+        return mpmath.expm(mpmath.matrix(X.tolist()))
+
+
 def expm_mp(X):
     """exp(X) by mpmath.expm at MP_DIGITS digits, rounded to a pair of float64 arrays (hi, lo)
     with hi + lo = exp(X) to about 1e-23 relative (lo is kept as float32 in the fixtures)."""
     import mpmath
     n = X.shape[0]
     with mpmath.workdps(MP_DIGITS):
-        Emp = mpmath.expm(mpmath.matrix(X.tolist()))
+        Emp = expm_mpf(X)
         hi = np.array([[float(Emp[i, j]) for j in range(n)] for i in range(n)])
         lo = np.array([[float(Emp[i, j] - mpmath.mpf(hi[i, j])) for j in range(n)] for i in range(n)])
     return hi, lo.astype(np.float32).astype(np.float64)
