@@ -33,6 +33,10 @@ Same function names, argument meaning, return values and error behaviour as the 
     GP_nlogmarginal(X, y, signal_var, sigma_RBF2, length_scale)   GPT_SGLD.jl:905
     ExactGP(X, y): nlogmarginal, gradnlogmarginal, value_and_grad, alpha, predict
                                                               GPkit InfExact / prediction
+    SoftmaxJoint(X, y, Z, b, C): neglogjointlkhd, gradneglogjointlkhd, langevin, scores, evaluate
+                                                              ImageExperiment.jl:135-204
+    GPNT_hyperparameters_ng(init_theta, init_hyperparams, neglogjointlkhd, gradneglogjointlkhd,
+                            Z, b; epsilon, num_sgld_iter, num_cg_iter)   GPT_SGLD.jl:1005
     datawhitening(X), proj, geod are not on the device path (host prep / inside the kernel).
 
 Arrays follow Julia's column-major layout: ``phi`` is (n, D, N) Fortran-ordered, ``U`` is
@@ -1006,3 +1010,219 @@ def GPNT_hyperparameters_optim(nlogmarginal, gradnlogmarginal, init_hyperparams,
     ``(minx, minf)``.  Optim.jl's ``:cg`` is replaced by L-BFGS-B without bounds (see
     GPNT_hyperparameters); only the objective and its gradient are parity-tested."""
     return _log_space_minimize(nlogmarginal, gradnlogmarginal, init_hyperparams, None, xtol, ftol)
+
+
+# ------------------------------------------------------------------ softmax classifier: hyper-parameters
+class SoftmaxJoint:
+    """Device-resident joint likelihood -log p(y, theta; h) of the full-theta softmax classifier
+    and its gradient (neglogjointlkhd / gradneglogjointlkhd, ImageExperiment.jl:135-204, with
+    featureNotensor / gradfeatureNotensor at ``Z``, ``b`` in place of the seed).
+
+    ``X`` (N, D), ``y`` (N, integers 1..C), ``Z`` (n, D), ``b`` (n) are uploaded once; ``C``
+    defaults to max(y) - min(y) + 1 (GPT_SGLD.jl:854) and may be passed when a class is absent.
+    Every method takes ``h = [length_scale (D entries, or one: the scalar form); sigma_RBF]``.
+    theta (n, C) is resident on the device: a ``theta_vec`` argument (length n*C, column-major,
+    or an (n, C) array) is uploaded and becomes the resident theta, ``None`` means the resident
+    one.  n <= 1024, D <= 16, C <= 32.  Nothing of size n*N*D, or n*N, is stored."""
+
+    def __init__(self, X, y, Z, b, C=None):
+        X = _f64(X)
+        if X.ndim != 2:
+            raise ValueError("X must be (N, D)")
+        N, D = X.shape
+        Z = _f64(Z)
+        n = Z.shape[0]
+        y = _f64(np.asarray(y, dtype=np.float64).ravel())
+        b = _f64(np.asarray(b, dtype=np.float64).ravel())
+        if Z.shape != (n, D) or b.size != n or y.size != N:
+            raise ValueError("Z must be (n, D), b of length n and y of length N")
+        if C is None:
+            C = int(y.max() - y.min() + 1)
+        self.n, self.N, self.D, self.C = n, N, D, int(C)
+        self._h = _lib.C.c_void_p()
+        check(lib().gpt_cjoint_create(_ptr(X), N, D, _ptr(y), self.C, _ptr(Z), _ptr(b), n,
+                                      _lib.C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gpt_cjoint_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # interpreter shutdown: the library may be gone already
+            pass
+
+    def _theta_arg(self, theta):
+        if theta is None:
+            return None
+        t = np.asarray(theta, dtype=np.float64)
+        if t.size != self.n * self.C or (t.ndim == 2 and t.shape != (self.n, self.C)):
+            raise ValueError("theta must have n*C entries")
+        return _f64(t.reshape((self.n, self.C), order="F"))
+
+    def _eval(self, theta, h, want_grad, want_theta_grad=True):
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        th = self._theta_arg(theta)
+        val = _lib.C.c_double()
+        nC = self.n * self.C
+        grad = np.empty(nC + h.size) if want_grad else None
+        gth = _ptr(grad) if want_grad and want_theta_grad else None
+        gh = _ptr(grad[nC:]) if want_grad else None
+        check(lib().gpt_cjoint_eval(self._h, _ptr(h), h.size, _ptr(th) if th is not None else None,
+                                    1 if want_grad else 0, _lib.C.byref(val), gth, gh))
+        return val.value, grad
+
+    def neglogjointlkhd(self, theta_vec, h):
+        return self._eval(theta_vec, h, False)[0]
+
+    def gradneglogjointlkhd(self, theta_vec, h):
+        """[vec(grad theta); grad length_scale; grad sigma_RBF], n*C + len(h) entries."""
+        return self._eval(theta_vec, h, True)[1]
+
+    def value_and_grad(self, theta_vec, h):
+        return self._eval(theta_vec, h, True)
+
+    def hyper_value_and_grad(self, h):
+        """Value and the gradient with respect to h alone at the resident theta (the M step)."""
+        val, grad = self._eval(None, h, True, want_theta_grad=False)
+        return val, grad[self.n * self.C:]
+
+    def theta(self):
+        out = np.empty((self.n, self.C), order="F")
+        check(lib().gpt_cjoint_get_theta(self._h, _ptr(out)))
+        return out
+
+    def set_theta(self, theta):
+        check(lib().gpt_cjoint_set_theta(self._h, _ptr(self._theta_arg(theta))))
+
+    @property
+    def steps(self):
+        """0-based counter of the next Langevin step."""
+        t = _lib.C.c_int64()
+        check(lib().gpt_cjoint_steps(self._h, _lib.C.byref(t)))
+        return t.value
+
+    def langevin(self, h, eps, nsteps, seed, t0=None):
+        """``nsteps`` Langevin steps on the resident theta at ``h`` (GPT_SGLD.jl:1031-1033),
+        theta <- theta - (eps/2 grad + sqrt(eps) xi), with no host round trip; the noise of
+        0-based step t and class c is normals(n, seed, t, THETA_NOISE, c).  ``t0`` sets the step
+        counter first (None: it continues).  A non-finite theta raises GPTError
+        (GPT_ERR_NAN_THETA) and the remaining steps are not taken."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        check(lib().gpt_cjoint_langevin(self._h, _ptr(h), h.size, float(eps), int(nsteps),
+                                        int(seed), -1 if t0 is None else int(t0)))
+
+    def _xtest(self, Xtest):
+        Xtest = _f64(Xtest)
+        if Xtest.ndim != 2 or Xtest.shape[1] != self.D:
+            raise ValueError("Xtest must be (Ntest, D)")
+        return Xtest
+
+    def scores(self, h, Xtest):
+        """featureNotensor(Xtest)' theta at ``h``: (Ntest, C)."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        Xtest = self._xtest(Xtest)
+        out = np.empty((Xtest.shape[0], self.C), order="F")
+        check(lib().gpt_cjoint_scores(self._h, _ptr(h), h.size, _ptr(Xtest), Xtest.shape[0],
+                                      _ptr(out)))
+        return out
+
+    def evaluate(self, h, Xtest, ytest):
+        """The prop_missed / mean_nlp line of the reference's loop (ImageExperiment.jl:258-268) as
+        a ClassEval of one sample; the scores never leave the device before they are evaluated."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        Xtest = self._xtest(Xtest)
+        Nt = Xtest.shape[0]
+        yi = _labels(ytest, Nt)
+        res = ClassEval()
+        res.prop_missed, res.mean_nlp, avg = np.empty(1), np.empty(1), np.empty(2)
+        res.mean_fhat = np.empty((Nt, self.C), order="F")
+        res.prediction = np.empty(Nt, dtype=np.int32)
+        res.nlp = np.empty(Nt)
+        res.scores = np.empty((Nt, self.C, 1), order="F")
+        check(lib().gpt_cjoint_class_eval(self._h, _ptr(h), h.size, _ptr(Xtest), _ptr(yi, P_I32), Nt,
+                                          _ptr(res.prop_missed), _ptr(res.mean_nlp), _ptr(avg),
+                                          _ptr(res.mean_fhat), _ptr(res.prediction, P_I32),
+                                          _ptr(res.nlp), _ptr(res.scores)))
+        res.avg_prop_missed, res.avg_mean_nlp = float(avg[0]), float(avg[1])
+        res.window = (0, 1)
+        return res
+
+
+def gpnt_neglogjoint_oneshot(X, y, Z, b, theta, hyperparams, C=None, want_grad=True):
+    """The one-shot host-pointer entry the Julia shim binds (gpt_gpnt_neglogjoint)."""
+    X = _f64(X)
+    N, D = X.shape
+    Z = _f64(Z)
+    n = Z.shape[0]
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    b = _f64(np.asarray(b, dtype=np.float64).ravel())
+    if C is None:
+        C = int(y.max() - y.min() + 1)
+    th = _f64(np.asarray(theta, dtype=np.float64).reshape((n, C), order="F"))
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    val = _lib.C.c_double()
+    grad = np.empty(n * C + h.size)
+    check(lib().gpt_gpnt_neglogjoint(_ptr(X), N, D, _ptr(y), C, _ptr(Z), _ptr(b), n, _ptr(th),
+                                     _ptr(h), h.size, 1 if want_grad else 0, _lib.C.byref(val),
+                                     _ptr(grad)))
+    return (val.value, grad) if want_grad else val.value
+
+
+def _joint(fn, what):
+    obj = getattr(fn, "__self__", None)
+    if not isinstance(obj, SoftmaxJoint) or getattr(fn, "__name__", "") != what:
+        raise TypeError("%s must be the %s method of a SoftmaxJoint (it stands for the reference's "
+                        "closure over the training data and the features)" % (what, what))
+    return obj
+
+
+def GPNT_hyperparameters_ng(init_theta, init_hyperparams, neglogjointlkhd, gradneglogjointlkhd, Z=None,
+                            b=None, epsilon=1e-2, num_sgld_iter=10, num_cg_iter=10, seed=0, tol=1e-7,
+                            max_iter=200, trace=False):
+    """GPT_SGLD.jl:1005-1063: stochastic EM on the non-Gaussian joint likelihood.  The two
+    function arguments are the ``neglogjointlkhd`` and ``gradneglogjointlkhd`` methods of one
+    SoftmaxJoint (which holds X, y, Z and b; ``Z`` and ``b`` are accepted for the reference's
+    signature and not read).  Per round: ``num_sgld_iter`` Langevin steps of size ``epsilon`` on
+    the resident theta (the step counter runs on from round to round, noise from ``seed``), then
+    ``num_cg_iter`` iterations of conjugate gradients over the log-hyper-parameters with theta
+    fixed and the chain-rule gradient ``grad .* exp(loghyper)`` (:1021).  It stops when
+    ``norm(exp(old) - exp(new)) <= tol`` (:1052, 1e-7 there) or after ``max_iter`` rounds: the
+    reference's loop has no cap, and a stochastic theta can keep it running for ever.
+
+    Returns ``exp(loghyper)``; with ``trace=True`` also a list with, per round, the reference's
+    printed ``(function_value_before, function_value_after, hyperparams)``.  theta stays resident
+    (``SoftmaxJoint.theta()``).  Optim.jl's ``:cg`` is replaced by
+    ``scipy.optimize.minimize(method="CG")``, so iterates are not the reference's; only the
+    objective and its gradient are parity-tested."""
+    from scipy.optimize import minimize
+
+    joint = _joint(neglogjointlkhd, "neglogjointlkhd")
+    if _joint(gradneglogjointlkhd, "gradneglogjointlkhd") is not joint:
+        raise TypeError("neglogjointlkhd and gradneglogjointlkhd must belong to one SoftmaxJoint")
+    joint.set_theta(init_theta)
+    lh = np.log(np.asarray(init_hyperparams, dtype=np.float64).ravel())
+
+    def fun(x):
+        hx = np.exp(x)
+        val, gh = joint.hyper_value_and_grad(hx)
+        return val, gh * hx
+
+    rounds = []
+    t = 0
+    for _ in range(int(max_iter)):
+        if num_sgld_iter > 0:
+            joint.langevin(np.exp(lh), epsilon, num_sgld_iter, seed, t0=t)
+            t += int(num_sgld_iter)
+        res = minimize(fun, lh, jac=True, method="CG", options={"maxiter": int(num_cg_iter)})
+        new = np.asarray(res.x, dtype=np.float64)
+        if trace:
+            rounds.append((joint.neglogjointlkhd(None, np.exp(lh)),
+                           joint.neglogjointlkhd(None, np.exp(new)), np.exp(new)))
+        absdiff = float(np.linalg.norm(np.exp(lh) - np.exp(new)))
+        lh = new
+        if absdiff <= tol:
+            break
+    return (np.exp(lh), rounds) if trace else np.exp(lh)

@@ -133,6 +133,28 @@ SIGNATURES = {
     "gpt_nlml_destroy": (C.c_int, [C.c_void_p]),
     "gpt_gpnt_nlogmarginal": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_int64, P_D,
                                         C.c_int64, C.c_int64, P_D, P_D]),
+    "gpt_cjoint_create": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, C.c_int64, P_D, P_D, C.c_int64,
+                                    C.POINTER(C.c_void_p)]),
+    "gpt_cjoint_eval": (C.c_int, [C.c_void_p, P_D, C.c_int64, P_D, C.c_int32, P_D, P_D, P_D]),
+    "gpt_cjoint_set_theta": (C.c_int, [C.c_void_p, P_D]),
+    "gpt_cjoint_get_theta": (C.c_int, [C.c_void_p, P_D]),
+    "gpt_cjoint_langevin": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_double, C.c_int64,
+                                      C.c_uint64, C.c_int64]),
+    "gpt_cjoint_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "gpt_cjoint_scores": (C.c_int, [C.c_void_p, P_D, C.c_int64, P_D, C.c_int64, P_D]),
+    "gpt_cjoint_scores_dev": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p]),
+    "gpt_cjoint_class_eval": (C.c_int, [C.c_void_p, P_D, C.c_int64, P_D, P_I32, C.c_int64, P_D, P_D,
+                                        P_D, P_D, P_I32, P_D, P_D]),
+    "gpt_cjoint_time": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int32, C.c_int32, P_D]),
+    "gpt_cjoint_destroy": (C.c_int, [C.c_void_p]),
+    "gpt_gpnt_neglogjoint": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, C.c_int64, P_D, P_D,
+                                       C.c_int64, P_D, P_D, C.c_int64, C.c_int64, P_D, P_D]),
+    "gpt_gpnt_joint_langevin": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, C.c_int64, P_D, P_D,
+                                          C.c_int64, P_D, P_D, C.c_int64, C.c_double, C.c_int64,
+                                          C.c_uint64, C.c_int64]),
+    "gpt_gpnt_joint_scores": (C.c_int, [P_D, C.c_int64, C.c_int64, C.c_int64, P_D, P_D, C.c_int64,
+                                        P_D, P_D, C.c_int64, P_D]),
     "gpt_egp_create": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, C.POINTER(C.c_void_p)]),
     "gpt_egp_eval": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int32, P_D, P_D, P_D]),
     "gpt_egp_eval_timed": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int32, P_D, P_D, P_D]),

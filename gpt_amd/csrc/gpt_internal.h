@@ -400,6 +400,46 @@ hipError_t launch_class_eval(const double* scores, const int32_t* y, long long N
 hipError_t launch_class_mean(const double* scores, long long Ntest, int C, int first, int last,
                              double* mean_out, hipStream_t st);
 
+// Joint likelihood of the full-theta softmax classifier and its gradient (cjoint.hip).
+struct CjLayout {
+  int CC, TI, theta_lds, nblk;   // CC: C rounded up to 2, 4, 8, 16, 32; TI: data columns per tile;
+                                 // theta_lds: theta (n x CC) sits in LDS; nblk: workgroups
+  long long ntiles;
+  size_t o_sr, o_X, o_inv, o_red, o_phi, o_S, o_theta, bytes;
+};
+CjLayout cjoint_layout(int n, long long N, int C);
+constexpr int kCjMaxBlocks = 256;                 // the bound of the grid-stride over tiles
+enum CjMode : int {
+  kCjValue = 0,      // the value's partial sums
+  kCjTheta = 1,      // and the partials of d/dtheta (the Langevin step)
+  kCjFull = 2,       // and those of d/dlength_scale, d/dsigma
+  kCjScores = 3,     // scores (N, C) = phi(X)'theta, no likelihood
+  kCjFeatures = 4    // diagnostics: the tile's phi and S only (the sincos share of an evaluation)
+};
+struct CjArgs {
+  const double* X;         // N*D   rows to evaluate, X[i + N k]
+  long long N;
+  int D, n, C;
+  const int32_t* y0;       // N     0-based labels (unused by kCjScores / kCjFeatures)
+  const double* Z;         // n*D
+  const double* b;         // n
+  const double* ls;        // D     length scales
+  double c;                // sqrt(2/n)·sigma_RBF
+  const double* theta;     // n*C
+  double* part_theta;      // nblk*n*C  per-workgroup partials of phi·R'
+  double* part_tx;         // nblk*D*n  per-workgroup partials of (S o theta R)·X, [k][j]
+  double* part_sc;         // nblk*2    per-workgroup value and sigma sums
+  double* scores;          // N*C       (kCjScores)
+  const int32_t* status;   // non-zero: the launch does nothing (a Langevin run that met a NaN)
+};
+hipError_t launch_cjoint_eval(const CjArgs& A, const CjLayout& L, int mode, hipStream_t st);
+// out = [value; d/dsigma; d/dl (D); d/dtheta (n*C)], the last two blocks only with `full`
+hipError_t launch_cjoint_finish(const CjArgs& A, const CjLayout& L, double sigma, bool full,
+                                double* out, hipStream_t st);
+// theta <- theta - (eps/2·(sum of the partials + theta) + sqrt(eps)·xi), xi of 0-based step t
+hipError_t launch_cjoint_update(const CjArgs& A, const CjLayout& L, double* theta, double eps,
+                                uint64_t seed, uint32_t t, int32_t* status, hipStream_t st);
+
 // Host-side Philox consumers (init / permutations / samplenz)
 void host_init_state(int n, int r, int D, int Q, uint64_t seed, bool stiefel, double sigma_w,
                      double* w, double* U, int cls = 0, bool cls_init = false);

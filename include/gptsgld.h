@@ -441,6 +441,74 @@ int gpt_gpnt_nlogmarginal(const double* X, int64_t N, int64_t D, const double* y
                           const double* b, int64_t n, const double* hyper, int64_t Lh,
                           int64_t want_grad, double* nlml_out, double* grad_out);
 
+/* ---- hyper-parameter learning of the softmax classifier: the joint likelihood ---------- */
+/* neglogjointlkhd / gradneglogjointlkhd (ImageExperiment.jl:135-204), the objective of
+ * GPNT_hyperparameters_ng (GPT_SGLD.jl:1005-1063): with phi = featureNotensor(X) at
+ *   hyper = [length_scale (D entries, or 1: the scalar form); sigma_RBF],  Lh = D + 1 or 2,
+ * and s = theta'phi (C, N),
+ *   value = sum_i (logsumexp(s[:, i]) - s[y_i, i]) + |theta|^2/2,
+ * and its gradient with respect to theta (n, C) and hyper.  X (N, D), Z (n, D), theta (n, C)
+ * column-major; y (N) doubles holding integers in 1..C (a class may be absent); n <= 1024,
+ * D <= 16, C <= 32.  A dimension out of range, a label that is no integer in 1..C, a NULL array
+ * or a hyper-parameter that is not positive and finite is GPT_ERR_BAD_DIMS before any kernel.
+ *
+ * The evaluator keeps X, y, Z, b, theta and its scratch on the device; nothing of size n*N is
+ * stored.  Equal inputs give equal bits, and want_grad = 0 returns the value bits of a gradient
+ * evaluation.  gpt_cjoint_eval: theta (n, C) is uploaded and becomes the resident one, NULL
+ * means the resident theta (zero after create); grad_theta (n*C) and grad_hyper (Lh) may be
+ * NULL. */
+typedef struct gpt_cjoint gpt_cjoint;
+int gpt_cjoint_create(const double* X, int64_t N, int64_t D, const double* y, int64_t C,
+                      const double* Z, const double* b, int64_t n, gpt_cjoint** out);
+int gpt_cjoint_eval(gpt_cjoint* h, const double* hyper, int64_t Lh, const double* theta,
+                    int32_t want_grad, double* value, double* grad_theta, double* grad_hyper);
+int gpt_cjoint_set_theta(gpt_cjoint* h, const double* theta);
+int gpt_cjoint_get_theta(gpt_cjoint* h, double* theta_out);
+/* nsteps Langevin steps on the resident theta at hyper with no host round trip
+ * (GPT_SGLD.jl:1031-1033): theta <- theta - (eps/2*grad_theta + sqrt(eps)*xi), where xi of 0-based
+ * step t, feature j and class c is element j of the normal stream (seed, t, THETA_NOISE, c), the
+ * contract of gpt_gpnt_sgld_class.  The handle keeps the counter of the next step (0 after
+ * create, gpt_cjoint_steps reads it): t0 >= 0 sets it first, t0 < 0 continues.  When theta turns
+ * non-finite the remaining steps are not taken and the call returns GPT_ERR_NAN_THETA. */
+int gpt_cjoint_langevin(gpt_cjoint* h, const double* hyper, int64_t Lh, double eps, int64_t nsteps,
+                        uint64_t seed, int64_t t0);
+int gpt_cjoint_steps(gpt_cjoint* h, int64_t* step_out);
+/* scores (Ntest, C) = featureNotensor(Xtest)'theta at hyper for the resident theta: the block
+ * gpt_class_eval reads as one sample.  The _dev form takes device pointers and a hipStream_t and
+ * does not synchronise. */
+int gpt_cjoint_scores(gpt_cjoint* h, const double* hyper, int64_t Lh, const double* Xtest,
+                      int64_t Ntest, double* scores_out);
+int gpt_cjoint_scores_dev(gpt_cjoint* h, const double* hyper, int64_t Lh, const double* Xtest_dev,
+                          int64_t Ntest, double* scores_dev, void* hip_stream);
+/* The scores of the test rows, kept on the device, through gpt_class_eval_dev as one sample
+ * (ImageExperiment.jl:258-268): outputs as gpt_class_eval with T = 1; scores_out (Ntest, C)
+ * optional. */
+int gpt_cjoint_class_eval(gpt_cjoint* h, const double* hyper, int64_t Lh, const double* Xtest,
+                          const int32_t* ytest, int64_t Ntest, double* prop_missed_out,
+                          double* mean_nlp_out, double* avg_out, double* mean_scores_out,
+                          int32_t* prediction_out, double* nlp_out, double* scores_out);
+/* Diagnostics (scripts/time_cjoint.py): device-event time in ms per evaluation over reps
+ * back-to-back evaluations in mode 0 (value), 1 (value and grad_theta partials), 2 (the full
+ * gradient) or 4 (the features phi and S of every tile alone). */
+int gpt_cjoint_time(gpt_cjoint* h, const double* hyper, int64_t Lh, int32_t mode, int32_t reps,
+                    double* ms_out);
+int gpt_cjoint_destroy(gpt_cjoint* h);
+/* One-shot host-pointer forms (create, one call, destroy).  grad_out (n*C + Lh) =
+ * [vec(grad_theta); grad_length_scale; grad_sigma_RBF], the reference's layout.
+ * gpt_gpnt_joint_langevin updates theta in place from step t0 >= 0; gpt_gpnt_joint_scores needs
+ * no training data. */
+int gpt_gpnt_neglogjoint(const double* X, int64_t N, int64_t D, const double* y, int64_t C,
+                         const double* Z, const double* b, int64_t n, const double* theta,
+                         const double* hyper, int64_t Lh, int64_t want_grad, double* value_out,
+                         double* grad_out);
+int gpt_gpnt_joint_langevin(const double* X, int64_t N, int64_t D, const double* y, int64_t C,
+                            const double* Z, const double* b, int64_t n, double* theta,
+                            const double* hyper, int64_t Lh, double eps, int64_t nsteps,
+                            uint64_t seed, int64_t t0);
+int gpt_gpnt_joint_scores(const double* Xtest, int64_t Ntest, int64_t D, int64_t C, const double* Z,
+                          const double* b, int64_t n, const double* theta, const double* hyper,
+                          int64_t Lh, double* scores_out);
+
 /* ---- exact GP regression (the reference's quality ceiling) ------------------------------ */
 /* GP_nlogmarginal (GPT_SGLD.jl:905-915) and GPkit's InfExact / prediction with CovSEiso or
  * CovSEard, LikGauss and a zero mean: K_ij = sigma_RBF^2 exp(-1/2 sum_k ((x_ik - x_jk)/l_k)^2),

@@ -13,7 +13,8 @@ export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTreg
        GPTregression_chains_x, GPT_SGLDERM, pred, RMSE,
        GPNT_SGLD, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
        init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal, GP_nlogmarginal, GP_gradnlogmarginal, GP_predict,
-       GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class
+       GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class,
+       neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores
 
 const LIB = get(ENV, "GPTSGLD_LIB", joinpath(@__DIR__, "..", "gpt_amd", "libgptsgld.so"))
 
@@ -537,6 +538,83 @@ function GP_predict(X::Array{Float64,2}, y::Array{Float64}, hyperparams::Vector{
     end
     lp = ytest === nothing ? nothing : lpv
     return fmu, fs2 .+ hyperparams[end], fmu, fs2, lp
+end
+
+# The joint likelihood of the full-theta softmax classifier (neglogjointlkhd /
+# gradneglogjointlkhd, ImageExperiment.jl:135-204; the objective of GPNT_hyperparameters_ng,
+# GPT_SGLD.jl:1005-1063): X, y, Z, b take the closures' place.  theta_vec has n*C entries
+# (vec of the n x C matrix), hyperparams = [length_scale (D entries, or one); sigma_RBF], labels are
+# integers in 1..C (C defaults to max - min + 1 and may be passed when a class is absent).  Every
+# length is checked here, before the library reads the arrays.
+function joint_dims(X::Array{Float64,2}, y::Array, Z::Array{Float64,2}, b::Array{Float64},
+                    theta_vec::Array{Float64}, hyperparams::Vector{Float64}, C::Integer)
+    N, D = size(X); n = size(Z, 1)
+    size(Z, 2) == D || error("Z must be (n, D)")
+    length(b) == n || error("b must have n entries")
+    length(y) == N || error("y must have N entries")
+    length(theta_vec) == n * C || error("theta_vec must have n*C entries")
+    (length(hyperparams) == 2 || length(hyperparams) == D + 1) ||
+        error("hyperparams must have 2 or D + 1 entries")
+    return N, D, n
+end
+joint_classes(y, C) = C === nothing ? Int(maximum(y) - minimum(y) + 1) : Int(C)
+
+function gpnt_joint(X::Array{Float64,2}, y::Array, Z::Array{Float64,2}, b::Array{Float64},
+                    theta_vec::Array{Float64}, hyperparams::Vector{Float64}, want_grad::Bool;
+                    C=nothing)
+    ncls = joint_classes(y, C)
+    N, D, n = joint_dims(X, y, Z, b, theta_vec, hyperparams, ncls)
+    yf = collect(Float64, vec(y))
+    value = Array{Float64}(undef, 1)
+    grad = Array{Float64}(undef, n * ncls + length(hyperparams))
+    check(ccall((:gpt_gpnt_neglogjoint, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64,
+                 Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+                X, N, D, yf, ncls, Z, vec(b), n, vec(theta_vec), hyperparams, length(hyperparams),
+                Int64(want_grad), value, grad))
+    return value[1], grad
+end
+# the reference's closures: neglogjointlkhd(theta_vec, hyperparams), gradneglogjointlkhd(...) ->
+# [vec(gradtheta); gradlength_scale; gradsigma_RBF]
+neglogjointlkhd(X, y, Z, b, theta_vec, hyperparams; C=nothing) =
+    gpnt_joint(X, y, Z, b, theta_vec, hyperparams, false; C=C)[1]
+gradneglogjointlkhd(X, y, Z, b, theta_vec, hyperparams; C=nothing) =
+    gpnt_joint(X, y, Z, b, theta_vec, hyperparams, true; C=C)[2]
+
+# nsteps Langevin steps on theta at hyperparams from the 0-based step t0 (the E step of
+# GPNT_hyperparameters_ng, GPT_SGLD.jl:1031-1033); returns the new theta_vec.  Error code 4: theta
+# turned non-finite.
+function joint_langevin(X::Array{Float64,2}, y::Array, Z::Array{Float64,2}, b::Array{Float64},
+                        theta_vec::Array{Float64}, hyperparams::Vector{Float64}, epsilon::Real,
+                        nsteps::Integer, seed::Integer; t0::Integer=0, C=nothing)
+    ncls = joint_classes(y, C)
+    N, D, n = joint_dims(X, y, Z, b, theta_vec, hyperparams, ncls)
+    (nsteps >= 0 && t0 >= 0) || error("nsteps and t0 must not be negative")
+    yf = collect(Float64, vec(y))
+    theta = collect(Float64, vec(theta_vec))
+    check(ccall((:gpt_gpnt_joint_langevin, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64,
+                 Ptr{Float64}, Ptr{Float64}, Int64, Float64, Int64, UInt64, Int64),
+                X, N, D, yf, ncls, Z, vec(b), n, theta, hyperparams, length(hyperparams),
+                epsilon, nsteps, UInt64(seed), t0))
+    return theta
+end
+
+# scores (Ntest, C) = featureNotensor(Xtest)' * theta at hyperparams: class_eval's input
+# (reshape to (Ntest, C, 1)), the prop_missed / mean_nlp line of ImageExperiment.jl:258-268
+function joint_scores(Xtest::Array{Float64,2}, Z::Array{Float64,2}, b::Array{Float64},
+                      theta::Array{Float64,2}, hyperparams::Vector{Float64})
+    Nt, D = size(Xtest); n, ncls = size(theta)
+    size(Z) == (n, D) || error("Z must be (n, D)")
+    length(b) == n || error("b must have n entries")
+    (length(hyperparams) == 2 || length(hyperparams) == D + 1) ||
+        error("hyperparams must have 2 or D + 1 entries")
+    scores = Array{Float64}(undef, Nt, ncls)
+    check(ccall((:gpt_gpnt_joint_scores, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64},
+                 Ptr{Float64}, Int64, Ptr{Float64}),
+                Xtest, Nt, D, ncls, Z, vec(b), n, theta, hyperparams, length(hyperparams), scores))
+    return scores
 end
 
 end # module
