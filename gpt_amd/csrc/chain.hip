@@ -429,16 +429,18 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
       const int gg = task / NCH, c = task - gg * NCH;
       const int q = 64 * c + ln;
       const bool ok = q < Q;
-      const int qq = ok ? q : 0;
-      // every LDS read of the task in flight at once: kChainDMax dimensions, no guards (rows
-      // kk >= D of the table hit the ones slots)
+      // every LDS read of the task in flight at once: w_q (clamped index, read by every lane:
+      // read under `ok` it compiles behind the product, under an exec mask, one more LDS round
+      // trip between the two barriers) and the kChainDMax dimensions, no guards (rows kk >= D of
+      // the table hit the ones slots)
+      const double wq = w_l[min(q, Q - 1)];
       double tv[kChainDMax];                       // Π_k temp (computeV), as a product tree
 #pragma unroll
       for (int kk = 0; kk < kChainDMax; ++kk)
         tv[kk] = tsl[((itp[x][kk >> 2] >> (8 * (kk & 3))) & 0xff) + gg];
       static_assert(kChainDMax == 8, "product tree below is written for 8 dimensions");
       const double V = ((tv[0] * tv[1]) * (tv[2] * tv[3])) * ((tv[4] * tv[5]) * (tv[6] * tv[7]));
-      const double wV = ok ? w_l[qq] * V : 0.0;
+      const double wV = ok ? wq * V : 0.0;
       if (ok) wVr[gg * kChainQS + q] = wV;         // w_q·V_q, gathered by the run sums in (e)
       vsave[x] = ok ? V : 0.0;
       const double fs = wave_sum(wV);
