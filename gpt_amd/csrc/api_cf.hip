@@ -94,8 +94,8 @@ static int cf_sgd_run(
          f.testpred_store && f.trainRMSE && f.testRMSE && f.N >= 1 && f.Ntest >= 1 &&
          f.ldr >= f.N && f.ldt >= f.Ntest && f.N == folds[0].N;
   if (!ok) { set_error(std::string("bad ") + name + " arguments"); return GPT_ERR_BAD_DIMS; }
-  if (!cf_rank_supported((int)r) || cf_lds_bytes((int)r, (int)m, (int)(D1 + D2), D1 <= 64 && D2 <= 64) > 160 * 1024) {
-    set_error(std::string(name) + ": rank not instantiated (1-6,8,10,12,15,16,20) or minibatch too large");
+  if (!rank_supported((int)r) || cf_lds_bytes((int)r, (int)m, (int)(D1 + D2), D1 <= 64 && D2 <= 64) > 160 * 1024) {
+    set_error(std::string(name) + ": rank not instantiated (" + ranks_text() + ") or minibatch too large");
     return GPT_ERR_BAD_DIMS;
   }
   const int64_t N = folds[0].N;
@@ -545,8 +545,8 @@ static int cf_gibbs_run(
       !(sigma_w > 0)) {
     set_error(std::string("bad ") + name + " arguments"); return GPT_ERR_BAD_DIMS;
   }
-  if (!cf_rank_supported((int)r) || r * r > 1024) {
-    set_error(std::string(name) + ": rank not instantiated (1-6,8,10,12,15,16,20)"); return GPT_ERR_BAD_DIMS;
+  if (!rank_supported((int)r) || r * r > 1024) {
+    set_error(std::string(name) + ": rank not instantiated (" + ranks_text() + ")"); return GPT_ERR_BAD_DIMS;
   }
   std::vector<int32_t> tu, tm, eu, em;
   std::vector<double> tr, er;

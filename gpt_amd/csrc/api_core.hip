@@ -146,7 +146,7 @@ bool valid_cfg(const gpt_sgld_config* c) {
   }
   if (c->D > kDMax) { set_error("D > 16 is not supported by the kernels"); return false; }
   if (!rank_supported((int)c->r)) {
-    set_error("rank r not instantiated (supported: 1-6,8,10,12,15,16,20)"); return false;
+    set_error("rank r not instantiated (supported: " + ranks_text() + ")"); return false;
   }
   if (c->n > (1 << 20) || c->N > (1LL << 31) - 1 || c->Q > (1 << 20)) {
     set_error("dimension too large"); return false;

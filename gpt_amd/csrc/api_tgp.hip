@@ -15,7 +15,7 @@ extern "C" int gpt_tgp_gibbs(const double* b, const double* y, int64_t n, int64_
       num_iterations <= burnin || !(sigma > 0)) {
     set_error("bad GPT_inf arguments"); return GPT_ERR_BAD_DIMS;
   }
-  if (!rank_supported((int)r)) { set_error("rank r not instantiated (supported: 1-6,8,10,12,15,16,20)"); return GPT_ERR_BAD_DIMS; }
+  if (!rank_supported((int)r)) { set_error("rank r not instantiated (supported: " + ranks_text() + ")"); return GPT_ERR_BAD_DIMS; }
   if (n * r > 8192 || q > 8192 || (double)n * D * N > 2e9) { set_error("dimension too large"); return GPT_ERR_BAD_DIMS; }
   std::vector<int32_t> I0((size_t)q * D);
   if (I) {

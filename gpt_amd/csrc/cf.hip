@@ -15,8 +15,6 @@
 
 namespace gpt {
 
-#define GPT_CF_RANKS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(15) X(16) X(20)
-
 constexpr int kCfNT = 1024;
 constexpr int kCfNW = kCfNT / 64;
 typedef double pd4 __attribute__((ext_vector_type(4)));
@@ -1321,18 +1319,11 @@ hipError_t launch_cfg_rows(int side, int r, const double* W, const double* Oth, 
                            const int32_t* other, const double* y, double signal_var, double su2,
                            uint64_t seed, uint32_t sweep, uint32_t stream, int32_t* status,
                            hipStream_t st) {
-  switch (r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    hipLaunchKernelGGL((cfg_rows_kernel<RR, 0>), dim3((rows_me + 3) / 4), dim3(256), 0, st,   \
-                       side, W, Oth, rows_oth, Me, rows_me, ptr, lst, other, y, signal_var,   \
-                       su2, seed, sweep, stream, status, nullptr, nullptr);                   \
-    break;
-    GPT_CF_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(r, [&](auto R) {
+    return launch<cfg_rows_kernel<R, 0>>(dim3((rows_me + 3) / 4), dim3(256), 0, st, side, W, Oth,
+                                         rows_oth, Me, rows_me, ptr, lst, other, y, signal_var,
+                                         su2, seed, sweep, stream, status, nullptr, nullptr);
+  });
 }
 
 // w | U, V (GPT_fullw_gibbs :1088-1094): precision M = Kronᵀ·Kron/σ² + I/σ_w² and rhs x =
@@ -1349,24 +1340,18 @@ hipError_t launch_cfg_wsystem(int r, const double* U, int n1, const double* V, i
   double* H = scratch;
   double* hv = H + (size_t)n1 * p;
   double* Zp = hv + (size_t)n1 * r;
-  switch (r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    hipLaunchKernelGGL((cfg_rows_kernel<RR, 1>), dim3((n1 + 3) / 4), dim3(256), 0, st, 0,      \
-                       nullptr, V, n2, nullptr, n1, uptr, ulst, movies, y, 1.0, 1.0,          \
-                       (uint64_t)0, 0u, 0u, nullptr, H, hv);                                  \
-    hipLaunchKernelGGL(cfg_wprec_kernel<RR>,                                                  \
-                       dim3((p + kWpTile - 1) / kWpTile, (p + kWpTile - 1) / kWpTile,        \
-                            kWpSlices), dim3(256), 0, st, H, U, n1, Zp);                      \
-    hipLaunchKernelGGL(cfg_wprec_fin_kernel<RR>, dim3((p * p + 255) / 256), dim3(256), 0, st, \
-                       Zp, alpha, beta, M);                                                   \
-    hipLaunchKernelGGL(cfg_wrhs_kernel<RR>, dim3(1), dim3(512), 0, st, hv, U, n1, ysc, x);    \
-    break;
-    GPT_CF_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(r, [&](auto R) {
+    hipLaunchKernelGGL((cfg_rows_kernel<R, 1>), dim3((n1 + 3) / 4), dim3(256), 0, st, 0, nullptr,
+                       V, n2, nullptr, n1, uptr, ulst, movies, y, 1.0, 1.0, (uint64_t)0, 0u, 0u,
+                       nullptr, H, hv);
+    hipLaunchKernelGGL(cfg_wprec_kernel<R>,
+                       dim3((p + kWpTile - 1) / kWpTile, (p + kWpTile - 1) / kWpTile, kWpSlices),
+                       dim3(256), 0, st, H, U, n1, Zp);
+    hipLaunchKernelGGL(cfg_wprec_fin_kernel<R>, dim3((p * p + 255) / 256), dim3(256), 0, st, Zp,
+                       alpha, beta, M);
+    hipLaunchKernelGGL(cfg_wrhs_kernel<R>, dim3(1), dim3(512), 0, st, hv, U, n1, ysc, x);
+    return hipGetLastError();
+  });
 }
 
 // Per sweep kept (GPT_fullw_gibbs / GPT_fixw_gibbs bookkeeping, :1097-1118): the train / test
@@ -1414,46 +1399,19 @@ size_t cf_lazy_lds_bytes(int r, int m, int nfeat, int rows, int nb) {
          16 * (size_t)nfeat * r + 16 + 16 + 16 * (size_t)m * r;
 }
 
-bool cf_rank_supported(int r) {
-  switch (r) {
-#define CASE(RR) case RR:
-    GPT_CF_RANKS(CASE)
-#undef CASE
-    return true;
-    default: return false;
-  }
-}
-
-template <int RR, int DM>
-static hipError_t launch_cf_epoch_t(const CfParams& P, const CfChain* chains, int nchains,
-                                    long long step0, int bt0, int nb, size_t lds, hipStream_t st,
-                                    const long long* step_base) {
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = set_max_lds_once((const void*)cf_epoch_kernel<RR, DM>, 160 * 1024, attr);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((cf_epoch_kernel<RR, DM>), dim3(nchains), dim3(kCfNT), lds, st, P, chains,
-                     step_base, step0, bt0, nb);
-  return hipGetLastError();
-}
-
 hipError_t launch_cf_epoch(const CfParams& P, const CfChain* chains, int nchains, long long step0,
                            int bt0, int nb, int domove, hipStream_t st,
                            const long long* step_base) {
   size_t lds = cf_lds_bytes(P.r, P.m, P.D1 + P.D2, P.D1 <= 64 && P.D2 <= 64);
   if (domove == 2)
     lds = std::max(lds, cf_lazy_lds_bytes(P.r, P.m, P.D1 + P.D2, P.rowsU + P.rowsV, nb));
-  switch (P.r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    if (domove == 1)                                                                          \
-      return launch_cf_epoch_t<RR, 1>(P, chains, nchains, step0, bt0, nb, lds, st, step_base); \
-    if (domove == 2)                                                                          \
-      return launch_cf_epoch_t<RR, 2>(P, chains, nchains, step0, bt0, nb, lds, st, step_base); \
-    return launch_cf_epoch_t<RR, 0>(P, chains, nchains, step0, bt0, nb, lds, st, step_base);
-    GPT_CF_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
+  const int dm = domove == 1 || domove == 2 ? domove : 0;
+  return with_rank(P.r, [&](auto R) {
+    return with_value(IntList<0, 1, 2>{}, dm, [&](auto DM) {
+      return launch_big_lds<cf_epoch_kernel<R, DM>>(kMaxLds, dim3(nchains), dim3(kCfNT), lds, st,
+                                                    P, chains, step_base, step0, bt0, nb);
+    });
+  });
 }
 
 // The training ratings of every fold in this epoch's order, once per epoch (the batch kernels
@@ -1479,32 +1437,17 @@ hipError_t launch_cf_move(const CfParams& P, const CfChain* chains, int nchains,
   const int RE = P.r + (P.r & 1);
   const unsigned blocks = (unsigned)(((long long)(P.rowsU + P.rowsV) * (RE / 2) + 255) / 256);
   const dim3 grid = nchains <= 8 ? dim3(8 * blocks) : dim3(blocks, nchains);
-  switch (P.r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    hipLaunchKernelGGL(cf_move_kernel<RR>, grid, dim3(256), 0, st, P, chains, step_base, step, \
-                       nchains);                                                              \
-    break;
-    GPT_CF_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(P.r, [&](auto R) {
+    return launch<cf_move_kernel<R>>(grid, dim3(256), 0, st, P, chains, step_base, step, nchains);
+  });
 }
 
 hipError_t launch_cf_eval(const CfParams& P, const CfChain* chains, int nchains, int nmax,
                           int counter, hipStream_t st) {
   dim3 grid((unsigned)((nmax + 255) / 256), 2, nchains);
-  switch (P.r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    hipLaunchKernelGGL(cf_eval_kernel<RR>, grid, dim3(256), 0, st, P, chains, counter);        \
-    break;
-    GPT_CF_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(P.r, [&](auto R) {
+    return launch<cf_eval_kernel<R>>(grid, dim3(256), 0, st, P, chains, counter);
+  });
 }
 
 }  // namespace gpt

@@ -797,9 +797,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
 }
 
 // ------------------------------------------------------------------------------ host side
-#define GPT_CHAIN_CFGS(X) \
-  X(1, 1) X(1, 2) X(1, 4) X(1, 8) X(2, 1) X(2, 2) X(2, 4) X(2, 8) X(3, 1) X(3, 2) X(3, 4) X(3, 8) \
-  X(4, 1) X(4, 2) X(4, 4) X(4, 8) X(5, 1) X(5, 2) X(5, 4) X(5, 8)
+static_assert(contains(ChainWVs{}, kChainDMax), "the wide U phase has one wave per dimension");
 
 // Static LDS of chain_kernel<R, J, G>: the row staging buffer.
 static int chain_wv(int D) { return D <= 4 ? 4 : kChainDMax; }
@@ -809,15 +807,11 @@ static int chain_J(int n) { return n <= 64 ? 1 : (n <= 128 ? 2 : (n <= 256 ? 4 :
 
 size_t chain_lds_bytes(int n, int D, int r, int Q, int m) {
   (void)n; (void)Q; (void)m;
-  const bool w4 = chain_wv(D) == 4;
-  switch (r) {
-    case 1: return w4 ? ChainLds<1, kChainG, 4>::bytes : ChainLds<1, kChainG>::bytes;
-    case 2: return w4 ? ChainLds<2, kChainG, 4>::bytes : ChainLds<2, kChainG>::bytes;
-    case 3: return w4 ? ChainLds<3, kChainG, 4>::bytes : ChainLds<3, kChainG>::bytes;
-    case 4: return w4 ? ChainLds<4, kChainG, 4>::bytes : ChainLds<4, kChainG>::bytes;
-    case 5: return w4 ? ChainLds<5, kChainG, 4>::bytes : ChainLds<5, kChainG>::bytes;
-    default: return (size_t)1 << 30;
-  }
+  return with_value_or(ChainRanks{}, r, (size_t)1 << 30, [&](auto R) {
+    return with_value_or(ChainWVs{}, chain_wv(D), (size_t)1 << 30, [&](auto WV) {
+      return (size_t)ChainLds<R, kChainG, WV>::bytes;
+    });
+  });
 }
 
 bool chain_supported(int n, int D, int r, int Q, int m, bool langevin, bool stiefel, int max_run) {
@@ -836,21 +830,15 @@ hipError_t launch_chain(const StepParams& P, const ChainDesc* chains, int nchain
   const int J = chain_J(P.n);
   const size_t lds = chain_lds_bytes(P.n, P.D, P.r, P.Q, P.m);
   dim3 grid(nchains), block(64 * P.D);
-#define CASE_W(RR, JJ, WW)                                                                    \
-  if (P.r == RR && J == JJ && (P.D <= 4) == (WW == 4)) {                                      \
-    static std::atomic<uint64_t> attr{0};                                                     \
-    hipError_t e = set_max_lds_once((const void*)chain_kernel<RR, JJ, kChainG, WW>,           \
-                                    (int)(160 * 1024 - chain_static_lds(JJ, WW)), attr);      \
-    if (e != hipSuccess) return e;                                                            \
-    hipLaunchKernelGGL((chain_kernel<RR, JJ, kChainG, WW>), grid, block, lds, st, P, chains, tbase, \
-                       t_local, nsteps);                                                      \
-    return hipGetLastError();                                                                 \
-  }
-#define CASE(RR, JJ) CASE_W(RR, JJ, kChainDMax) CASE_W(RR, JJ, 4)
-  GPT_CHAIN_CFGS(CASE)
-#undef CASE
-#undef CASE_W
-  return hipErrorInvalidValue;
+  return with_value(ChainRanks{}, P.r, [&](auto R) {
+    return with_value(ChainJs{}, J, [&](auto JJ) {
+      return with_value(ChainWVs{}, chain_wv(P.D), [&](auto WV) {
+        return launch_big_lds<chain_kernel<R, JJ, kChainG, WV>>(
+            (int)(kMaxLds - chain_static_lds(JJ, WV)), grid, block, lds, st, P, chains, tbase,
+            t_local, nsteps);
+      });
+    });
+  });
 }
 
 }  // namespace gpt

@@ -314,41 +314,17 @@ __global__ __launch_bounds__(256) void cjoint_update_kernel(const double* __rest
     __hip_atomic_store(status, GPT_ERR_NAN_THETA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int CC, int MODE>
-static hipError_t launch_cj(const CjArgs& A, const CjLayout& L, hipStream_t st) {
-  static std::atomic<uint64_t> latch{0};
-  if (L.bytes > 64 * 1024) {
-    const hipError_t e = set_max_lds_once((const void*)cjoint_eval_kernel<CC, MODE>, (int)kCjLds, latch);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((cjoint_eval_kernel<CC, MODE>), dim3(L.nblk), dim3(kNT), L.bytes, st, A, L);
-  return hipGetLastError();
-}
-
-template <int CC>
-static hipError_t launch_cj_mode(const CjArgs& A, const CjLayout& L, int mode, hipStream_t st) {
-  switch (mode) {
-    case kCjValue: return launch_cj<CC, kCjValue>(A, L, st);
-    case kCjTheta: return launch_cj<CC, kCjTheta>(A, L, st);
-    case kCjFull: return launch_cj<CC, kCjFull>(A, L, st);
-    case kCjScores: return launch_cj<CC, kCjScores>(A, L, st);
-    case kCjFeatures: return launch_cj<CC, kCjFeatures>(A, L, st);
-    default: return hipErrorInvalidValue;
-  }
-}
-
 hipError_t launch_cjoint_eval(const CjArgs& A, const CjLayout& L, int mode, hipStream_t st) {
   if (A.n < 1 || A.n > 1024 || A.D < 1 || A.D > kDMax || A.C < 1 || A.C > 32 || A.N < 1 ||
       L.bytes > kCjLds || L.nblk < 1 || L.nblk > kCjMaxBlocks)
     return hipErrorInvalidValue;
-  switch (L.CC) {
-    case 2: return launch_cj_mode<2>(A, L, mode, st);
-    case 4: return launch_cj_mode<4>(A, L, mode, st);
-    case 8: return launch_cj_mode<8>(A, L, mode, st);
-    case 16: return launch_cj_mode<16>(A, L, mode, st);
-    case 32: return launch_cj_mode<32>(A, L, mode, st);
-    default: return hipErrorInvalidValue;
-  }
+  using Modes = IntList<kCjValue, kCjTheta, kCjFull, kCjScores, kCjFeatures>;
+  return with_value(IntList<2, 4, 8, 16, 32>{}, L.CC, [&](auto CC) {
+    return with_value(Modes{}, mode, [&](auto MODE) {
+      return launch_lds_over_64k<cjoint_eval_kernel<CC, MODE>>((int)kCjLds, dim3(L.nblk), dim3(kNT),
+                                                               L.bytes, st, A, L);
+    });
+  });
 }
 
 hipError_t launch_cjoint_finish(const CjArgs& A, const CjLayout& L, double sigma, bool full,

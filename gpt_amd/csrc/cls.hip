@@ -137,21 +137,6 @@ __global__ __launch_bounds__(kNT) void ntc_chain_kernel(
   for (int e = tid; e < n * C; e += kNT) ch.theta[e] = theta_l[e];
 }
 
-template <int CC>
-static hipError_t launch_ntc_cc(const double* phi, const int32_t* y0, const NtcChain* chains,
-                                int nchains, int n, int N, int C, int m, int nb, long long total,
-                                double decay_rate, int store_every, long long t0, int nsteps,
-                                const NtcLayout& L, hipStream_t st) {
-  static std::atomic<uint64_t> latch{0};
-  if (L.bytes > 64 * 1024) {
-    hipError_t e = set_max_lds_once((const void*)ntc_chain_kernel<CC>, 160 * 1024, latch);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(ntc_chain_kernel<CC>, dim3(nchains), dim3(kNT), L.bytes, st, phi, y0, chains,
-                     n, N, C, m, nb, total, decay_rate, store_every, t0, nsteps, L);
-  return hipGetLastError();
-}
-
 hipError_t launch_ntc_chain(const double* phi, const int32_t* y0, const NtcChain* chains,
                             int nchains, int n, int N, int C, int m, int nb, long long total,
                             double decay_rate, int store_every, long long t0, int nsteps,
@@ -159,17 +144,12 @@ hipError_t launch_ntc_chain(const double* phi, const int32_t* y0, const NtcChain
   const NtcLayout L = ntc_layout(n, C, m);
   if (C < 1 || C > 32 || L.bytes > 160 * 1024 || nchains < 1 || store_every < 1)
     return hipErrorInvalidValue;
-#define NTC_GO(K)                                                                             \
-  return launch_ntc_cc<K>(phi, y0, chains, nchains, n, N, C, m, nb, total, decay_rate,        \
-                          store_every, t0, nsteps, L, st)
-  switch (L.CC) {
-    case 2: NTC_GO(2);
-    case 4: NTC_GO(4);
-    case 8: NTC_GO(8);
-    case 16: NTC_GO(16);
-    default: NTC_GO(32);
-  }
-#undef NTC_GO
+  const int cc = contains(IntList<2, 4, 8, 16>{}, L.CC) ? L.CC : 32;    // C rounded up
+  return with_value(IntList<2, 4, 8, 16, 32>{}, cc, [&](auto CC) {
+    return launch_lds_over_64k<ntc_chain_kernel<CC>>(
+        kMaxLds, dim3(nchains), dim3(kNT), L.bytes, st, phi, y0, chains, n, N, C, m, nb, total,
+        decay_rate, store_every, t0, nsteps, L);
+  });
 }
 
 // ------------------------------------------------------------------ scores of full-theta samples

@@ -2,10 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <atomic>
 #include <string>
 #include <vector>
 #include "gpt_common.h"
+#include "launch_util.h"
 #include "../../include/gptsgld.h"
 
 namespace gpt {
@@ -143,20 +143,6 @@ GPT_HD StepLayout step_layout(int n, int D, int r, int Q, int m) {
   return L;
 }
 
-// Raise a kernel's dynamic-LDS limit once per device.  Thread-safe: host threads (one per GPU, or
-// several sessions) may race to set the same attribute, which is idempotent; the latch only
-// skips the call once a device has it.
-inline hipError_t set_max_lds_once(const void* fn, int bytes, std::atomic<uint64_t>& latch) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (latch.load(std::memory_order_acquire) & bit) return hipSuccess;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) latch.fetch_or(bit, std::memory_order_acq_rel);
-  return e;
-}
-
 // Host helpers (api_core.hip / api_session.hip / api_pred.hip; sgld.hip, pred.hip)
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
@@ -198,7 +184,6 @@ size_t epoch_order_ws_ints(int N, int nchains);
 hipError_t launch_epoch_order(const ChainDesc* chains, int nchains, int N, int nb,
                               long long total_steps, const long long* tbase, int t_local,
                               int e_fixed, int32_t* ws, hipStream_t st);
-bool rank_supported(int r);
 // vphase_cols' tables for a session (step_layout(n, D, r, Q, m).vcols): (D+1)·Q·16 ints
 void vphase_cols_tables(const std::vector<int32_t>& I0, int n, int D, int r, int Q, int m,
                         std::vector<int32_t>& out);
@@ -316,7 +301,6 @@ struct CfChain {
 
 size_t cf_lds_bytes(int r, int m, int nfeat, bool masks);
 size_t cf_lazy_lds_bytes(int r, int m, int nfeat, int rows, int nb);
-bool cf_rank_supported(int r);
 hipError_t launch_cf_epoch(const CfParams& P, const CfChain* chains, int nchains, long long step0,
                            int bt0, int nb, int domove, hipStream_t st,
                            const long long* step_base = nullptr);

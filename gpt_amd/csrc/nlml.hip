@@ -469,12 +469,9 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   GPT_HIPCHK(hipGetLastError());
   mark();
   if (want_grad) {
-    static std::atomic<uint64_t> attr{0};
-    GPT_HIPCHK(set_max_lds_once((const void*)nlml_trinv_kernel, 160 * 1024, attr));
     GPT_HIPCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
-    hipLaunchKernelGGL(nlml_trinv_kernel, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
-                       trinv_lds_bytes(n), st, h->A, n, h->Xt);
-    GPT_HIPCHK(hipGetLastError());
+    GPT_HIPCHK(launch_big_lds<nlml_trinv_kernel>(kMaxLds, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
+                                                 trinv_lds_bytes(n), st, h->A, n, h->Xt));
     mark();
     GPT_HIPCHK(dense_syrk(h->Xt, n, n, 1.0, 0.0, h->P, st));
     hipLaunchKernelGGL(nlml_mirror_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256),

@@ -130,18 +130,13 @@ hipError_t launch_epoch_order(const ChainDesc* chains, int nchains, int N, int n
                               long long total_steps, const long long* tbase, int t_local,
                               int e_fixed, int32_t* ws, hipStream_t st) {
   if (N < 1) return hipSuccess;
-  if (epoch_order_in_lds(N)) {
-    static std::atomic<uint64_t> attr{0};
-    hipError_t e = set_max_lds_once((const void*)epoch_order_kernel<true>, kOrdLdsMax, attr);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(epoch_order_kernel<true>, dim3(nchains), dim3(kOrdNT), (size_t)12 * N, st,
-                       chains, N, nb, total_steps, tbase, t_local, e_fixed, nullptr);
-  } else {
-    if (!ws) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(epoch_order_kernel<false>, dim3(nchains), dim3(kOrdNT), 0, st, chains, N,
-                       nb, total_steps, tbase, t_local, e_fixed, ws);
-  }
-  return hipGetLastError();
+  if (epoch_order_in_lds(N))
+    return launch_big_lds<epoch_order_kernel<true>>(kOrdLdsMax, dim3(nchains), dim3(kOrdNT),
+                                                    (size_t)12 * N, st, chains, N, nb, total_steps,
+                                                    tbase, t_local, e_fixed, nullptr);
+  if (!ws) return hipErrorInvalidValue;
+  return launch<epoch_order_kernel<false>>(dim3(nchains), dim3(kOrdNT), 0, st, chains, N, nb,
+                                           total_steps, tbase, t_local, e_fixed, ws);
 }
 
 }  // namespace gpt

@@ -196,8 +196,6 @@ __global__ __launch_bounds__(kNT) void mean_sse_kernel(const double* __restrict_
   if (threadIdx.x == 0) sse_out[s < S ? 1 + s : 0] = tot;
 }
 
-#define GPT_RANKS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(15) X(16) X(20)
-
 // ---- stacked-sample prediction on the fp64 matrix cores (GPT_SGLD.jl:233-243 over S samples)
 //
 // phidotU of S samples at once is one GEMM per dimension k:
@@ -635,28 +633,15 @@ static hipError_t launch_pred_gemm(const double* Us, const double* phitest, int 
   return hipGetLastError();
 }
 
-template <int NN>
-static hipError_t launch_vphase_pairs(const double* w, const double* T, const int32_t* offp, int D,
-                                      int r, long long rows, int Q, double* fhat, int Sc,
-                                      long long ldF, size_t plds, hipStream_t st) {
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = set_max_lds_once((const void*)pred_vphase_pairs_kernel<NN>, 160 * 1024, attr);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(pred_vphase_pairs_kernel<NN>, dim3((unsigned)((rows + 63) / 64), Sc),
-                     dim3(64 * kPairWaves), plds, st, w, T, offp, D, r, rows, Q, fhat, ldF);
-  return hipGetLastError();
-}
-
+using PairNTs = IntList<1, 2, 3, 4, 5, 6, 7, 8>;   // pair tables per entry
 static hipError_t vphase_pairs(int NTp, const double* w, const double* T, const int32_t* offp,
                                int D, int r, long long rows, int Q, double* fhat, int Sc,
                                long long ldF, size_t plds, hipStream_t st) {
-  switch (NTp) {
-#define PCASE(NN) \
-    case NN: return launch_vphase_pairs<NN>(w, T, offp, D, r, rows, Q, fhat, Sc, ldF, plds, st);
-    PCASE(1) PCASE(2) PCASE(3) PCASE(4) PCASE(5) PCASE(6) PCASE(7) PCASE(8)
-#undef PCASE
-    default: return hipErrorInvalidValue;
-  }
+  return with_value(PairNTs{}, NTp, [&](auto NN) {
+    return launch_big_lds<pred_vphase_pairs_kernel<NN>>(
+        kMaxLds, dim3((unsigned)((rows + 63) / 64), Sc), dim3(64 * kPairWaves), plds, st, w, T,
+        offp, D, r, rows, Q, fhat, ldF);
+  });
 }
 
 // Which V-phase kernel the last prediction call on this thread launched (gpt_pred_last_vphase):
@@ -682,16 +667,13 @@ void pred_last_route(int32_t* out, int len) {
 // its LDS fits a CU (as many workgroups as the LDS lets every CU hold), else the
 // one-tile-per-workgroup kernel.
 constexpr int kRowsPfWaves = 16;
+using RowsPfDs = IntList<2, 3, 4, 5, 6, 7, 8, 9, 10, 12>;   // the D the kernel is specialised for
 template <int DD, int NPW, int NW = kRowsPfWaves>
 static hipError_t launch_rows_pf(const double* w, const double* T, const int32_t* offs, int D, int r,
                                  long long Ntest, int Q, double* fhat, int Sc, hipStream_t st) {
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e =
-      set_max_lds_once((const void*)pred_vphase_rows_pf_kernel<DD, NW, NPW>, 160 * 1024, attr);
-  if (e != hipSuccess) return e;
   g_pred_vphase = 1;
   int dev = 0, cus = 0;
-  e = hipGetDevice(&dev);
+  hipError_t e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (e != hipSuccess) return e;
   const size_t lds = 8 * (size_t)D * r * 64 + 8 * (size_t)NW * 64 + 4 * (((size_t)Q * D + 3) & ~3) +
@@ -702,9 +684,8 @@ static hipError_t launch_rows_pf(const double* w, const double* T, const int32_t
   g_pred_route.tdim = DD;
   g_pred_route.npw = NPW;
   g_pred_route.grid = (int32_t)grid;
-  hipLaunchKernelGGL((pred_vphase_rows_pf_kernel<DD, NW, NPW>), dim3(grid), dim3(64 * NW), lds, st,
-                     w, T, offs, D, r, Ntest, Q, fhat, Sc);
-  return hipGetLastError();
+  return launch_big_lds<pred_vphase_rows_pf_kernel<DD, NW, NPW>>(
+      kMaxLds, dim3(grid), dim3(64 * NW), lds, st, w, T, offs, D, r, Ntest, Q, fhat, Sc);
 }
 
 static hipError_t launch_vphase_rows(const double* w, const double* T, const int32_t* offs, int D,
@@ -716,27 +697,24 @@ static hipError_t launch_vphase_rows(const double* w, const double* T, const int
                         4 * (((size_t)Q * D + 3) & ~(size_t)3) + 8 * (size_t)Q;
   if (D * r <= kRowsPfWaves * 16 && pf_lds <= 160 * 1024) {
     // rows per wave: 10 (D·r ≤ 160: kin40kExperiment.jl's D = 8, r = 20) or 16
+    // (DD = D where the kernel is instantiated for that D, else its run-time-D form DD = 0)
     if (D * r <= kRowsPfWaves * 10) {
-      switch (D) {
-#define DCASE(X) case X: return launch_rows_pf<X, 10>(w, T, offs, D, r, Ntest, Q, fhat, Sc, st);
-        DCASE(2) DCASE(3) DCASE(4) DCASE(5) DCASE(6) DCASE(7) DCASE(8) DCASE(9) DCASE(10) DCASE(12)
-#undef DCASE
-        default: return launch_rows_pf<0, 10>(w, T, offs, D, r, Ntest, Q, fhat, Sc, st);
-      }
+      bool fixed = false;
+      const hipError_t e = with_value(RowsPfDs{}, D, [&](auto DD) {
+        fixed = true;
+        return launch_rows_pf<DD, 10>(w, T, offs, D, r, Ntest, Q, fhat, Sc, st);
+      });
+      if (fixed) return e;
+      return launch_rows_pf<0, 10>(w, T, offs, D, r, Ntest, Q, fhat, Sc, st);
     }
     return launch_rows_pf<0, 16>(w, T, offs, D, r, Ntest, Q, fhat, Sc, st);
-  }
-  if (rlds > 64 * 1024) {
-    static std::atomic<uint64_t> attr{0};
-    const hipError_t e = set_max_lds_once((const void*)pred_vphase_rows_kernel, 160 * 1024, attr);
-    if (e != hipSuccess) return e;
   }
   g_pred_vphase = 2;
   g_pred_route.tdim = g_pred_route.npw = 0;
   g_pred_route.grid = (int32_t)((Ntest + 63) / 64);
-  hipLaunchKernelGGL(pred_vphase_rows_kernel, dim3((unsigned)((Ntest + 63) / 64), Sc),
-                     dim3(64 * kRowsWaves), rlds, st, w, T, offs, D, r, Ntest, Q, fhat);
-  return hipGetLastError();
+  const dim3 grid((unsigned)((Ntest + 63) / 64), Sc), block(64 * kRowsWaves);
+  return launch_lds_over_64k<pred_vphase_rows_kernel>(kMaxLds, grid, block, rlds, st, w, T, offs,
+                                                      D, r, Ntest, Q, fhat);
 }
 
 // The prediction's pass buffers come from a private stream-ordered pool per device that keeps its
@@ -896,20 +874,10 @@ static hipError_t launch_pred_direct(const double* w, const double* U, const int
   if (Ntest <= 0 || S <= 0) return hipSuccess;
   const size_t lds = pred_lds_bytes(n, D, r, Q);
   dim3 grid((unsigned)((Ntest + 63) / 64), S);
-  switch (r) {
-#define CASE(RR)                                                                             \
-  case RR: {                                                                                 \
-    static std::atomic<uint64_t> attr{0};                                                         \
-    hipError_t e = set_max_lds_once((const void*)pred_kernel<RR>, 160 * 1024, attr);              \
-    if (e != hipSuccess) return e;                                                                \
-    hipLaunchKernelGGL(pred_kernel<RR>, grid, dim3(kNT), lds, st, w, U, I0, phitest, n, D,   \
-                       Ntest, Q, fhat);                                                      \
-  } break;
-    GPT_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(r, [&](auto R) {
+    return launch_big_lds<pred_kernel<R>>(kMaxLds, grid, dim3(kNT), lds, st, w, U, I0, phitest, n,
+                                          D, Ntest, Q, fhat);
+  });
 }
 
 // Prediction over S stored samples: the MFMA path (stacked-sample GEMM + V-phase) by default;
@@ -938,20 +906,10 @@ hipError_t launch_pred_x(const double* w, const double* U, const int32_t* I0, co
   if (Ntest <= 0 || S <= 0) return hipSuccess;
   const size_t lds = pred_x_lds_bytes(n, D, r, Q);
   dim3 grid((unsigned)((Ntest + 63) / 64), S);
-  switch (r) {
-#define CASE(RR)                                                                             \
-  case RR: {                                                                                 \
-    static std::atomic<uint64_t> attr{0};                                                         \
-    hipError_t e = set_max_lds_once((const void*)pred_x_kernel<RR>, 160 * 1024, attr);            \
-    if (e != hipSuccess) return e;                                                                \
-    hipLaunchKernelGGL(pred_x_kernel<RR>, grid, dim3(kNT), lds, st, w, U, I0, X, ls, Z, bfe, c, \
-                       n, D, Ntest, Q, fhat);                                                \
-  } break;
-    GPT_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(r, [&](auto R) {
+    return launch_big_lds<pred_x_kernel<R>>(kMaxLds, grid, dim3(kNT), lds, st, w, U, I0, X, ls, Z,
+                                            bfe, c, n, D, Ntest, Q, fhat);
+  });
 }
 
 hipError_t launch_mean_rmse(const double* fhat, const double* ytest, long long Ntest, int S,

@@ -678,8 +678,6 @@ __global__ void advance_kernel(long long* tbase, long long by) {
   if (threadIdx.x == 0 && blockIdx.x == 0) tbase[0] += by;
 }
 
-#define GPT_RANKS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(15) X(16) X(20)
-
 void vphase_cols_tables(const std::vector<int32_t>& I0, int n, int D, int r, int Q, int m,
                         std::vector<int32_t>& out) {
   const StepLayout L = step_layout(n, D, r, Q, m);
@@ -699,65 +697,34 @@ void vphase_cols_tables(const std::vector<int32_t>& I0, int n, int D, int r, int
     }
 }
 
-bool rank_supported(int r) {
-  switch (r) {
-#define CASE(RR) case RR:
-    GPT_RANKS(CASE)
-#undef CASE
-    return true;
-    default: return false;
-  }
-}
-
 hipError_t launch_temp_init(const StepParams& P, const ChainDesc* chains, int nchains,
                             const long long* tbase, hipStream_t st) {
   const StepLayout L = step_layout(P.n, P.D, P.r, P.Q, P.m);
-  dim3 grid(P.D, nchains);
-  switch (P.r) {
-#define CASE(RR)                                                                           \
-  case RR:                                                                                 \
-    hipLaunchKernelGGL(temp_init_kernel<RR>, grid, dim3(kNT), L.bytes, st, P, chains, tbase, 0); \
-    break;
-    GPT_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(P.r, [&](auto R) {
+    return launch<temp_init_kernel<R>>(dim3(P.D, nchains), dim3(kNT), L.bytes, st, P, chains,
+                                       tbase, 0);
+  });
 }
 
 hipError_t launch_step(const StepParams& P, const ChainDesc* chains, int nchains,
                        const long long* tbase, int t_local, hipStream_t st) {
   const StepLayout L = step_layout(P.n, P.D, P.r, P.Q, P.m);
-  dim3 grid(P.D + 1, nchains);
-  switch (P.r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    hipLaunchKernelGGL(sgld_step_kernel<RR>, grid, dim3(kNT), L.bytes, st, P, chains, tbase,  \
-                       t_local, 0);                                                           \
-    break;
-    GPT_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(P.r, [&](auto R) {
+    return launch<sgld_step_kernel<R>>(dim3(P.D + 1, nchains), dim3(kNT), L.bytes, st, P, chains,
+                                       tbase, t_local, 0);
+  });
 }
 
 hipError_t launch_step_rms(const StepParams& P, const ChainDesc* chains, int nchains,
                            const long long* tbase, int t_local, hipStream_t st) {
   const StepLayout L = step_layout(P.n, P.D, P.r, P.Q, P.m);
-  switch (P.r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    hipLaunchKernelGGL(sgld_step_kernel<RR>, dim3(1, nchains), dim3(kNT), L.bytes, st, P,     \
-                       chains, tbase, t_local, P.D);                                          \
-    hipLaunchKernelGGL(sgld_step_kernel<RR>, dim3(P.D, nchains), dim3(kNT), L.bytes, st, P,   \
-                       chains, tbase, t_local, 0);                                            \
-    break;
-    GPT_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(P.r, [&](auto R) {
+    hipLaunchKernelGGL(sgld_step_kernel<R>, dim3(1, nchains), dim3(kNT), L.bytes, st, P, chains,
+                       tbase, t_local, P.D);
+    hipLaunchKernelGGL(sgld_step_kernel<R>, dim3(P.D, nchains), dim3(kNT), L.bytes, st, P, chains,
+                       tbase, t_local, 0);
+    return hipGetLastError();
+  });
 }
 
 // GPT_SGLDERMw (GPT_SGLD.jl:1065-1118): U never moves, so each step is temp of its batch with the
@@ -765,61 +732,53 @@ hipError_t launch_step_rms(const StepParams& P, const ChainDesc* chains, int nch
 hipError_t launch_step_wonly(const StepParams& P, const ChainDesc* chains, int nchains,
                              const long long* tbase, int t_local, hipStream_t st) {
   const StepLayout L = step_layout(P.n, P.D, P.r, P.Q, P.m);
-  switch (P.r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    hipLaunchKernelGGL(temp_init_kernel<RR>, dim3(P.D, nchains), dim3(kNT), L.bytes, st, P,   \
-                       chains, tbase, t_local);                                               \
-    hipLaunchKernelGGL(sgld_step_kernel<RR>, dim3(1, nchains), dim3(kNT), L.bytes, st, P,     \
-                       chains, tbase, t_local, P.D);                                          \
-    break;
-    GPT_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(P.r, [&](auto R) {
+    hipLaunchKernelGGL(temp_init_kernel<R>, dim3(P.D, nchains), dim3(kNT), L.bytes, st, P, chains,
+                       tbase, t_local);
+    hipLaunchKernelGGL(sgld_step_kernel<R>, dim3(1, nchains), dim3(kNT), L.bytes, st, P, chains,
+                       tbase, t_local, P.D);
+    return hipGetLastError();
+  });
 }
 
 // GPTclassification: the class-fhat pass (one workgroup per class) then the step of every class.
 hipError_t launch_step_cls(const StepParams& P, const ChainDesc* chains, int nchains,
                            const long long* tbase, int t_local, hipStream_t st) {
   const StepLayout L = step_layout(P.n, P.D, P.r, P.Q, P.m);
-  switch (P.r) {
-#define CASE(RR)                                                                              \
-  case RR:                                                                                    \
-    hipLaunchKernelGGL(sgld_step_kernel<RR>, dim3(1, nchains), dim3(kNT), L.bytes, st, P,     \
-                       chains, tbase, t_local, P.D + 1);                                      \
-    hipLaunchKernelGGL(sgld_step_kernel<RR>, dim3(P.D + 1, nchains), dim3(kNT), L.bytes, st,  \
-                       P, chains, tbase, t_local, 0);                                         \
-    break;
-    GPT_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(P.r, [&](auto R) {
+    hipLaunchKernelGGL(sgld_step_kernel<R>, dim3(1, nchains), dim3(kNT), L.bytes, st, P, chains,
+                       tbase, t_local, P.D + 1);
+    hipLaunchKernelGGL(sgld_step_kernel<R>, dim3(P.D + 1, nchains), dim3(kNT), L.bytes, st, P,
+                       chains, tbase, t_local, 0);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_advance(long long* tbase, long long by, hipStream_t st) {
-  hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, tbase, by);
-  return hipGetLastError();
+  return launch<advance_kernel>(dim3(1), dim3(64), 0, st, tbase, by);
 }
 
-// Opt the kernels into >64 KiB of dynamic LDS once per process.
+// Opt the grid kernels of every rank into >64 KiB of dynamic LDS once per device (eagerly, at
+// session creation: hipFuncSetAttribute must stay out of stream capture).  Their launchers above
+// rely on it: launch<> raises no limit.
+template <int... Rs> static hipError_t set_lds_limits_of(IntList<Rs...>) {
+  const void* const fns[] = {(const void*)sgld_step_kernel<Rs>...,
+                             (const void*)temp_init_kernel<Rs>...};
+  hipError_t e = hipSuccess;
+  for (const void* fn : fns)
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+  return e;
+}
+
 hipError_t set_lds_limits() {
   static std::atomic<uint64_t> done{0};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   if (done.load(std::memory_order_acquire) & (1ull << (dev & 63))) return hipSuccess;
-#define CASE(RR)                                                                              \
-  e = hipFuncSetAttribute((const void*)sgld_step_kernel<RR>,                                   \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);            \
-  if (e != hipSuccess) return e;                                                              \
-  e = hipFuncSetAttribute((const void*)temp_init_kernel<RR>,                                   \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);            \
+  e = set_lds_limits_of(Ranks{});
   if (e != hipSuccess) return e;
-  GPT_RANKS(CASE)
-#undef CASE
   done.fetch_or(1ull << (dev & 63), std::memory_order_acq_rel);
   return e;
 }

@@ -540,22 +540,13 @@ void dense_trsv(const double* M, int p, double* x, int trans, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------ host side
-#define GPT_TGP_RANKS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(15) X(16) X(20)
-
 static hipError_t launch_tgp_temp(const double* U, const double* b, int n, int D, long long N,
                                   int r, int d0, int nd, double* temp, hipStream_t st) {
   const size_t lds = 8 * (size_t)r * (((n + 63) / 64) * 64 + 1);
   dim3 grid((unsigned)((N + 63) / 64), nd);
-  switch (r) {
-#define CASE(RR)                                                                             \
-  case RR:                                                                                   \
-    hipLaunchKernelGGL(tgp_temp_kernel<RR>, grid, dim3(kNT), lds, st, U, b, n, D, N, d0, temp); \
-    break;
-    GPT_TGP_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(r, [&](auto R) {
+    return launch<tgp_temp_kernel<R>>(grid, dim3(kNT), lds, st, U, b, n, D, N, d0, temp);
+  });
 }
 
 static unsigned nblk(long long cnt, int t) { return (unsigned)((cnt + t - 1) / t); }
@@ -873,38 +864,19 @@ static hipError_t launch_gmc_kick(const double* U, double* mom, const double* gU
                                   int D, int r, int init, uint64_t seed, uint32_t epoch,
                                   hipStream_t st) {
   const size_t lds = gmc_kick_lds(n, r);
-  switch (r) {
-#define CASE(RR)                                                                              \
-  case RR: {                                                                                  \
-    static std::atomic<uint64_t> attr{0};                                                         \
-    hipError_t e = set_max_lds_once((const void*)gmc_kick_kernel<RR>, 160 * 1024, attr);          \
-    if (e != hipSuccess) return e;                                                                \
-    hipLaunchKernelGGL(gmc_kick_kernel<RR>, dim3(D), dim3(kNT), lds, st, U, mom, gU, c, n, init, \
-                       seed, epoch);                                                          \
-  } break;
-    GPT_TGP_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(r, [&](auto R) {
+    return launch_big_lds<gmc_kick_kernel<R>>(kMaxLds, dim3(D), dim3(kNT), lds, st, U, mom, gU, c,
+                                              n, init, seed, epoch);
+  });
 }
 
 static hipError_t launch_gmc_geod(double* U, double* mom, double t, int n, int D, int r,
                                   int32_t* status, hipStream_t st) {
   const size_t lds = gmc_geod_lds(n, r);
-  switch (r) {
-#define CASE(RR)                                                                              \
-  case RR: {                                                                                  \
-    static std::atomic<uint64_t> attr{0};                                                         \
-    hipError_t e = set_max_lds_once((const void*)gmc_geod_kernel<RR>, 160 * 1024, attr);          \
-    if (e != hipSuccess) return e;                                                                \
-    hipLaunchKernelGGL(gmc_geod_kernel<RR>, dim3(D), dim3(kNT), lds, st, U, mom, t, n, status); \
-  } break;
-    GPT_TGP_RANKS(CASE)
-#undef CASE
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_rank(r, [&](auto R) {
+    return launch_big_lds<gmc_geod_kernel<R>>(kMaxLds, dim3(D), dim3(kNT), lds, st, U, mom, t, n,
+                                              status);
+  });
 }
 
 // Full-data gradients at (w, U): fhat/res, gw, gU (all device; scratch temp (D·r·N), V (Q·N),

@@ -1091,8 +1091,6 @@ __global__ __launch_bounds__(64, 1) void wv_dim_kernel(StepParams P,
 }
 
 // ------------------------------------------------------------------------------------ host side
-#define GPT_WV_CFGS(X) X(6) X(8) X(10) X(12) X(15) X(16) X(20)
-
 static int wv_J(int n) { return n <= 64 ? 1 : (n <= 128 ? 2 : (n <= 192 ? 3 : (n <= 256 ? 4 : 0))); }
 
 // + the U noise's two 16-entry (sin, cos) tables (fm_sincos_tab2) past everything else
@@ -1103,11 +1101,7 @@ size_t wv_vphase_lds_bytes(int D, int r, int Q, int m) {
 
 bool wave_supported(int n, int D, int r, int Q, int m, bool langevin, bool stiefel) {
   if (!langevin || !stiefel) return false;        // SGD / Euclidean variants: grid engine
-  bool inst = false;
-#define CASE(RR) inst |= (r == RR);
-  GPT_WV_CFGS(CASE)
-#undef CASE
-  if (!inst || wv_J(n) == 0 || m > kWvMaxM || D < 1 || D > kDMax) return false;
+  if (!contains(WaveRanks{}, r) || wv_J(n) == 0 || m > kWvMaxM || D < 1 || D > kDMax) return false;
   if (3 * r * r > n * r) return false;            // expm(−tA)'s scratch below the Grams
   if ((long long)D * r * m >= 65536 || Q >= 65536) return false;   // 16-bit V-phase tables
   return wv_vphase_lds_bytes(D, r, Q, m) <= 160 * 1024 && wv_dim_lds_bytes(n, r, m) <= 160 * 1024;
@@ -1139,33 +1133,18 @@ hipError_t launch_wave(const StepParams& P, const ChainDesc* chains, int nchains
   const int J = wv_J(P.n);
   const size_t ldsv = wv_vphase_lds_bytes(P.D, P.r, P.Q, P.m);
   const size_t ldsd = wv_dim_lds_bytes(P.n, P.r, P.m);
-#define CASE_J(RR, JJ)                                                                        \
-  if (J == JJ) {                                                                              \
-    static std::atomic<uint64_t> attr{0};                                                     \
-    hipError_t e = set_max_lds_once((const void*)wv_dim_kernel<RR, JJ>, 160 * 1024, attr);    \
-    if (e != hipSuccess) return e;                                                            \
-    hipLaunchKernelGGL((wv_dim_kernel<RR, JJ>), dim3(nchains * P.D), dim3(64), ldsd, st, P,   \
-                       chains, tbase, t_local, nchains, init ? 1 : 0);                        \
-    return hipGetLastError();                                                                 \
-  }
-#define CASE(RR)                                                                              \
-  if (P.r == RR) {                                                                            \
-    if (!init) {                                                                              \
-      static std::atomic<uint64_t> attr{0};                                                   \
-      hipError_t e = set_max_lds_once((const void*)wv_vphase_kernel<RR>, 160 * 1024, attr);   \
-      if (e != hipSuccess) return e;                                                          \
-      hipLaunchKernelGGL((wv_vphase_kernel<RR>), dim3(nchains), dim3(512), ldsv, st, P,       \
-                         chains, tbase, t_local);                                             \
-      e = hipGetLastError();                                                                  \
-      if (e != hipSuccess) return e;                                                          \
-    }                                                                                         \
-    CASE_J(RR, 1) CASE_J(RR, 2) CASE_J(RR, 3) CASE_J(RR, 4)                                   \
-    return hipErrorInvalidValue;                                                              \
-  }
-  GPT_WV_CFGS(CASE)
-#undef CASE
-#undef CASE_J
-  return hipErrorInvalidValue;
+  return with_value(WaveRanks{}, P.r, [&](auto R) {
+    if (!init) {
+      const hipError_t e = launch_big_lds<wv_vphase_kernel<R>>(
+          kMaxLds, dim3(nchains), dim3(512), ldsv, st, P, chains, tbase, t_local);
+      if (e != hipSuccess) return e;
+    }
+    return with_value(WaveJs{}, J, [&](auto JJ) {
+      return launch_big_lds<wv_dim_kernel<R, JJ>>(kMaxLds, dim3(nchains * P.D), dim3(64), ldsd, st,
+                                                  P, chains, tbase, t_local, nchains,
+                                                  init ? 1 : 0);
+    });
+  });
 }
 
 }  // namespace gpt
@@ -1229,17 +1208,19 @@ static hipError_t expm_check_launch(int count, const double* A, double* E, int32
 // hipErrorInvalidValue for a (mode, nn) pair that is not instantiated
 hipError_t launch_expm_check(int nn, int count, const double* A, double* E, int32_t* bad, int mode,
                              hipStream_t st, long long* stamps) {
-#define CASE(MODEV, NNV) \
-  if (mode == MODEV && nn == NNV) return expm_check_launch<NNV, MODEV>(count, A, E, bad, st, stamps);
-#define GEOD_SIZES(M) CASE(M, 12) CASE(M, 16) CASE(M, 20) CASE(M, 24) CASE(M, 30) CASE(M, 32) CASE(M, 40)
-  CASE(0, 6) CASE(0, 8) CASE(0, 10) CASE(0, 15) GEOD_SIZES(0)
-  CASE(1, 1) CASE(1, 2) CASE(1, 3) CASE(1, 4) CASE(1, 5) CASE(1, 6) CASE(1, 8) CASE(1, 10)
-  CASE(1, 15) GEOD_SIZES(1)
-  GEOD_SIZES(2)
-  CASE(3, 40)
-  GEOD_SIZES(4)
-#undef GEOD_SIZES
-#undef CASE
-  return hipErrorInvalidValue;
+  const auto go = [&](auto MODE, auto sizes) {
+    return with_value(sizes, nn, [&](auto NN) {
+      return expm_check_launch<NN, MODE>(count, A, E, bad, st, stamps);
+    });
+  };
+  using Geod = IntList<12, 16, 20, 24, 30, 32, 40>;      // 2r of the wave ranks
+  switch (mode) {
+    case 0: return go(Int<0>{}, IntList<6, 8, 10, 12, 15, 16, 20, 24, 30, 32, 40>{});
+    case 1: return go(Int<1>{}, IntList<1, 2, 3, 4, 5, 6, 8, 10, 12, 15, 16, 20, 24, 30, 32, 40>{});
+    case 2: return go(Int<2>{}, Geod{});
+    case 3: return go(Int<3>{}, IntList<40>{});
+    case 4: return go(Int<4>{}, Geod{});
+    default: return hipErrorInvalidValue;
+  }
 }
 }  // namespace gpt

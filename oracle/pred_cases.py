@@ -139,7 +139,7 @@ def expected_route(shape, rows=False):
     return ROWS, 0, 0
 
 
-FIXED_D = (2, 3, 4, 5, 6, 7, 8, 9, 10, 12)            # the DCASE list of launch_vphase_rows
+FIXED_D = (2, 3, 4, 5, 6, 7, 8, 9, 10, 12)            # pred.hip's RowsPfDs (launch_vphase_rows)
 
 
 def rows_pf_grid(shape, cus):

@@ -18,6 +18,11 @@ def _pred_source():
     return open(os.path.join(ROOT, "gpt_amd", "csrc", "pred.hip")).read()
 
 
+def _int_list(src, name):
+    """The values of `using <name> = IntList<...>;` in the source."""
+    return tuple(int(v) for v in re.search(r"using %s = IntList<([^>]*)>" % name, src).group(1).split(","))
+
+
 def test_fixture_holds_every_case():
     st = PC._stored()
     assert os.path.getsize(PC.GOLDEN) < 1 << 20
@@ -83,8 +88,7 @@ def test_table_routes_are_the_dispatchs():
     for c in PC.CASES:
         assert (c.kind, c.tdim, c.npw) == PC.expected_route(c.shape, c.rows), PC.case_id(c)
     src = _pred_source()
-    dcases = re.search(r"DCASE\(2\)[^\n]*", src).group(0)
-    assert tuple(int(v) for v in re.findall(r"DCASE\((\d+)\)", dcases)) == PC.FIXED_D
+    assert _int_list(src, "RowsPfDs") == PC.FIXED_D
     assert PC.gemm_tiles((6, 3, 300, 2, 6, 2)) == 9 and PC.gemm_tiles((6, 1, 20, 2, 2, 1)) == 1
     assert any(PC.gemm_tiles(c.shape) % 8 for c in PC.CASES)
     for s in PC.DIRECT_SHAPES:
@@ -96,10 +100,7 @@ def test_table_reaches_every_instantiation():
     every NT of vphase_pairs' switch and the one-tile rows kernel are in the table, but for the
     ones PC.HELD_ELSEWHERE names an existing test for."""
     src = _pred_source()
-    dcases = re.search(r"DCASE\(2\)[^\n]*", src).group(0)
-    dds = {int(v) for v in re.findall(r"DCASE\((\d+)\)", dcases)}
-    pcases = re.search(r"PCASE\(1\)[^\n]*", src).group(0)
-    nts = {int(v) for v in re.findall(r"PCASE\((\d+)\)", pcases)}
+    dds, nts = set(_int_list(src, "RowsPfDs")), set(_int_list(src, "PairNTs"))
     assert dds == {2, 3, 4, 5, 6, 7, 8, 9, 10, 12} and nts == set(range(1, 9))
     have_dd = {c.tdim for c in PC.CASES if c.kind == PC.ROWS_PF and c.tdim > 0}
     have_nt = {c.tdim for c in PC.CASES if c.kind == PC.PAIRS}
