@@ -83,6 +83,7 @@ SIGNATURES = {
                                     C.c_uint32, C.c_uint32, P_D, P_U32]),
     "gpt_debug_gaussian_draw": (C.c_int, [C.c_int32, P_D, P_D, C.c_uint64, C.c_uint32, C.c_uint32,
                                           C.c_uint32, P_D, P_I32]),
+    "gpt_debug_cf_init": (C.c_int, [P_D, C.c_int64, P_D, C.c_int64, C.c_int64]),
     "gpt_pred_trim_pool": (C.c_int, []),
     "gpt_cf_last_timing": (C.c_int, [P_D, P_D, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gpt_cf_last_mode": (C.c_int, [C.POINTER(C.c_int32)]),

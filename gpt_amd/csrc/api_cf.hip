@@ -79,6 +79,10 @@ static thread_local int32_t g_cf_mode = 0;      // gpt_cf_last_mode
 // GPTSGLD_CF_STAMPS=1: per-phase s_memtime of fold 0's first epoch (gpt_cf_last_stamps)
 static thread_local std::vector<long long> g_cf_stamps;
 
+// gpt_debug_cf_init's one-shot initial state of the next CF SGD run on this thread
+struct CfInject { bool armed = false; int64_t rowsU = 0, rowsV = 0, r = 0; std::vector<double> U, V; };
+static thread_local CfInject g_cf_inject;
+
 static int cf_sgd_run(
     const char* name, std::vector<CfFold>& folds, const double* UserData, int64_t n1, int64_t D1,
     const double* MovieData, int64_t n2, int64_t D2, double signal_var, double sigma_u,
@@ -86,6 +90,8 @@ static int cf_sgd_run(
     double b, double c, int64_t burnin, int64_t maxepoch, uint64_t seed, int32_t langevin,
     int32_t stiefel, int32_t avg, bool fixw, CfInit init) {
   const int F = (int)folds.size();
+  CfInject inj;                                      // taken here: cleared however the run ends
+  std::swap(inj, g_cf_inject);
   bool ok = F >= 1 && (D1 == 0 || UserData) && (D2 == 0 || MovieData) && w_init && n1 >= 1 &&
             n2 >= 1 && D1 >= 0 && D2 >= 0 && m >= 1 && burnin >= 0 && maxepoch >= 0 &&
             signal_var > 0 && sigma_u > 0 && sigma_w > 0;
@@ -113,6 +119,16 @@ static int cf_sgd_run(
     if (stiefel && init != kCfInitSigma) host_stiefel_polar(Z.data(), (int)r, rows, M);
     else if (init == kCfInitUnit) for (size_t e = 0; e < Z.size(); ++e) M[e] = Z[e];
     else for (size_t e = 0; e < Z.size(); ++e) M[e] = sigma_u * Z[e];
+  }
+  if (inj.armed) {
+    if (inj.rowsU != rowsU || inj.rowsV != rowsV || inj.r != r) {
+      set_error(std::string(name) + ": the injected U0 / V0 (gpt_debug_cf_init) are " +
+                std::to_string(inj.rowsU) + " and " + std::to_string(inj.rowsV) + " rows of rank " +
+                std::to_string(inj.r) + ", the run has " + std::to_string(rowsU) + " and " +
+                std::to_string(rowsV) + " of rank " + std::to_string(r));
+      return GPT_ERR_BAD_DIMS;
+    }
+    U0 = inj.U; V0 = inj.V;
   }
   const size_t nU = U0.size(), nV = V0.size(), rr = (size_t)r * r;
   const int nbatch = (int)((N + m - 1) / m);
@@ -426,6 +442,21 @@ extern "C" int gpt_cf_fullw_sideinfo_folds(
   if (status)
     for (int64_t f = 0; f < F; ++f) status[f] = folds[f].status;
   return rc;
+}
+
+extern "C" int gpt_debug_cf_init(const double* U0, int64_t rowsU, const double* V0, int64_t rowsV,
+                                 int64_t r) {
+  g_cf_inject = CfInject{};
+  if (!U0 && !V0) return GPT_OK;                     // disarm
+  if (!U0 || !V0 || rowsU < 1 || rowsV < 1 || r < 1) {
+    set_error("gpt_debug_cf_init: U0 and V0 (rows >= 1, r >= 1), or both null");
+    return GPT_ERR_BAD_DIMS;
+  }
+  g_cf_inject.U.assign(U0, U0 + (size_t)rowsU * r);
+  g_cf_inject.V.assign(V0, V0 + (size_t)rowsV * r);
+  g_cf_inject.rowsU = rowsU; g_cf_inject.rowsV = rowsV; g_cf_inject.r = r;
+  g_cf_inject.armed = true;
+  return GPT_OK;
 }
 
 extern "C" int gpt_cf_last_timing(double* epoch_ms, double* eval_ms, int64_t* epochs,

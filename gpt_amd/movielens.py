@@ -5,6 +5,8 @@ BASELINE config 5) on libgptsgld.so.
                        w_init, m, epsw, epsU, a, b, c, burnin, maxepoch, param_seed,
                        ytrainMean, ytrainStd; langevin=False, stiefel=False, avg=False)
                                                              100k_movielensExperiment.jl:409-551
+                       (the four SGD entries also take U_init=, V_init=: the initial U and V in
+                       place of the Philox draw, for the tests' injected state)
     GPT_fullw_gibbs(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w,
                     w_init, burnin, maxepoch, n_samples, param_seed, ytrainMean, ytrainStd;
                     avg=False, rotated_w=False)              100k_movielensExperiment.jl:1032-1129
@@ -48,6 +50,19 @@ def _ptr(a):
     return a.ctypes.data_as(P_D)
 
 
+def _inject(U_init, V_init):
+    """Hand U_init ((n1+D1) x r) and V_init ((n2+D2) x r) to the next CF SGD run of this thread
+    (gpt_debug_cf_init: one shot, the run checks the dimensions); nothing when both are None."""
+    if U_init is None and V_init is None:
+        return
+    if U_init is None or V_init is None:
+        raise ValueError("U_init and V_init go together")
+    U0, V0 = _f64(U_init), _f64(V_init)
+    if U0.ndim != 2 or V0.ndim != 2 or U0.shape[1] != V0.shape[1]:
+        raise ValueError("U_init is (n1 + D1) x r and V_init (n2 + D2) x r")
+    check(lib().gpt_debug_cf_init(_ptr(U0), U0.shape[0], _ptr(V0), V0.shape[0], U0.shape[1]))
+
+
 def fold(data, i):
     """(Ratingtrain, Ratingtest, UserData, MovieData, ytrainMean, ytrainStd) of fold i (1..5),
     ratings standardised with the training mean / std (:570-575)."""
@@ -62,7 +77,8 @@ def fold(data, i):
 
 def GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w,
                        w_init, m, epsw, epsU, a, b, c, burnin, maxepoch, param_seed, ytrainMean,
-                       ytrainStd, langevin=False, stiefel=False, avg=False):
+                       ytrainStd, langevin=False, stiefel=False, avg=False, U_init=None, V_init=None):
+    """U_init / V_init (tests): the initial U and V in place of the Philox draw."""
     Rt = _f64(Rating)
     Rs = _f64(Ratingtest)
     Ud = _f64(UserData)
@@ -80,6 +96,7 @@ def GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigm
     tps = np.zeros((Ntest, maxepoch), order="F")
     trm = np.zeros(maxepoch)
     tsm = np.zeros(maxepoch)
+    _inject(U_init, V_init)
     code = lib().gpt_cf_fullw_sideinfo(
         _ptr(Rt), N, N, _ptr(Ud), n1, D1, _ptr(Md), n2, D2, _ptr(Rs), Ntest, Ntest,
         float(signal_var), float(sigma_u), float(sigma_w), _ptr(w0), r, int(m), float(epsw),
@@ -137,7 +154,7 @@ def _nan_or_check(code):
 
 def GPT_fixw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m, epsU,
                       a, b, c, burnin, maxepoch, param_seed, ytrainMean, ytrainStd,
-                      langevin=False, stiefel=False, avg=False):
+                      langevin=False, stiefel=False, avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:282-404 -> (U_store, V_store, testpred_store, trainRMSEvec,
     testRMSEvec)."""
     Rt, Rs, w0, r, tps, trm, tsm = _sgd_common(Rating, Ratingtest, w, maxepoch)
@@ -146,6 +163,7 @@ def GPT_fixw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma
     n2, D2 = Md.shape
     U_store = np.zeros((n1 + D1, r, maxepoch), order="F")
     V_store = np.zeros((n2 + D2, r, maxepoch), order="F")
+    _inject(U_init, V_init)
     _nan_or_check(lib().gpt_cf_fixw_sideinfo(
         _ptr(Rt), Rt.shape[0], Rt.shape[0], _ptr(Ud), n1, D1, _ptr(Md), n2, D2, _ptr(Rs),
         Rs.shape[0], Rs.shape[0], float(signal_var), float(sigma_u), _ptr(w0), r, int(m),
@@ -158,7 +176,7 @@ def GPT_fixw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma
 
 def GPT_fullw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w, w_init, m,
               epsw, epsU, burnin, maxepoch, param_seed, ytrainMean, ytrainStd, langevin=False,
-              stiefel=False, avg=False):
+              stiefel=False, avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:160-279 (no side information) -> (w_store, U_store, V_store,
     testpred_store, trainRMSEvec, testRMSEvec)."""
     Rt, Rs, w0, r, tps, trm, tsm = _sgd_common(Rating, Ratingtest, w_init, maxepoch)
@@ -166,6 +184,7 @@ def GPT_fullw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigm
     w_store = np.zeros((r, r, maxepoch), order="F")
     U_store = np.zeros((n1, r, maxepoch), order="F")
     V_store = np.zeros((n2, r, maxepoch), order="F")
+    _inject(U_init, V_init)
     _nan_or_check(lib().gpt_cf_fullw(
         _ptr(Rt), Rt.shape[0], Rt.shape[0], n1, n2, _ptr(Rs), Rs.shape[0], Rs.shape[0],
         float(signal_var), float(sigma_u), float(sigma_w), _ptr(w0), r, int(m), float(epsw),
@@ -178,13 +197,14 @@ def GPT_fullw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigm
 
 def GPT_fixw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m, epsU, burnin,
              maxepoch, param_seed, ytrainMean, ytrainStd, langevin=False, stiefel=False,
-             avg=False):
+             avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:56-156 (no side information, w fixed) -> (U_store, V_store,
     testpred_store, trainRMSEvec, testRMSEvec)."""
     Rt, Rs, w0, r, tps, trm, tsm = _sgd_common(Rating, Ratingtest, w, maxepoch)
     n1, n2 = np.shape(UserData)[0], np.shape(MovieData)[0]
     U_store = np.zeros((n1, r, maxepoch), order="F")
     V_store = np.zeros((n2, r, maxepoch), order="F")
+    _inject(U_init, V_init)
     _nan_or_check(lib().gpt_cf_fixw(
         _ptr(Rt), Rt.shape[0], Rt.shape[0], n1, n2, _ptr(Rs), Rs.shape[0], Rs.shape[0],
         float(signal_var), float(sigma_u), _ptr(w0), r, int(m), float(epsU), int(burnin),

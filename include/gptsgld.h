@@ -235,6 +235,14 @@ int gpt_debug_expm(int32_t nn, int32_t count, int32_t mode, const double* A, dou
  * normals (seed, c1, c2, c3) of element e = 0..p-1; *status = 1 if M is not positive definite. */
 int gpt_debug_gaussian_draw(int32_t p, const double* M, const double* x, uint64_t seed, uint32_t c1,
                             uint32_t c2, uint32_t c3, double* out, int32_t* status);
+/* Test entry: the initial U ((n1+D1) x r) and V ((n2+D2) x r), both column-major, of the next CF
+ * SGD / SGLD run on this thread (gpt_cf_fullw_sideinfo, gpt_cf_fixw_sideinfo, gpt_cf_fullw,
+ * gpt_cf_fixw, gpt_cf_fullw_sideinfo_folds: every fold starts from them) in place of the host's
+ * Philox draw.  The arrays are copied.  One shot: that run takes the pair and clears it whether or
+ * not it succeeds; rows or rank that differ from the run's are GPT_ERR_BAD_DIMS there, with a
+ * message.  The Stiefel path takes the columns as they are (orthonormal is the caller's business).
+ * U0 = V0 = NULL clears a pending pair; one of them NULL, rows < 1 or r < 1 is GPT_ERR_BAD_DIMS. */
+int gpt_debug_cf_init(const double* U0, int64_t rowsU, const double* V0, int64_t rowsV, int64_t r);
 /* Test entry: one function of the noise path (gpt_amd/csrc/fastmath.h, gpt_common.h) evaluated on
  * the device on `count` host inputs, called as the engines call it (coefficients through the
  * constant table, the sin/cos tables filled in LDS by sincos_tab_fill).  fn:

@@ -63,11 +63,12 @@ def predict(ratings, U, V, w, uidx, vidx, a, b, c):
 def GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w,
                        w_init, m, epsw, epsU, a, b, c, burnin, maxepoch, param_seed, ytrainMean,
                        ytrainStd, langevin=False, stiefel=False, avg=False, fixw=False,
-                       init="side"):
+                       init="side", U_init=None, V_init=None):
     """100k_movielensExperiment.jl:409-551 (fixw / init: the other SGD variants, below).  Rating (N, 3+) holds 1-based user / movie ids and
     the standardised rating.  Returns (w_store (r, r, T), U_store (n1+D1, r, T), V_store,
     testpred_store (Ntest, T), trainRMSEvec (T), testRMSEvec (T)), T = maxepoch; entries of
-    epochs after an early stop (:545-547) stay 0 (10 for testRMSEvec, as :441)."""
+    epochs after an early stop (:545-547) stay 0 (10 for testRMSEvec, as :441).  U_init / V_init
+    (both or neither) replace the drawn initial U and V (the tests' injected state)."""
     Rating = np.asarray(Rating, dtype=np.float64)
     Ratingtest = np.asarray(Ratingtest, dtype=np.float64)
     N, Ntest = len(Rating), len(Ratingtest)
@@ -82,6 +83,9 @@ def GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigm
     testpred_store = np.zeros((Ntest, maxepoch), order="F")
     U = init_uv(n1 + D1, r, param_seed, 0, stiefel, sigma_u, init)
     V = init_uv(n2 + D2, r, param_seed, 1, stiefel, sigma_u, init)
+    if U_init is not None:
+        U = np.array(U_init, dtype=np.float64).reshape((n1 + D1, r))
+        V = np.array(V_init, dtype=np.float64).reshape((n2 + D2, r))
     uidx, vidx = side_rows(UserData, MovieData)
     trainRMSE = np.zeros(maxepoch)
     testRMSE = 10.0 * np.ones(maxepoch)
@@ -163,13 +167,14 @@ def GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigm
 
 def GPT_fixw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m, epsU,
                       a, b, c, burnin, maxepoch, param_seed, ytrainMean, ytrainStd,
-                      langevin=False, stiefel=False, avg=False):
+                      langevin=False, stiefel=False, avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:282-404: GPT_fullw_sideinfo with w fixed (no gradw, no w
     step) and U, V = σ_u·randn (:294, also under stiefel).  Returns (U_store, V_store,
     testpred_store, trainRMSE, testRMSE)."""
     out = GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, 1.0, w,
                              m, 0.0, epsU, a, b, c, burnin, maxepoch, param_seed, ytrainMean,
-                             ytrainStd, langevin, stiefel, avg, fixw=True, init="sigma")
+                             ytrainStd, langevin, stiefel, avg, fixw=True, init="sigma",
+                             U_init=U_init, V_init=V_init)
     return out[1:]
 
 
@@ -179,25 +184,27 @@ def _no_side(UserData, MovieData):
 
 def GPT_fullw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w, w_init, m,
               epsw, epsU, burnin, maxepoch, param_seed, ytrainMean, ytrainStd, langevin=False,
-              stiefel=False, avg=False):
+              stiefel=False, avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:160-279: no side information — pred = sum((U[user,:]*w).*
     V[movie,:]), gradw = kron(V[movie,:]', U[user,:]') (= the side-information model at a = 1,
     b = c = 0 with no feature rows); U, V = randn or the Stiefel polar init (:175-180)."""
     ud, md = _no_side(UserData, MovieData)
     return GPT_fullw_sideinfo(Rating, ud, md, Ratingtest, signal_var, sigma_u, sigma_w, w_init, m,
                               epsw, epsU, 1.0, 0.0, 0.0, burnin, maxepoch, param_seed, ytrainMean,
-                              ytrainStd, langevin, stiefel, avg, init="unit")
+                              ytrainStd, langevin, stiefel, avg, init="unit", U_init=U_init,
+                              V_init=V_init)
 
 
 def GPT_fixw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m, epsU, burnin,
              maxepoch, param_seed, ytrainMean, ytrainStd, langevin=False, stiefel=False,
-             avg=False):
+             avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:56-156: no side information, w fixed, U, V = σ_u·randn.
     Returns (U_store, V_store, testpred_store, trainRMSE, testRMSE)."""
     ud, md = _no_side(UserData, MovieData)
     out = GPT_fullw_sideinfo(Rating, ud, md, Ratingtest, signal_var, sigma_u, 1.0, w, m, 0.0,
                              epsU, 1.0, 0.0, 0.0, burnin, maxepoch, param_seed, ytrainMean,
-                             ytrainStd, langevin, stiefel, avg, fixw=True, init="sigma")
+                             ytrainStd, langevin, stiefel, avg, fixw=True, init="sigma",
+                             U_init=U_init, V_init=V_init)
     return out[1:]
 
 
