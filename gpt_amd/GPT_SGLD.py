@@ -578,6 +578,177 @@ def GPNT_SGLD(phi, y, signal_var, sigma_theta, m, eps_theta, decay_rate, burnin,
     return out
 
 
+def _per_chain(values, nchains, what):
+    v = _f64(np.atleast_1d(values)).ravel()
+    if v.size == 1 and nchains > 1:
+        v = _f64(np.full(nchains, v[0]))
+    if v.size != nchains:
+        raise ValueError("%s must be a scalar or have one entry per chain" % what)
+    return v
+
+
+def _chains_args(y, N, signal_vars, sigma_thetas, eps_thetas, seeds, store_every):
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    if y.size != N:
+        raise ValueError("the features and y disagree on N")
+    seeds = np.ascontiguousarray([int(s) & (2 ** 64 - 1) for s in np.atleast_1d(seeds)], dtype=np.uint64)
+    k = seeds.size
+    if k < 1:
+        raise ValueError("seeds must have one entry per chain")
+    if int(store_every) < 1:
+        raise ValueError("store_every must be >= 1")
+    return (y, _per_chain(signal_vars, k, "signal_vars"), _per_chain(sigma_thetas, k, "sigma_thetas"),
+            _per_chain(eps_thetas, k, "eps_thetas"), seeds)
+
+
+def _chains_out(n, N, m, burnin, maxepoch, store_every, nchains):
+    if int(m) < 1:
+        raise ValueError("m must be >= 1")
+    kept = (int(maxepoch) + int(burnin)) * (-(-N // int(m))) // int(store_every)
+    return np.zeros((n, max(kept, 0), nchains), order="F"), np.zeros(nchains, dtype=np.int32)
+
+
+def GPNT_SGLD_chains(phi, y, signal_vars, sigma_thetas, m, eps_thetas, decay_rate, burnin, maxepoch,
+                     seeds, store_every=1):
+    """Sibling GPNT_SGLD chains on one phi / y in one launch (step-size, noise and seed sweeps):
+    chain k runs GPNT_SGLD with signal_vars[k], sigma_thetas[k], eps_thetas[k] and seeds[k];
+    scalars broadcast to the number of seeds.  ``store_every`` keeps the 1-based steps divisible
+    by it (numbatches: the epoch ends; burn-in steps count).  Returns (theta_store (n, kept,
+    nchains), status (nchains)); a chain that met a NaN has a zero store and status
+    GPT_ERR_NAN_THETA."""
+    phi = _f64(phi)
+    n, N = phi.shape
+    y, sv, sth, eps, seeds = _chains_args(y, N, signal_vars, sigma_thetas, eps_thetas, seeds,
+                                          store_every)
+    out, status = _chains_out(n, N, m, burnin, maxepoch, store_every, seeds.size)
+    check(lib().gpt_gpnt_sgld_chains(_ptr(phi), _ptr(y), n, N, int(m), _ptr(sv), _ptr(sth),
+                                     _ptr(eps), float(decay_rate), int(burnin), int(maxepoch),
+                                     _ptr(seeds, P_U64), seeds.size, int(store_every), _ptr(out),
+                                     _ptr(status, P_I32)))
+    return out, status
+
+
+def _notensor_inputs(X, length_scale, Z, b):
+    X = _f64(X)
+    if X.ndim != 2:
+        raise ValueError("X must be (N, D)")
+    D = X.shape[1]
+    Z = _f64(Z)
+    b = _f64(np.asarray(b, dtype=np.float64).ravel())
+    n = Z.shape[0]
+    if Z.shape != (n, D) or b.size != n:
+        raise ValueError("Z must be (n, D) and b of length n")
+    ls = _f64(np.atleast_1d(length_scale)).ravel()
+    if ls.size not in (1, D):
+        raise ValueError("dimensions of X and length_scale do not match")
+    return X, ls, Z, b, n
+
+
+def GPNT_SGLD_chains_x(X, y, length_scale, sigma_RBF, Z, b, signal_vars, sigma_thetas, m, eps_thetas,
+                       decay_rate, burnin, maxepoch, seeds, store_every=1):
+    """GPNT_SGLD_chains on phi = featureNotensor(X, length_scale, sigma_RBF, Z, b) formed on the
+    device: the same doubles, and no (n, N) host array."""
+    X, ls, Z, b, n = _notensor_inputs(X, length_scale, Z, b)
+    N, D = X.shape
+    y, sv, sth, eps, seeds = _chains_args(y, N, signal_vars, sigma_thetas, eps_thetas, seeds,
+                                          store_every)
+    out, status = _chains_out(n, N, m, burnin, maxepoch, store_every, seeds.size)
+    check(lib().gpt_gpnt_sgld_chains_x(_ptr(X), _ptr(y), N, D, _ptr(ls), ls.size, float(sigma_RBF),
+                                       _ptr(Z), _ptr(b), n, int(m), _ptr(sv), _ptr(sth), _ptr(eps),
+                                       float(decay_rate), int(burnin), int(maxepoch),
+                                       _ptr(seeds, P_U64), seeds.size, int(store_every), _ptr(out),
+                                       _ptr(status, P_I32)))
+    return out, status
+
+
+def gpnt_last_route():
+    """The route of the last GPNT_SGLD_chains* call on this thread (gpt_gpnt_last_route): ``rows``
+    staged per group (0 = not staged), ``groups`` per full batch, ``lds_bytes`` of the launches."""
+    out = np.zeros(3, dtype=np.int32)
+    check(lib().gpt_gpnt_last_route(_ptr(out, P_I32), out.size))
+    return dict(rows=int(out[0]), groups=int(out[1]), lds_bytes=int(out[2]))
+
+
+def gpnt_last_timing():
+    """Device-event ms of the last calls on this thread (gpt_gpnt_last_timing): ``sampler`` the
+    launches of GPNT_SGLD_chains*, ``eval`` the scores and reduction kernels of GPNT_pred*."""
+    out = np.zeros(2)
+    check(lib().gpt_gpnt_last_timing(_ptr(out), out.size))
+    return dict(sampler=float(out[0]), eval=float(out[1]))
+
+
+class RegEval:
+    """Result of GPNT_pred / GPNT_pred_x: ``sample_rmse`` (T) the test RMSE of every sample,
+    ``mean_fhat`` (Ntest) the prediction averaged over the window and ``rmse`` its test RMSE,
+    ``window`` the half-open 0-based sample range, and ``scores`` (Ntest, T) when asked."""
+    __slots__ = ("sample_rmse", "mean_fhat", "rmse", "window", "scores")
+
+    def __repr__(self):
+        return "RegEval(T=%d, rmse=%.6g, window=%r)" % (self.sample_rmse.size, self.rmse, self.window)
+
+
+def _reg_samples(theta_store, cols, n, ytest, Nt, window):
+    theta = np.asarray(theta_store, dtype=np.float64)
+    if theta.ndim == 1:
+        theta = theta.reshape((-1, 1))
+    if theta.ndim != 2:
+        raise ValueError("theta_store must be (n, T): one chain's samples")
+    if cols is not None:
+        theta = theta[:, np.asarray(cols, dtype=np.int64)]
+    theta = _f64(theta)
+    if theta.shape[0] != n:
+        raise ValueError("theta_store and the test features disagree on n")
+    T = theta.shape[1]
+    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+    if yt.size != Nt:
+        raise ValueError("ytest must have one target per test row")
+    first, last = _window(window, T)
+    if not 0 <= first < last <= T:
+        raise ValueError("the window must satisfy 0 <= first < last <= %d" % T)
+    return theta, yt, T, first, last
+
+
+def _reg_eval_call(fn, head, Nt, T, first, last, scale, want_scores):
+    res = RegEval()
+    res.sample_rmse = np.empty(T)
+    res.mean_fhat = np.empty(Nt)
+    rmse = np.empty(1)
+    res.scores = np.empty((Nt, T), order="F") if want_scores else None
+    check(fn(*(head + [T, first, last, float(scale), _ptr(res.sample_rmse), _ptr(res.mean_fhat),
+                       _ptr(rmse), _ptr(res.scores) if want_scores else None])))
+    res.rmse = float(rmse[0])
+    res.window = (first, last)
+    return res
+
+
+def GPNT_pred(theta_store, phitest, ytest, cols=None, window=None, scale=1.0, scores=False):
+    """Evaluation of GPNT_SGLD samples (PowerPlantNoTensorExperiment.jl:51-63): theta_store (n, T)
+    of one chain, phitest (n, Ntest).  ``cols`` selects stored samples (0-based) on the host before
+    the call; ``window`` is the half-open 0-based range over the selected samples whose averaged
+    prediction is scored ((59, 100) is Julia's 60:100; default all); ``scale`` multiplies every
+    RMSE (ytrainStd).  Returns a RegEval."""
+    phitest = _f64(phitest)
+    if phitest.ndim != 2:
+        raise ValueError("phitest must be (n, Ntest)")
+    n, Nt = phitest.shape
+    theta, yt, T, first, last = _reg_samples(theta_store, cols, n, ytest, Nt, window)
+    return _reg_eval_call(lib().gpt_gpnt_pred, [_ptr(theta), _ptr(phitest), _ptr(yt), n, Nt], Nt, T,
+                          first, last, scale, bool(scores))
+
+
+def GPNT_pred_x(theta_store, Xtest, ytest, length_scale, sigma_RBF, Z, b, cols=None, window=None,
+                scale=1.0, scores=False):
+    """GPNT_pred on phitest = featureNotensor(Xtest, length_scale, sigma_RBF, Z, b) formed on the
+    device."""
+    Xtest, ls, Z, b, n = _notensor_inputs(Xtest, length_scale, Z, b)
+    Nt, D = Xtest.shape
+    theta, yt, T, first, last = _reg_samples(theta_store, cols, n, ytest, Nt, window)
+    return _reg_eval_call(lib().gpt_gpnt_pred_x,
+                          [_ptr(theta), _ptr(Xtest), _ptr(yt), Nt, D, _ptr(ls), ls.size,
+                           float(sigma_RBF), _ptr(Z), _ptr(b), n], Nt, T, first, last, scale,
+                          bool(scores))
+
+
 # ------------------------------------------------------------------ classification
 def GPNT_SGLDclass(phi, y, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch, param_seed=0):
     """Full-theta softmax SGLD (GPT_SGLD.jl:851-901), labels y in 1..C.  Returns theta_store

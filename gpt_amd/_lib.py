@@ -109,6 +109,20 @@ SIGNATURES = {
                                 C.c_int64, C.c_int64, C.c_int64, C.c_double, P_D, P_D]),
     "gpt_gpnt_sgld": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64,
                                 C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_uint64, P_D]),
+    "gpt_gpnt_sgld_chains": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_int64, P_D, P_D, P_D,
+                                       C.c_double, C.c_int64, C.c_int64, P_U64, C.c_int32,
+                                       C.c_int64, P_D, P_I32]),
+    "gpt_gpnt_sgld_chains_x": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, P_D, C.c_int64, C.c_double,
+                                         P_D, P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_double,
+                                         C.c_int64, C.c_int64, P_U64, C.c_int32, C.c_int64, P_D,
+                                         P_I32]),
+    "gpt_gpnt_pred": (C.c_int, [P_D, P_D, P_D, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                C.c_int64, C.c_double, P_D, P_D, P_D, P_D]),
+    "gpt_gpnt_pred_x": (C.c_int, [P_D, P_D, P_D, C.c_int64, C.c_int64, P_D, C.c_int64, C.c_double,
+                                  P_D, P_D, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double,
+                                  P_D, P_D, P_D, P_D]),
+    "gpt_gpnt_last_route": (C.c_int, [P_I32, C.c_int32]),
+    "gpt_gpnt_last_timing": (C.c_int, [P_D, C.c_int32]),
     "gpt_gpnt_sgld_class": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_double, C.c_int64,
                                       C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_uint64,
                                       P_D]),

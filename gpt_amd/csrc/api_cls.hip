@@ -94,22 +94,8 @@ extern "C" int gpt_sgld_classification(const gpt_sgld_config* cfg, const double*
 // [0] the sampler's launches, [1] the scores (nt_scores_kernel or the stacked prediction),
 // [2] the evaluation kernels.
 static thread_local double g_cls_ms[3] = {0.0, 0.0, 0.0};
-struct ClsTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  hipStream_t st;
-  int slot;
-  ClsTimer(int slot_, hipStream_t st_) : st(st_), slot(slot_) {
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
-    (void)hipEventRecord(a, st);
-  }
-  void stop() { if (b) (void)hipEventRecord(b, st); }
-  ~ClsTimer() {                       // after the caller's synchronisation
-    float ms = 0.0f;
-    if (a && b && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess)
-      g_cls_ms[slot] = ms;
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
+struct ClsTimer : EventTimer {
+  ClsTimer(int slot, hipStream_t st_) : EventTimer(&g_cls_ms[slot], st_) {}
 };
 extern "C" int gpt_class_last_timing(double* ms_out) {
   if (!ms_out) { set_error("gpt_class_last_timing: null argument"); return GPT_ERR_BAD_DIMS; }

@@ -1,0 +1,292 @@
+// Full-theta regression from host arrays: sibling GPNT_SGLD chains (gpnt.hip) from phi or from X,
+// and the evaluation of stored samples: test RMSE per sample and of the prediction averaged over
+// a window of samples (PowerPlantNoTensorExperiment.jl:42-63).
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <unordered_map>
+#include <vector>
+
+#include "host_util.h"
+
+using namespace gpt;
+
+// gpt_gpnt_last_route / gpt_gpnt_last_timing of this thread
+static thread_local int32_t g_gpnt_route[3] = {0, 0, 0};
+static thread_local double g_gpnt_ms[2] = {0.0, 0.0};
+
+extern "C" int gpt_gpnt_last_route(int32_t* out, int32_t len) {
+  if (!out || len < 0) { set_error("gpt_gpnt_last_route: bad output"); return GPT_ERR_BAD_DIMS; }
+  for (int32_t x = 0; x < len; ++x) out[x] = x < 3 ? g_gpnt_route[x] : 0;
+  return GPT_OK;
+}
+
+extern "C" int gpt_gpnt_last_timing(double* ms, int32_t len) {
+  if (!ms || len < 0) { set_error("gpt_gpnt_last_timing: bad output"); return GPT_ERR_BAD_DIMS; }
+  for (int32_t x = 0; x < len; ++x) ms[x] = x < 2 ? g_gpnt_ms[x] : 0.0;
+  return GPT_OK;
+}
+
+// GPTSGLD_GPNT_ROWS=<g> (read on every call): at most g staged rows per group, 0 = no staging;
+// -1 when unset or not a number
+static int gpnt_rows_cap() {
+  const char* ev = std::getenv("GPTSGLD_GPNT_ROWS");
+  if (!ev || !*ev) return -1;
+  char* end = nullptr;
+  const long v = std::strtol(ev, &end, 10);
+  if (end == ev || v < 0) return -1;
+  return (int)std::min<long>(v, 1 << 30);
+}
+
+struct GpntRun {
+  long long nb, total, kept;
+  int epochs;
+  GpntLayout L;
+};
+
+static bool gpnt_run_info(const void* data, const double* y, int64_t n, int64_t N, int64_t m,
+                          const double* signal_var, const double* sigma_theta,
+                          const double* eps_theta, int64_t burnin, int64_t maxepoch,
+                          const uint64_t* seeds, int32_t nchains, int64_t store_every,
+                          const double* theta_store, const int32_t* status, GpntRun* R) {
+  if (!data || !y || !signal_var || !sigma_theta || !eps_theta || !seeds || !theta_store || !status) {
+    set_error("gpt_gpnt_sgld_chains: null argument"); return false;
+  }
+  if (n < 1 || N < 1 || m < 1 || burnin < 0 || maxepoch < 0 || nchains < 1 || store_every < 1 ||
+      n > (1 << 20) || N > (1LL << 31) - 1 || m > (1LL << 31) - 1 || nchains > 65535 ||
+      store_every > (1 << 30) || burnin + maxepoch > (1 << 24)) {
+    set_error("bad GPNT_SGLD_chains dimensions"); return false;
+  }
+  R->L = gpnt_layout((int)n, (int)N, (int)m, gpnt_rows_cap());
+  if (R->L.base > (size_t)kMaxLds) {
+    set_error("GPNT_SGLD_chains: theta (n) and the batch's bookkeeping exceed 160 KiB of LDS");
+    return false;
+  }
+  R->nb = (N + m - 1) / m;
+  R->epochs = (int)(burnin + maxepoch);
+  R->total = (long long)R->epochs * R->nb;
+  R->kept = R->total / store_every;
+  return true;
+}
+
+// The chains on device features dphi (n, N); y and every other array are the host's.
+static int gpnt_chains_core(const double* dphi, const double* y, int64_t n, int64_t N, int64_t m,
+                            const double* signal_var, const double* sigma_theta,
+                            const double* eps_theta, double decay_rate, const uint64_t* seeds,
+                            int32_t nchains, int64_t store_every, const GpntRun& R,
+                            double* theta_store, int32_t* status) {
+  const int epochs = R.epochs;
+  const long long nb = R.nb, total = R.total, kept = R.kept;
+  // epoch orders: one set per distinct seed
+  std::unordered_map<uint64_t, size_t> ord_of;
+  std::vector<size_t> ord_at(nchains);
+  for (int k = 0; k < nchains; ++k) {
+    auto it = ord_of.find(seeds[k]);
+    if (it == ord_of.end()) it = ord_of.emplace(seeds[k], ord_of.size()).first;
+    ord_at[k] = it->second;
+  }
+  const size_t per = (size_t)epochs * N;
+  std::vector<int32_t> ord(per * ord_of.size());
+  for (const auto& kv : ord_of) host_epoch_orders((int)N, kv.first, epochs, ord.data() + per * kv.second);
+  std::vector<double> th0((size_t)n * nchains);
+  for (int k = 0; k < nchains; ++k)
+    for (int64_t j = 0; j < n; ++j)
+      th0[(size_t)n * k + j] = sigma_theta[k] * host_normal(seeds[k], (uint32_t)j, 0, kThetaInit, 0);
+  const size_t nkept = (size_t)n * (size_t)kept * nchains;
+  DevMem dy, dord, dth, dst, dstat, dch;
+  GPT_HIPCHK(dy.upload(y, (size_t)N));
+  GPT_HIPCHK(dord.upload(ord.data(), ord.size()));
+  GPT_HIPCHK(dth.upload(th0.data(), th0.size()));
+  GPT_HIPCHK(dst.alloc<double>(nkept));
+  GPT_HIPCHK(dstat.alloc<int32_t>(nchains));
+  std::vector<GpntChain> ch(nchains);
+  for (int k = 0; k < nchains; ++k) {
+    ch[k].order = dord.as<int32_t>() + per * ord_at[k];
+    ch[k].theta = dth.as<double>() + (size_t)n * k;
+    ch[k].store = dst.as<double>() + (size_t)n * (size_t)kept * k;
+    ch[k].status = dstat.as<int32_t>() + k;
+    ch[k].seed = seeds[k];
+    ch[k].eps_theta = eps_theta[k];
+    ch[k].signal_var = signal_var[k];
+    ch[k].sigma_theta = sigma_theta[k];
+  }
+  GPT_HIPCHK(dch.upload(ch.data(), ch.size()));
+  GPT_HIPCHK(dstat.zero());
+  GPT_HIPCHK(dst.zero());
+  g_gpnt_route[0] = R.L.rows;
+  g_gpnt_route[1] = R.L.groups;
+  g_gpnt_route[2] = (int32_t)R.L.bytes;
+  const int chunk = (int)std::min<long long>(nb, 4096);       // steps per launch, within an epoch
+  {
+    EventTimer tm(&g_gpnt_ms[0], nullptr);
+    for (int e = 0; e < epochs; ++e)
+      for (long long b0 = 0; b0 < nb; b0 += chunk) {
+        hipError_t er = launch_gpnt_chain(dphi, dy.as<double>(), dch.as<GpntChain>(), nchains,
+                                          (int)n, (int)N, (int)m, (int)nb, total, decay_rate,
+                                          (int)store_every, (long long)e * nb + b0,
+                                          (int)std::min<long long>(chunk, nb - b0), R.L, nullptr);
+        if (er != hipSuccess) return hip_fail(er, "gpnt_chain kernel");
+      }
+    tm.stop();
+    GPT_HIPCHK(dstat.download(status, nchains));
+  }
+  GPT_HIPCHK(dst.download(theta_store, nkept));
+  for (int k = 0; k < nchains; ++k)                            // GPT_SGLD.jl:840-843
+    if (status[k]) std::memset(theta_store + (size_t)n * (size_t)kept * k, 0, 8 * (size_t)n * (size_t)kept);
+  return GPT_OK;
+}
+
+extern "C" int gpt_gpnt_sgld_chains(const double* phi, const double* y, int64_t n, int64_t N,
+                                    int64_t m, const double* signal_var, const double* sigma_theta,
+                                    const double* eps_theta, double decay_rate, int64_t burnin,
+                                    int64_t maxepoch, const uint64_t* seeds, int32_t nchains,
+                                    int64_t store_every, double* theta_store, int32_t* status) {
+  GpntRun R;
+  if (!gpnt_run_info(phi, y, n, N, m, signal_var, sigma_theta, eps_theta, burnin, maxepoch, seeds,
+                     nchains, store_every, theta_store, status, &R))
+    return GPT_ERR_BAD_DIMS;
+  for (int k = 0; k < nchains; ++k) status[k] = 0;
+  if (R.total == 0) return GPT_OK;
+  DevMem dphi;
+  GPT_HIPCHK(dphi.upload(phi, (size_t)n * N));
+  return gpnt_chains_core(dphi.as<double>(), y, n, N, m, signal_var, sigma_theta, eps_theta,
+                          decay_rate, seeds, nchains, store_every, R, theta_store, status);
+}
+
+static bool valid_feature_args(const double* ls, int64_t ls_len, int64_t D, const double* Z,
+                               const double* b) {
+  if (!ls || !Z || !b || D < 1 || D > (1 << 20)) { set_error("bad feature arguments"); return false; }
+  if (ls_len != 1 && ls_len != D) {
+    set_error("dimensions of X and length_scale do not match"); return false;
+  }
+  return true;
+}
+
+// dphi (n, rows) = featureNotensor(X, length_scale, sigma_rbf, Z, b) formed on the device: the
+// doubles gpt_feature_notensor makes, with no n x rows host array.
+static int device_features(const double* X, int64_t rows, int64_t D, const double* ls,
+                           int64_t ls_len, double sigma_rbf, const double* Z, const double* b,
+                           int64_t n, DevMem& dphi) {
+  std::vector<double> lsv(D);
+  for (int64_t k = 0; k < D; ++k) lsv[k] = ls[ls_len == 1 ? 0 : k];
+  DevMem dX, dls, dZ, db;
+  GPT_HIPCHK(dX.upload(X, (size_t)rows * D));
+  GPT_HIPCHK(dls.upload(lsv.data(), lsv.size()));
+  GPT_HIPCHK(dZ.upload(Z, (size_t)n * D));
+  GPT_HIPCHK(db.upload(b, (size_t)n));
+  GPT_HIPCHK(dphi.alloc<double>((size_t)n * rows));
+  const double c = std::sqrt(2.0 / (double)n) * sigma_rbf;
+  const hipError_t e = launch_feature_notensor(dX.as<double>(), rows, (int)D, dls.as<double>(), c,
+                                               dZ.as<double>(), db.as<double>(), (int)n,
+                                               dphi.as<double>(), nullptr);
+  if (e != hipSuccess) return hip_fail(e, "feature kernel");
+  GPT_HIPCHK(hipStreamSynchronize(nullptr));                 // the inputs are freed on return
+  return GPT_OK;
+}
+
+extern "C" int gpt_gpnt_sgld_chains_x(const double* X, const double* y, int64_t N, int64_t D,
+                                      const double* length_scale, int64_t ls_len, double sigma_rbf,
+                                      const double* Z, const double* b, int64_t n, int64_t m,
+                                      const double* signal_var, const double* sigma_theta,
+                                      const double* eps_theta, double decay_rate, int64_t burnin,
+                                      int64_t maxepoch, const uint64_t* seeds, int32_t nchains,
+                                      int64_t store_every, double* theta_store, int32_t* status) {
+  GpntRun R;
+  if (!gpnt_run_info(X, y, n, N, m, signal_var, sigma_theta, eps_theta, burnin, maxepoch, seeds,
+                     nchains, store_every, theta_store, status, &R) ||
+      !valid_feature_args(length_scale, ls_len, D, Z, b))
+    return GPT_ERR_BAD_DIMS;
+  for (int k = 0; k < nchains; ++k) status[k] = 0;
+  if (R.total == 0) return GPT_OK;
+  DevMem dphi;
+  const int rc = device_features(X, N, D, length_scale, ls_len, sigma_rbf, Z, b, n, dphi);
+  if (rc != GPT_OK) return rc;
+  return gpnt_chains_core(dphi.as<double>(), y, n, N, m, signal_var, sigma_theta, eps_theta,
+                          decay_rate, seeds, nchains, store_every, R, theta_store, status);
+}
+
+// ---------------------------------------------------------------------------------- evaluation
+static bool valid_gpnt_pred(const void* theta, const void* data, const void* ytest, int64_t n,
+                            int64_t Ntest, int64_t T, int64_t avg_first, int64_t avg_last,
+                            const void* sample_rmse, const void* mean, const void* rmse) {
+  if (!theta || !data || !ytest || !sample_rmse || !mean || !rmse) {
+    set_error("gpt_gpnt_pred: null argument"); return false;
+  }
+  if (n < 1 || Ntest < 1 || T < 1 || n > (1 << 24) || T > (1 << 22) || Ntest > (1LL << 40)) {
+    set_error("gpt_gpnt_pred: bad dimensions"); return false;
+  }
+  if (avg_first < 0 || avg_last > T || avg_first >= avg_last) {
+    set_error("gpt_gpnt_pred: the window must satisfy 0 <= avg_first < avg_last <= T"); return false;
+  }
+  return true;
+}
+
+// scores (Ntest, T) = phitestᵀ·theta on device features, then mean_sse_kernel twice: on all T
+// samples for the per-sample figures and on the window's columns for its mean and error.
+static int gpnt_pred_core(const double* theta, const double* dphi, const double* ytest, int64_t n,
+                          int64_t Ntest, int64_t T, int64_t avg_first, int64_t avg_last,
+                          double scale, double* sample_rmse_out, double* mean_out,
+                          double* rmse_out, double* scores_out) {
+  const int64_t S = avg_last - avg_first;
+  const size_t nscores = (size_t)Ntest * T;
+  DevMem dth, dy, ds, dmean, dsse, dwin;
+  GPT_HIPCHK(dth.upload(theta, (size_t)n * T));
+  GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
+  GPT_HIPCHK(ds.alloc<double>(nscores));
+  GPT_HIPCHK(dmean.alloc<double>((size_t)Ntest));
+  GPT_HIPCHK(dsse.alloc<double>((size_t)T + 1));
+  GPT_HIPCHK(dwin.alloc<double>((size_t)S + 1));
+  {
+    EventTimer tm(&g_gpnt_ms[1], nullptr);
+    hipError_t e = launch_nt_scores(dphi, dth.as<double>(), (int)n, Ntest, T, ds.as<double>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "nt_scores kernel");
+    e = launch_mean_rmse(ds.as<double>(), dy.as<double>(), Ntest, (int)T, nullptr,
+                         dsse.as<double>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
+    e = launch_mean_rmse(ds.as<double>() + (size_t)avg_first * Ntest, dy.as<double>(), Ntest, (int)S,
+                         dmean.as<double>(), dwin.as<double>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
+    tm.stop();
+    GPT_HIPCHK(hipStreamSynchronize(nullptr));
+  }
+  std::vector<double> sse((size_t)T + 1);
+  double wsse = 0.0;
+  GPT_HIPCHK(dsse.download(sse.data(), sse.size()));
+  GPT_HIPCHK(dwin.download(&wsse, 1));
+  GPT_HIPCHK(dmean.download(mean_out, (size_t)Ntest));
+  for (int64_t t = 0; t < T; ++t) sample_rmse_out[t] = scale * std::sqrt(sse[1 + t] / (double)Ntest);
+  *rmse_out = scale * std::sqrt(wsse / (double)Ntest);
+  if (scores_out) GPT_HIPCHK(ds.download(scores_out, nscores));
+  return GPT_OK;
+}
+
+extern "C" int gpt_gpnt_pred(const double* theta, const double* phitest, const double* ytest,
+                             int64_t n, int64_t Ntest, int64_t T, int64_t avg_first,
+                             int64_t avg_last, double scale, double* sample_rmse_out,
+                             double* mean_out, double* rmse_out, double* scores_out) {
+  if (!valid_gpnt_pred(theta, phitest, ytest, n, Ntest, T, avg_first, avg_last, sample_rmse_out,
+                       mean_out, rmse_out))
+    return GPT_ERR_BAD_DIMS;
+  DevMem dphi;
+  GPT_HIPCHK(dphi.upload(phitest, (size_t)n * Ntest));
+  return gpnt_pred_core(theta, dphi.as<double>(), ytest, n, Ntest, T, avg_first, avg_last, scale,
+                        sample_rmse_out, mean_out, rmse_out, scores_out);
+}
+
+extern "C" int gpt_gpnt_pred_x(const double* theta, const double* Xtest, const double* ytest,
+                               int64_t Ntest, int64_t D, const double* length_scale,
+                               int64_t ls_len, double sigma_rbf, const double* Z, const double* b,
+                               int64_t n, int64_t T, int64_t avg_first, int64_t avg_last,
+                               double scale, double* sample_rmse_out, double* mean_out,
+                               double* rmse_out, double* scores_out) {
+  if (!valid_gpnt_pred(theta, Xtest, ytest, n, Ntest, T, avg_first, avg_last, sample_rmse_out,
+                       mean_out, rmse_out) ||
+      !valid_feature_args(length_scale, ls_len, D, Z, b))
+    return GPT_ERR_BAD_DIMS;
+  DevMem dphi;
+  const int rc = device_features(Xtest, Ntest, D, length_scale, ls_len, sigma_rbf, Z, b, n, dphi);
+  if (rc != GPT_OK) return rc;
+  return gpnt_pred_core(theta, dphi.as<double>(), ytest, n, Ntest, T, avg_first, avg_last, scale,
+                        sample_rmse_out, mean_out, rmse_out, scores_out);
+}

@@ -351,6 +351,27 @@ hipError_t launch_gpnt(const double* phi, const double* y, const int32_t* order,
                        double* theta_store, int32_t* status, const long long* tbase, int t_local,
                        hipStream_t st);
 
+// Sibling GPNT_SGLD chains (gpnt.hip): one workgroup per chain, theta in LDS for a launch of up
+// to one epoch's steps.
+struct GpntChain {
+  const int32_t* order;  // epochs*N cumulative epoch orders of the chain's seed (0-based rows)
+  double* theta;         // n       current theta
+  double* store;         // n*kept
+  int32_t* status;       // 0 ok, GPT_ERR_NAN_THETA
+  uint64_t seed;
+  double eps_theta, signal_var, sigma_theta;
+};
+struct GpntLayout {
+  int rows, groups;      // rows: feature rows staged per group (0: none); groups per full batch
+  size_t o_theta, o_idx, o_y, o_res, o_flag, o_phi, base, bytes;   // base: bytes without the rows
+};
+GpntLayout gpnt_layout(int n, int N, int m, int rows_cap);   // rows_cap < 0: as many as fit
+// steps t0 .. t0+nsteps-1 (0-based, those below total) of every chain
+hipError_t launch_gpnt_chain(const double* phi, const double* y, const GpntChain* chains,
+                             int nchains, int n, int N, int m, int nb, long long total,
+                             double decay_rate, int store_every, long long t0, int nsteps,
+                             const GpntLayout& L, hipStream_t st);
+
 // Classification (cls.hip).  GPNT_SGLDclass: one workgroup per chain, theta (n x C) in LDS for a
 // launch of up to one epoch's steps.
 struct NtcChain {

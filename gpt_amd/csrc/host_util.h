@@ -101,4 +101,26 @@ struct ScopedEvents {
   }
 };
 
+// Device-event time in ms of the work put on st between construction and stop(), written to *ms
+// when the timer goes out of scope (after the caller's synchronisation).
+struct EventTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  hipStream_t st;
+  double* ms;
+  EventTimer(double* ms_, hipStream_t st_) : st(st_), ms(ms_) {
+    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
+    (void)hipEventRecord(a, st);
+  }
+  EventTimer(const EventTimer&) = delete;
+  EventTimer& operator=(const EventTimer&) = delete;
+  void stop() { if (b) (void)hipEventRecord(b, st); }
+  ~EventTimer() {
+    float t = 0.0f;
+    if (a && b && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&t, a, b) == hipSuccess)
+      *ms = t;
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+
 }  // namespace gpt

@@ -351,6 +351,61 @@ int gpt_gpnt_sgld(const double* phi, const double* y, int64_t n, int64_t N, doub
                   double sigma_theta, int64_t m, double eps_theta, double decay_rate,
                   int64_t burnin, int64_t maxepoch, uint64_t seed, double* theta_store);
 
+/* Sibling GPNT_SGLD chains of one launch on a shared phi / y (step-size, noise and seed sweeps,
+ * PowerPlantNoTensorExperiment.jl / kin40kNoTensorExperiment.jl): chain k runs GPNT_SGLD with
+ * signal_var[k], sigma_theta[k], eps_theta[k] and seeds[k]; theta0, step noise and epoch orders are
+ * gpt_gpnt_sgld's for that seed.  One workgroup per chain keeps theta in LDS for an epoch's steps
+ * and reads each feature row of a batch from memory once per step where at least four rows fit
+ * beside theta (n up to about 4000 at m = 50; past that the rows are read twice, which measures
+ * faster than groups of fewer rows).  store_every >= 1 keeps the 1-based
+ * steps divisible by it (1: every step, as the reference; numbatches: the epoch ends; burn-in steps
+ * count); theta_store (n, kept, nchains), kept = total steps / store_every.  status[k] =
+ * GPT_ERR_NAN_THETA and a zero-filled store for a chain that met a NaN (GPT_SGLD.jl:840-843); the
+ * other chains are untouched and the call returns GPT_OK.  theta and the batch's bookkeeping must
+ * fit the 160 KiB of LDS (n = 16 000 at m = 50 does); otherwise GPT_ERR_BAD_DIMS.
+ * GPTSGLD_GPNT_ROWS=<g> (read on every call) stages min(g, what fits) feature rows per group,
+ * 0 = none; the results do not depend on it. */
+int gpt_gpnt_sgld_chains(const double* phi, const double* y, int64_t n, int64_t N, int64_t m,
+                         const double* signal_var, const double* sigma_theta,
+                         const double* eps_theta, double decay_rate, int64_t burnin,
+                         int64_t maxepoch, const uint64_t* seeds, int32_t nchains,
+                         int64_t store_every, double* theta_store, int32_t* status);
+/* The same with phi = featureNotensor(X, length_scale, sigma_rbf, Z, b) formed on the device (the
+ * doubles gpt_feature_notensor makes; no n*N host array).  X (N, D) column-major, ls_len 1 or D,
+ * Z (n, D), b (n). */
+int gpt_gpnt_sgld_chains_x(const double* X, const double* y, int64_t N, int64_t D,
+                           const double* length_scale, int64_t ls_len, double sigma_rbf,
+                           const double* Z, const double* b, int64_t n, int64_t m,
+                           const double* signal_var, const double* sigma_theta,
+                           const double* eps_theta, double decay_rate, int64_t burnin,
+                           int64_t maxepoch, const uint64_t* seeds, int32_t nchains,
+                           int64_t store_every, double* theta_store, int32_t* status);
+/* Evaluation of T stored samples theta (n, T) on phitest (n, Ntest) against ytest
+ * (PowerPlantNoTensorExperiment.jl:51-63): scores[i, t] = sum_j phitest[j, i]*theta[j, t],
+ * sample_rmse_out[t] = scale*||ytest - scores[:, t]||/sqrt(Ntest), mean_out (Ntest) the mean of the
+ * scores of the samples avg_first <= t < avg_last (0-based, half open) and *rmse_out the same
+ * figure on it; scores_out (Ntest, T) optional.  A null required pointer or a window that is empty
+ * or outside [0, T] is GPT_ERR_BAD_DIMS before any kernel runs. */
+int gpt_gpnt_pred(const double* theta, const double* phitest, const double* ytest, int64_t n,
+                  int64_t Ntest, int64_t T, int64_t avg_first, int64_t avg_last, double scale,
+                  double* sample_rmse_out, double* mean_out, double* rmse_out, double* scores_out);
+/* The same with phitest = featureNotensor(Xtest, length_scale, sigma_rbf, Z, b) formed on the
+ * device. */
+int gpt_gpnt_pred_x(const double* theta, const double* Xtest, const double* ytest, int64_t Ntest,
+                    int64_t D, const double* length_scale, int64_t ls_len, double sigma_rbf,
+                    const double* Z, const double* b, int64_t n, int64_t T, int64_t avg_first,
+                    int64_t avg_last, double scale, double* sample_rmse_out, double* mean_out,
+                    double* rmse_out, double* scores_out);
+/* The route of the last gpt_gpnt_sgld_chains* call on this thread (measurement, for the route
+ * assertions of tests/test_gpu_gpnt.py); the first min(len, 3) of: [0] feature rows staged per
+ * group (0 = not staged), [1] groups per full batch, [2] dynamic LDS bytes of the sampler's
+ * launches.  Entries past 3 are set to 0. */
+int gpt_gpnt_last_route(int32_t* out, int32_t len);
+/* Device-event times in ms of the last calls on this thread (measurement, scripts/time_gpnt.py):
+ * [0] the sampler's launches of gpt_gpnt_sgld_chains*, [1] the scores and reduction kernels of
+ * gpt_gpnt_pred*.  Entries past 2 are set to 0. */
+int gpt_gpnt_last_timing(double* ms, int32_t len);
+
 /* ---- classification: the full-theta softmax sampler and the evaluation of scores ------ */
 /* GPNT_SGLDclass(phi,y,sigma_theta,m,eps_theta,decay_rate,burnin,maxepoch,param_seed)
  * GPT_SGLD.jl:851-901.  phi (n, N); y (N) integer labels in 1..C, C = max(y) - min(y) + 1 <= 32

@@ -11,7 +11,7 @@ module GPT_SGLD_HIP
 
 export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTregression, GPTregression_chains,
        GPTregression_chains_x, GPT_SGLDERM, pred, RMSE,
-       GPNT_SGLD, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
+       GPNT_SGLD, GPNT_SGLD_chains, GPNT_SGLD_chains_x, GPNT_pred, GPNT_pred_x, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
        init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal, GP_nlogmarginal, GP_gradnlogmarginal, GP_predict,
        GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class,
        neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores
@@ -380,6 +380,105 @@ function GPNT_SGLD(phi::Array{Float64,2}, y::Array{Float64}, signal_var::Real, s
     end
     check(rc)
     return store
+end
+
+# Sibling GPNT_SGLD chains on one phi / y (step-size, noise and seed sweeps of
+# PowerPlantNoTensorExperiment.jl / kin40kNoTensorExperiment.jl): chain k runs GPNT_SGLD with
+# signal_vars[k], sigma_thetas[k], eps_thetas[k], seeds[k].  (theta_store (n, kept, nchains),
+# status (nchains)); store_every keeps the 1-based steps divisible by it (cld(N, m): the epoch ends)
+function GPNT_SGLD_chains(phi::Array{Float64,2}, y::Array{Float64}, signal_vars::Vector{Float64},
+                          sigma_thetas::Vector{Float64}, m::Integer, eps_thetas::Vector{Float64},
+                          decay_rate::Real, burnin::Integer, maxepoch::Integer,
+                          seeds::Vector{UInt64}; store_every::Integer=1)
+    n, N = size(phi); nch = length(seeds)
+    length(y) == N || error("phi and y disagree on N")
+    for (name, v) in (("signal_vars", signal_vars), ("sigma_thetas", sigma_thetas),
+                      ("eps_thetas", eps_thetas))
+        length(v) == nch || error("$name must have one entry per chain (length(seeds) = $nch)")
+    end
+    store_every >= 1 || error("store_every must be >= 1")
+    kept = div((maxepoch + burnin) * cld(N, m), store_every)
+    store = zeros(Float64, n, kept, nch); status = zeros(Int32, nch)
+    check(ccall((:gpt_gpnt_sgld_chains, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Float64, Int64, Int64, Ptr{UInt64}, Int32, Int64, Ptr{Float64},
+                 Ptr{Int32}),
+                phi, vec(y), n, N, m, signal_vars, sigma_thetas, eps_thetas, decay_rate, burnin,
+                maxepoch, seeds, nch, store_every, store, status))
+    return store, status
+end
+
+# The same with phi = featureNotensor(X, length_scale, sigma_RBF, Z, b) formed on the device
+function GPNT_SGLD_chains_x(X::Array{Float64,2}, y::Array{Float64}, length_scale, sigma_RBF::Real,
+                            Z::Array{Float64,2}, b::Array{Float64}, signal_vars::Vector{Float64},
+                            sigma_thetas::Vector{Float64}, m::Integer, eps_thetas::Vector{Float64},
+                            decay_rate::Real, burnin::Integer, maxepoch::Integer,
+                            seeds::Vector{UInt64}; store_every::Integer=1)
+    N, D = size(X); n = size(Z, 1); nch = length(seeds)
+    ls = collect(Float64, length_scale isa Real ? [length_scale] : length_scale)
+    length(y) == N || error("X and y disagree on N")
+    (size(Z, 2) == D && length(b) == n) || error("Z must be (n, D) and b of length n")
+    (length(ls) == 1 || length(ls) == D) || error("dimensions of X and length_scale do not match")
+    for (name, v) in (("signal_vars", signal_vars), ("sigma_thetas", sigma_thetas),
+                      ("eps_thetas", eps_thetas))
+        length(v) == nch || error("$name must have one entry per chain (length(seeds) = $nch)")
+    end
+    store_every >= 1 || error("store_every must be >= 1")
+    kept = div((maxepoch + burnin) * cld(N, m), store_every)
+    store = zeros(Float64, n, kept, nch); status = zeros(Int32, nch)
+    check(ccall((:gpt_gpnt_sgld_chains_x, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Float64,
+                 Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Float64, Int64, Int64, Ptr{UInt64}, Int32, Int64, Ptr{Float64}, Ptr{Int32}),
+                X, vec(y), N, D, ls, length(ls), sigma_RBF, Z, vec(b), n, m, signal_vars,
+                sigma_thetas, eps_thetas, decay_rate, burnin, maxepoch, seeds, nch, store_every,
+                store, status))
+    return store, status
+end
+
+# The evaluation of GPNT_SGLD samples (PowerPlantNoTensorExperiment.jl:51-63): the test RMSE of
+# every sample, the prediction averaged over `window` (1-based, inclusive, as 60:100 there) and
+# its test RMSE, all times `scale`
+struct RegEval
+    sample_rmse::Vector{Float64}; mean_fhat::Vector{Float64}; rmse::Float64
+    scores::Array{Float64,2}
+end
+
+# theta_store (n, T) samples of one chain, phitest (n, Ntest)
+function GPNT_pred(theta_store::Array{Float64,2}, phitest::Array{Float64,2}, ytest::Array{Float64};
+                   window=nothing, scale::Real=1.0)
+    n, T = size(theta_store); Nt = size(phitest, 2); a, b = class_window(window, T)
+    size(phitest, 1) == n || error("theta_store and phitest disagree on n")
+    length(ytest) == Nt || error("ytest must have one target per test row")
+    0 <= a < b <= T || error("the window must lie in 1:$T")
+    sr = Array{Float64}(undef, T); mf = Array{Float64}(undef, Nt); rm = Array{Float64}(undef, 1)
+    sc = Array{Float64}(undef, Nt, T)
+    check(ccall((:gpt_gpnt_pred, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Int64,
+                 Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                theta_store, phitest, vec(ytest), n, Nt, T, a, b, scale, sr, mf, rm, sc))
+    return RegEval(sr, mf, rm[1], sc)
+end
+
+# The same with phitest = featureNotensor(Xtest, length_scale, sigma_RBF, Z, b) formed on the device
+function GPNT_pred_x(theta_store::Array{Float64,2}, Xtest::Array{Float64,2}, ytest::Array{Float64},
+                     length_scale, sigma_RBF::Real, Z::Array{Float64,2}, bfeat::Array{Float64};
+                     window=nothing, scale::Real=1.0)
+    n, T = size(theta_store); Nt, D = size(Xtest); a, b = class_window(window, T)
+    ls = collect(Float64, length_scale isa Real ? [length_scale] : length_scale)
+    (size(Z) == (n, D) && length(bfeat) == n) || error("Z must be (n, D) and b of length n")
+    (length(ls) == 1 || length(ls) == D) || error("dimensions of Xtest and length_scale do not match")
+    length(ytest) == Nt || error("ytest must have one target per test row")
+    0 <= a < b <= T || error("the window must lie in 1:$T")
+    sr = Array{Float64}(undef, T); mf = Array{Float64}(undef, Nt); rm = Array{Float64}(undef, 1)
+    sc = Array{Float64}(undef, Nt, T)
+    check(ccall((:gpt_gpnt_pred_x, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                 Float64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Float64,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                theta_store, Xtest, vec(ytest), Nt, D, ls, length(ls), sigma_RBF, Z, vec(bfeat), n,
+                T, a, b, scale, sr, mf, rm, sc))
+    return RegEval(sr, mf, rm[1], sc)
 end
 
 # GPNT_SGLDclass(phi,y,sigma_theta,m,eps_theta,decay_rate,burnin,maxepoch,param_seed)
