@@ -55,7 +55,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import C, P_D, P_I32, P_U64, SGLDConfig, check, lib
+from ._lib import (GPT_ERR_BAD_DIMS, C, GPTError, P_D, P_I32, P_U64, SGLDConfig, check, lib)
 
 
 def _f64(a):
@@ -980,6 +980,96 @@ class NoTensorMarginal:
         return (phi, S) if sin else phi
 
 
+    def predict(self, h, Xtest, ytest=None, chunk=None):
+        """The closed-form predictive of the model at ``h``: GPkit's named tuple (ymu, ys2, fmu,
+        fs2, lp) for ``Xtest`` (Ntest, D), as ``ExactGP.predict`` returns it; lp is None without
+        ``ytest``.  With l = theta_mean(h) and A = L L': fmu = phi*'l and fs2 = signal_var
+        colsum((L^-1 phi*)^2), a sum of squares.  The factor of the last evaluation is reused when
+        ``h`` equals its hyper-parameters bit for bit.  ``chunk`` test rows go through the device
+        at a time (None: the library's choice); the results do not depend on it."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        Xtest, yt = _gpnt_test_args(Xtest, ytest, self.D)
+        Nt = Xtest.shape[0]
+        fmu, fs2 = np.empty(Nt), np.empty(Nt)
+        lp = np.empty(Nt) if yt is not None else None
+        check(lib().gpt_nlml_predict(self._h, _ptr(h), h.size, _ptr(Xtest), Nt,
+                                     _ptr(yt) if yt is not None else None,
+                                     0 if chunk is None else int(chunk), _ptr(fmu), _ptr(fs2),
+                                     _ptr(lp) if lp is not None else None))
+        return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+
+
+GPPrediction = collections.namedtuple("GPPrediction", "ymu ys2 fmu fs2 lp")
+RFFKernelError = collections.namedtuple("RFFKernelError", "frob norm_K max_abs")
+
+
+def _bad_dims(msg):
+    return GPTError(GPT_ERR_BAD_DIMS, msg)
+
+
+def _gpnt_test_args(Xtest, ytest, D):
+    Xtest = _f64(Xtest)
+    if Xtest.ndim != 2 or Xtest.shape[1] != D or Xtest.shape[0] < 1:
+        raise _bad_dims("Xtest must be (Ntest, D) with Ntest >= 1")
+    yt = None
+    if ytest is not None:
+        yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+        if yt.size != Xtest.shape[0]:
+            raise _bad_dims("ytest must have length Ntest")
+    return Xtest, yt
+
+
+def _gpnt_feature_args(X, Z, b):
+    X, Z = _f64(X), _f64(Z)
+    b = _f64(np.asarray(b, dtype=np.float64).ravel())
+    if X.ndim != 2 or Z.ndim != 2 or Z.shape[1] != X.shape[1] or b.size != Z.shape[0]:
+        raise _bad_dims("X must be (N, D), Z (n, D) and b of length n")
+    return X, Z, b
+
+
+def gpnt_predict_oneshot(X, y, Z, b, hyperparams, Xtest, ytest=None):
+    """The one-shot host-pointer prediction the Julia shim binds (gpt_gpnt_predict)."""
+    X, Z, b = _gpnt_feature_args(X, Z, b)
+    N, D = X.shape
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    if y.size != N:
+        raise _bad_dims("y must have length N")
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    Xtest, yt = _gpnt_test_args(Xtest, ytest, D)
+    Nt = Xtest.shape[0]
+    fmu, fs2 = np.empty(Nt), np.empty(Nt)
+    lp = np.empty(Nt) if yt is not None else None
+    check(lib().gpt_gpnt_predict(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), Z.shape[0], _ptr(h),
+                                 h.size, _ptr(Xtest), Nt, _ptr(yt) if yt is not None else None,
+                                 _ptr(fmu), _ptr(fs2), _ptr(lp) if lp is not None else None))
+    return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+
+
+def rff_kernel_error(X, Z, b, hyperparams):
+    """How far the n random features are from the kernel they approximate
+    (PowerPlantDataExperiment.jl:47-97): with K the exact squared-exponential kernel matrix of
+    ``X`` (N, D) at ``hyperparams`` (ExactGP's covariance, no noise term; signal_var is validated
+    and unused) and K_rff = phi'phi, phi = featureNotensor(X, l, sigma_RBF, Z, b), the named tuple
+    (frob = |K - K_rff|_F, the reference's FrobError; norm_K = |K|_F; max_abs = max|K - K_rff|)
+    over all N^2 entries.  Neither matrix is stored.  n <= 8192, N <= 65536, D <= 16 and
+    8 n N <= 2 GiB."""
+    X, Z, b = _gpnt_feature_args(X, Z, b)
+    N, D = X.shape
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    out = np.empty(3)
+    check(lib().gpt_rff_kernel_error(_ptr(X), N, D, _ptr(Z), _ptr(b), Z.shape[0], _ptr(h), h.size,
+                                     _ptr(out)))
+    return RFFKernelError(*out.tolist())
+
+
+def rff_last_timing():
+    """Device-event times in ms of the last calls: rff_kernel_error's features and its tile pass,
+    and the chunks of NoTensorMarginal.predict."""
+    ms = np.zeros(3)
+    check(lib().gpt_rff_last_timing(_ptr(ms), 3))
+    return ms
+
+
 def _marginal(obj, what):
     if not isinstance(obj, NoTensorMarginal):
         raise TypeError("%s must be a NoTensorMarginal (it stands for the reference's closure over "
@@ -1014,9 +1104,6 @@ def gpnt_nlogmarginal_oneshot(X, y, Z, b, hyperparams, want_grad=True):
 
 
 # ------------------------------------------------------------------ exact GP regression
-GPPrediction = collections.namedtuple("GPPrediction", "ymu ys2 fmu fs2 lp")
-
-
 class ExactGP:
     """Device-resident exact GP regression: squared-exponential kernel (iso or ARD), Gaussian
     noise, zero mean — GP_nlogmarginal (GPT_SGLD.jl:905-915) and GPkit's InfExact / prediction

@@ -148,6 +148,13 @@ SIGNATURES = {
     "gpt_nlml_destroy": (C.c_int, [C.c_void_p]),
     "gpt_gpnt_nlogmarginal": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_int64, P_D,
                                         C.c_int64, C.c_int64, P_D, P_D]),
+    "gpt_nlml_predict": (C.c_int, [C.c_void_p, P_D, C.c_int64, P_D, C.c_int64, P_D, C.c_int64,
+                                   P_D, P_D, P_D]),
+    "gpt_gpnt_predict": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_int64, P_D,
+                                   C.c_int64, P_D, C.c_int64, P_D, P_D, P_D, P_D]),
+    "gpt_rff_kernel_error": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, C.c_int64, P_D,
+                                       C.c_int64, P_D]),
+    "gpt_rff_last_timing": (C.c_int, [P_D, C.c_int32]),
     "gpt_cjoint_create": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, C.c_int64, P_D, P_D, C.c_int64,
                                     C.POINTER(C.c_void_p)]),
     "gpt_cjoint_eval": (C.c_int, [C.c_void_p, P_D, C.c_int64, P_D, C.c_int32, P_D, P_D, P_D]),

@@ -11,6 +11,10 @@
 //   d/dσ²  = (N−n)/(2σ²) + tr P/2 + (lᵀbv − yᵀy)/(2σ⁴) + lᵀl/(2σ²):
 // one GEMM (W, never stored) whose epilogue contracts with S and X.  All fp64, no atomics, every
 // sum in a fixed order.
+//
+// From the same factor, the model's closed-form predictive (fmu = phisᵀl, fs2 = σ²·colsum((L⁻¹phis)²),
+// lp: gpt_nlml_predict), and the error of phiᵀphi against the exact kernel matrix
+// (gpt_rff_kernel_error, PowerPlantDataExperiment.jl:47-97).  DESIGN §6f.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -326,6 +330,304 @@ static hipError_t launch_grad(int D, unsigned grid, hipStream_t st, const double
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------- closed-form predictive
+// fmu[i] = Σ_j phis[j + n i]·l[j]: nlml_resid_kernel's wave per test column.
+__global__ __launch_bounds__(256) void nlml_pmean_kernel(const double* __restrict__ phis,
+                                                         const double* __restrict__ l, int n,
+                                                         int nc, double* __restrict__ fmu) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= nc) return;
+  const double* col = phis + (size_t)n * i;
+  double s = 0.0;
+  for (int j = lane; j < n; j += 64) s = fma(col[j], l[j], s);
+  s = wave_sum(s);
+  if (lane == 0) fmu[i] = s;
+}
+
+// fs2[i] = σ²·Σ_r V[r,i]², V = L⁻¹·phis on v_mfma_f64_16x16x4f64, never stored.  A workgroup owns
+// 32 test columns; its four waves take the 32-row tiles of L⁻¹ round robin (tile rt to wave
+// rt mod 4, which evens out the triangle).  The MFMA's first operand is L⁻¹ (rows ↔ features r;
+// row r is Xt + n·r, contiguous in K, and zero past k = r, so the K loop of tile rt stops at
+// min(n, 32 rt + 32)) and its second phis (columns ↔ test columns i, contiguous in K): lane λ
+// receives V[r = (λ>>4) + 4·reg][i = λ&15].  Operand loads, clamps and the K tail are
+// nlml_grad_kernel's.  The squares are summed in a fixed order: in the lane over reg, the two row
+// halves and the wave's tiles, then over the four lane groups λ>>4 (two exchange rounds), then
+// over the waves in wave order through LDS.  A column's sum depends on n alone: not on the chunk,
+// on nc or on its place in the tile.  Rows r >= n read row 0 and are selected to an exact zero;
+// columns i >= nc read column 0 and are not written.  lp (optional) needs fmu and ytest.
+template <bool V2>
+__global__ __launch_bounds__(256) void nlml_pvar_kernel(
+    const double* __restrict__ Xt, const double* __restrict__ phis, int n, int nc, double s2,
+    const double* __restrict__ fmu, const double* __restrict__ ytest, double* __restrict__ fs2,
+    double* __restrict__ lp) {
+  __shared__ double red[4][32];
+  const int lane = threadIdx.x & 63, wv = uni(threadIdx.x >> 6), kl = lane >> 4, li = lane & 15;
+  const int i0 = blockIdx.x * 32;
+  const int nrt = (n + 31) / 32;
+  const double* pb[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int i = i0 + 16 * u + li;
+    pb[u] = phis + (size_t)n * (i < nc ? i : 0);
+  }
+  auto ld = [&](const double* p, int j, double& x0, double& x1) {
+    if constexpr (V2) {              // n even: j even, rows 16-B aligned
+      const nd2 v = *(const nd2*)(p + min(j, n - 2));
+      x0 = v[0]; x1 = v[1];
+    } else {
+      x0 = p[min(j, n - 1)];
+      x1 = p[min(j + 1, n - 1)];
+    }
+  };
+  struct Ops { double a0[2], a1[2], b0[2], b1[2]; };
+  double ss[2] = {0.0, 0.0};
+  for (int rt = wv; rt < nrt; rt += 4) {
+    const int r0 = 32 * rt;
+    const int kend = min(n, r0 + 32), nfull = kend & ~15;
+    const double* pa[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int r = r0 + 16 * t + li;
+      pa[t] = Xt + (size_t)n * (r < n ? r : 0);
+    }
+    nd4 acc[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) acc[t][u] = nd4{0.0, 0.0, 0.0, 0.0};
+    auto load = [&](int j, Ops& o) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) ld(pa[t], j, o.a0[t], o.a1[t]);
+#pragma unroll
+      for (int u = 0; u < 2; ++u) ld(pb[u], j, o.b0[u], o.b1[u]);
+    };
+    auto ktail = [&](int j, Ops& o) {    // zero the L⁻¹ halves past n (one operand suffices)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        o.a0[t] = j < n ? o.a0[t] : 0.0;
+        o.a1[t] = j + 1 < n ? o.a1[t] : 0.0;
+      }
+    };
+    auto mma = [&](const Ops& o) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+          acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0[t], o.b0[u], acc[t][u], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+          acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1[t], o.b1[u], acc[t][u], 0, 0, 0);
+    };
+    Ops Xo, Yo;
+    load(2 * kl, Xo);
+    for (int k0 = 0; k0 < nfull; k0 += 16) {
+      load(k0 + 8 + 2 * kl, Yo);
+      mma(Xo);
+      load(k0 + 16 + 2 * kl, Xo);
+      mma(Yo);
+    }
+    if (nfull < kend) {                  // kend = n, not a multiple of 16
+      load(nfull + 8 + 2 * kl, Yo);
+      ktail(nfull + 2 * kl, Xo);
+      ktail(nfull + 8 + 2 * kl, Yo);
+      mma(Xo);
+      mma(Yo);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const bool rok = r0 + 16 * t + kl + 4 * reg < n;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const double v = rok ? acc[t][u][reg] : 0.0;
+          ss[u] = fma(v, v, ss[u]);
+        }
+      }
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    double v = self_sum<32>(ss[u], lane);
+    v = self_sum<16>(v, lane);
+    if (kl == 0) red[wv][16 * u + li] = v;
+  }
+  __syncthreads();
+  const int i = i0 + (int)threadIdx.x;
+  if (threadIdx.x < 32 && i < nc) {
+    const double var = s2 * (((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) +
+                             red[3][threadIdx.x]);
+    fs2[i] = var;
+    if (lp) {
+      const double ys2 = var + s2, d = ytest[i] - fmu[i];
+      lp[i] = -(d * d) / (2.0 * ys2) - 0.5 * log(2.0 * M_PI * ys2);
+    }
+  }
+}
+
+// ------------------------------------------------------ kernel approximation error
+// ‖K − K_rff‖_F, ‖K‖_F and max|K − K_rff| over all N² entries, K the squared-exponential kernel
+// matrix (exactgp.hip's covariance, no noise term) and K_rff = phiᵀphi, neither ever stored.  One
+// workgroup per lower 64 × 64 tile t = bi(bi+1)/2 + bj (bi >= bj); wave w owns the 32 × 32
+// sub-tile (w>>1, w&1) as 2 × 2 MFMA 16×16×4 f64 accumulators, K loop over n.  Both operands are
+// columns of phi (contiguous in K): the first the rows i, the second the columns j, so lane λ
+// receives K_rff[i = (λ>>4) + 4·reg][j = λ&15]; loads, clamps and the K tail are
+// nlml_grad_kernel's.  Epilogue: the tile's X rows and columns and 1/ℓ are staged in LDS; every
+// accumulator entry forms k(x_i, x_j) as exactgp.hip's egp_cov does, ((x_ik − x_jk)·(1/ℓ_k))² summed
+// in k order and the device exp (dividing the rows by ℓ first would lose the difference's low
+// digits at a small ℓ), and adds d², k² and max|d| in the lane (entries with i >= N or j >= N are selected to an exact zero).  Diagonal tiles are
+// computed in full and count once, the others count twice.  Lane -> wave_sum / wave_max -> the
+// waves in wave order -> part[3 t + {0, 1, 2}]; kerr_finish_kernel adds the tiles in tile order.
+constexpr int kKerrTile = 64;
+constexpr int kKerrLd = kDMax + 1;     // LDS row stride of the staged inputs
+
+__device__ __forceinline__ void kerr_tile_of(long long t, int& bi, int& bj) {
+  long long a = (long long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+  while (a * (a + 1) / 2 > t) --a;
+  while ((a + 1) * (a + 2) / 2 <= t) ++a;
+  bi = (int)a;
+  bj = (int)(t - a * (a + 1) / 2);
+}
+
+template <bool V2>
+__global__ __launch_bounds__(256) void kerr_tile_kernel(const double* __restrict__ phi,
+                                                        const double* __restrict__ X,
+                                                        const double* __restrict__ ls, int n,
+                                                        int N, int D, double sig2,
+                                                        double* __restrict__ part) {
+  __shared__ double xs[2][kKerrTile * kKerrLd];
+  __shared__ double invl[kDMax];
+  __shared__ double red[4][3];
+  const int tid = threadIdx.x, lane = tid & 63, wv = uni(tid >> 6), kl = lane >> 4, li = lane & 15;
+  int bi, bj;
+  kerr_tile_of((long long)blockIdx.x, bi, bj);
+  for (int x = tid; x < 2 * kKerrTile * D; x += 256) {
+    const int side = x / (kKerrTile * D), rem = x - side * kKerrTile * D;
+    const int k = rem / kKerrTile, r = rem - k * kKerrTile;
+    const int row = min((side ? bj : bi) * kKerrTile + r, N - 1);
+    xs[side][r * kKerrLd + k] = X[row + (size_t)N * k];
+  }
+  if (tid < D) invl[tid] = 1.0 / ls[tid];
+  const int i0 = bi * kKerrTile + 32 * (wv >> 1), j0 = bj * kKerrTile + 32 * (wv & 1);
+  const double *pa[2], *pb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int i = i0 + 16 * t + li, j = j0 + 16 * t + li;
+    pa[t] = phi + (size_t)n * (i < N ? i : 0);
+    pb[t] = phi + (size_t)n * (j < N ? j : 0);
+  }
+  auto ld = [&](const double* p, int j, double& x0, double& x1) {
+    if constexpr (V2) {              // n even: j even, columns 16-B aligned
+      const nd2 v = *(const nd2*)(p + min(j, n - 2));
+      x0 = v[0]; x1 = v[1];
+    } else {
+      x0 = p[min(j, n - 1)];
+      x1 = p[min(j + 1, n - 1)];
+    }
+  };
+  struct Ops { double a0[2], a1[2], b0[2], b1[2]; };
+  const int nfull = n & ~15;
+  nd4 acc[2][2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) acc[t][u] = nd4{0.0, 0.0, 0.0, 0.0};
+  auto load = [&](int j, Ops& o) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) ld(pa[t], j, o.a0[t], o.a1[t]);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) ld(pb[u], j, o.b0[u], o.b1[u]);
+  };
+  auto ktail = [&](int j, Ops& o) {      // zero the first operand's halves past n
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      o.a0[t] = j < n ? o.a0[t] : 0.0;
+      o.a1[t] = j + 1 < n ? o.a1[t] : 0.0;
+    }
+  };
+  auto mma = [&](const Ops& o) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0[t], o.b0[u], acc[t][u], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1[t], o.b1[u], acc[t][u], 0, 0, 0);
+  };
+  Ops Xo, Yo;
+  load(2 * kl, Xo);
+  for (int k0 = 0; k0 < nfull; k0 += 16) {
+    load(k0 + 8 + 2 * kl, Yo);
+    mma(Xo);
+    load(k0 + 16 + 2 * kl, Xo);
+    mma(Yo);
+  }
+  if (nfull < n) {
+    load(nfull + 8 + 2 * kl, Yo);
+    ktail(nfull + 2 * kl, Xo);
+    ktail(nfull + 8 + 2 * kl, Yo);
+    mma(Xo);
+    mma(Yo);
+  }
+  __syncthreads();                       // the staged inputs
+  double sd = 0.0, sk = 0.0, mx = 0.0;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int il = 32 * (wv >> 1) + 16 * t + kl + 4 * reg;      // row within the tile
+      const double* xi = xs[0] + il * kKerrLd;
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int jl = 32 * (wv & 1) + 16 * u + li;
+        const double* xj = xs[1] + jl * kKerrLd;
+        double s = 0.0;
+        for (int k = 0; k < D; ++k) {
+          const double d = (xi[k] - xj[k]) * invl[k];
+          s = fma(d, d, s);
+        }
+        const bool ok = bi * kKerrTile + il < N && bj * kKerrTile + jl < N;
+        const double kv = ok ? sig2 * exp(-0.5 * s) : 0.0;
+        const double dv = ok ? kv - acc[t][u][reg] : 0.0;
+        sd = fma(dv, dv, sd);
+        sk = fma(kv, kv, sk);
+        mx = fmax(mx, fabs(dv));
+      }
+    }
+  sd = wave_sum(sd);
+  sk = wave_sum(sk);
+  mx = wave_max(mx);
+  if (lane == 0) { red[wv][0] = sd; red[wv][1] = sk; red[wv][2] = mx; }
+  __syncthreads();
+  if (tid == 0) {
+    const double w = bi == bj ? 1.0 : 2.0;
+    double* out = part + 3 * (size_t)blockIdx.x;
+    out[0] = w * (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]);
+    out[1] = w * (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]);
+    out[2] = fmax(fmax(red[0][2], red[1][2]), fmax(red[2][2], red[3][2]));
+  }
+}
+
+// out = {sqrt Σ_t part[3t], sqrt Σ_t part[3t+1], max_t part[3t+2]}: lanes 0, 1, 2 take one
+// quantity each and walk the tiles in tile order.
+__global__ __launch_bounds__(64) void kerr_finish_kernel(const double* __restrict__ part,
+                                                         long long ntiles,
+                                                         double* __restrict__ out) {
+  const int q = threadIdx.x;
+  if (q >= 3) return;
+  double a = 0.0;
+  for (long long t = 0; t < ntiles; ++t) {
+    const double v = part[3 * t + q];
+    a = q == 2 ? fmax(a, v) : a + v;
+  }
+  out[q] = q == 2 ? a : sqrt(a);
+}
+
 }  // namespace gpt
 
 using namespace gpt;
@@ -339,6 +641,14 @@ struct gpt_nlml {
          *e = nullptr, *part = nullptr, *gl = nullptr, *scal = nullptr;
   int32_t* status = nullptr;
   bool have_features = false, have_sin = false;
+  // gpt_nlml_predict: A holds the factor of hyper-parameters `last` (have_factor), Xt its L⁻ᵀ
+  // (have_xt); phis is the test chunk's features, grown on demand
+  bool have_factor = false, have_xt = false;
+  double last[kDMax + 2] = {0};
+  int64_t last_Lh = 0;
+  double* phis = nullptr;
+  size_t phis_cols = 0;
+  DevMem phis_mem;
   DevSet mem;
   std::vector<hipEvent_t> ev;         // gpt_nlml_eval_timed's phase marks
   ~gpt_nlml() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
@@ -448,6 +758,7 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   GPT_HIPCHK(hipMemcpyAsync(h->ls, lsv, 8 * (size_t)D, hipMemcpyHostToDevice, st));
   GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
   h->have_features = h->have_sin = false;
+  h->have_factor = h->have_xt = false;
   mark();
   {
     const long long total = (long long)n * N;
@@ -536,6 +847,10 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
     grad[Lh - 1] = (dN - dn) / (2 * s2) + trP / 2 + (bl - yy) / (2 * s2 * s2) + ll / (2 * s2);
   }
   if (theta_mean) std::memcpy(theta_mean, lh.data(), 8 * (size_t)n);
+  std::memcpy(h->last, hyper, 8 * (size_t)Lh);
+  h->last_Lh = Lh;
+  h->have_factor = true;
+  h->have_xt = want_grad != 0;
   return GPT_OK;
 }
 
@@ -576,4 +891,174 @@ extern "C" int gpt_gpnt_nlogmarginal(const double* X, int64_t N, int64_t D, cons
   rc = gpt_nlml_eval(h, hyper, Lh, want_grad ? 1 : 0, nlml_out, grad_out, nullptr);
   gpt_nlml_destroy(h);
   return rc;
+}
+
+// ------------------------------------------------------------------ closed-form predictive
+// gpt_rff_last_timing of this thread: the kernel error's features and its tile pass, the
+// prediction's chunks (uploads of the chunks' rows included)
+static thread_local double g_rff_ms[3] = {0.0, 0.0, 0.0};
+
+extern "C" int gpt_rff_last_timing(double* ms, int32_t len) {
+  if (!ms || len < 0) { set_error("gpt_rff_last_timing: bad output"); return GPT_ERR_BAD_DIMS; }
+  for (int32_t x = 0; x < len; ++x) ms[x] = x < 3 ? g_rff_ms[x] : 0.0;
+  return GPT_OK;
+}
+
+constexpr int kNlmlChunk = 4096;       // test columns per chunk when the caller passes 0, and at most
+
+static bool nlml_test_ok(const void* Xtest, int64_t Ntest, const void* ytest, int64_t chunk,
+                         const void* fmu, const void* fs2, const void* lp) {
+  if (!Xtest || !fmu || !fs2) { set_error("nlml: null test input or output"); return false; }
+  if (lp && !ytest) { set_error("nlml: lp needs ytest"); return false; }
+  if (Ntest < 1 || Ntest > (1LL << 31) - 1) { set_error("nlml: Ntest must be in 1..2^31-1"); return false; }
+  if (chunk < 0) { set_error("nlml: chunk must be >= 0"); return false; }
+  return true;
+}
+
+static void nlml_nan_fill_test(int64_t Ntest, double* fmu, double* fs2, double* lp) {
+  const double q = std::nan("");
+  for (int64_t i = 0; i < Ntest; ++i) {
+    fmu[i] = fs2[i] = q;
+    if (lp) lp[i] = q;
+  }
+}
+
+extern "C" int gpt_nlml_predict(gpt_nlml* h, const double* hyper, int64_t Lh, const double* Xtest,
+                                int64_t Ntest, const double* ytest, int64_t chunk, double* fmu,
+                                double* fs2, double* lp) {
+  if (!h) { set_error("nlml: null handle"); return GPT_ERR_BAD_DIMS; }
+  if (!nlml_hyper_ok(hyper, Lh, h->D) || !nlml_test_ok(Xtest, Ntest, ytest, chunk, fmu, fs2, lp))
+    return GPT_ERR_BAD_DIMS;
+  const int n = h->n, D = h->D;
+  if (!(h->have_factor && h->last_Lh == Lh && std::memcmp(h->last, hyper, 8 * (size_t)Lh) == 0)) {
+    double val = 0.0;
+    const int rc = nlml_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
+    if (rc != GPT_OK) {
+      nlml_nan_fill_test(Ntest, fmu, fs2, lp);
+      return rc;
+    }
+  }
+  hipStream_t st = nullptr;
+  if (!h->have_xt) {
+    GPT_HIPCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
+    GPT_HIPCHK(launch_big_lds<nlml_trinv_kernel>(kMaxLds, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
+                                                 trinv_lds_bytes(n), st, h->A, n, h->Xt));
+    h->have_xt = true;
+  }
+  const int cw = (int)std::min<int64_t>(chunk == 0 ? kNlmlChunk : std::min<int64_t>(chunk, kNlmlChunk),
+                                        Ntest);
+  if (h->phis_cols < (size_t)cw) {
+    h->phis = nullptr;
+    h->phis_cols = 0;
+    h->phis_mem = DevMem();              // the old block is freed before the larger one is taken
+    GPT_HIPCHK(h->phis_mem.alloc<double>((size_t)n * cw));
+    h->phis = h->phis_mem.as<double>();
+    h->phis_cols = (size_t)cw;
+  }
+  DevSet tmp;
+  double *dX = nullptr, *dy = nullptr, *dmu = nullptr, *dv = nullptr, *dlp = nullptr;
+  GPT_HIPCHK(tmp.alloc(&dX, (size_t)cw * D));
+  GPT_HIPCHK(tmp.alloc(&dmu, (size_t)Ntest));
+  GPT_HIPCHK(tmp.alloc(&dv, (size_t)Ntest));
+  if (lp) {
+    GPT_HIPCHK(tmp.alloc(&dlp, (size_t)Ntest));
+    GPT_HIPCHK(tmp.upload(&dy, ytest, (size_t)Ntest));
+  }
+  const double sigma = hyper[Lh - 2], s2 = hyper[Lh - 1];
+  const double c = std::sqrt(2.0 / (double)n) * sigma;      // h->ls holds the factor's length scales
+  EventTimer tm(&g_rff_ms[2], st);
+  for (int64_t c0 = 0; c0 < Ntest; c0 += cw) {
+    const int nc = (int)std::min<int64_t>(cw, Ntest - c0);
+    // the chunk's rows of Xtest (Ntest, D) as a dense (nc, D) block
+    GPT_HIPCHK(hipMemcpy2DAsync(dX, 8 * (size_t)nc, Xtest + c0, 8 * (size_t)Ntest, 8 * (size_t)nc,
+                                (size_t)D, hipMemcpyHostToDevice, st));
+    const long long total = (long long)n * nc;
+    hipLaunchKernelGGL(nlml_feature_kernel, dim3((unsigned)std::min((total + 255) / 256, 4096LL)),
+                       dim3(256), 0, st, dX, (long long)nc, D, h->ls, c, h->Z, h->b, n, h->phis,
+                       (double*)nullptr);
+    hipLaunchKernelGGL(nlml_pmean_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->phis, h->l, n,
+                       nc, dmu + c0);
+    if (n % 2 == 0)
+      hipLaunchKernelGGL(nlml_pvar_kernel<true>, dim3((nc + 31) / 32), dim3(256), 0, st, h->Xt,
+                         h->phis, n, nc, s2, dmu + c0, lp ? dy + c0 : (const double*)nullptr,
+                         dv + c0, lp ? dlp + c0 : (double*)nullptr);
+    else
+      hipLaunchKernelGGL(nlml_pvar_kernel<false>, dim3((nc + 31) / 32), dim3(256), 0, st, h->Xt,
+                         h->phis, n, nc, s2, dmu + c0, lp ? dy + c0 : (const double*)nullptr,
+                         dv + c0, lp ? dlp + c0 : (double*)nullptr);
+    GPT_HIPCHK(hipGetLastError());
+  }
+  tm.stop();
+  GPT_HIPCHK(hipMemcpyAsync(fmu, dmu, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipMemcpyAsync(fs2, dv, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
+  if (lp) GPT_HIPCHK(hipMemcpyAsync(lp, dlp, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipStreamSynchronize(st));
+  return GPT_OK;
+}
+
+extern "C" int gpt_gpnt_predict(const double* X, int64_t N, int64_t D, const double* y,
+                                const double* Z, const double* b, int64_t n, const double* hyper,
+                                int64_t Lh, const double* Xtest, int64_t Ntest, const double* ytest,
+                                double* fmu, double* fs2, double* lp) {
+  if (!nlml_dims_ok(X, N, D, y, Z, b, n) || !nlml_hyper_ok(hyper, Lh, D) ||
+      !nlml_test_ok(Xtest, Ntest, ytest, 0, fmu, fs2, lp))
+    return GPT_ERR_BAD_DIMS;
+  gpt_nlml* h = nullptr;
+  int rc = gpt_nlml_create(X, N, D, y, Z, b, n, &h);
+  if (rc != GPT_OK) return rc;
+  rc = gpt_nlml_predict(h, hyper, Lh, Xtest, Ntest, ytest, 0, fmu, fs2, lp);
+  gpt_nlml_destroy(h);
+  return rc;
+}
+
+// ------------------------------------------------------------------ kernel approximation error
+// Limits: n <= 8192, N <= 65536 and phi (n × N doubles) at most 2 GiB.
+constexpr int64_t kKerrNMax = 8192, kKerrRowsMax = 65536;
+constexpr int64_t kKerrPhiBytes = 2LL << 30;
+
+extern "C" int gpt_rff_kernel_error(const double* X, int64_t N, int64_t D, const double* Z,
+                                    const double* b, int64_t n, const double* hyper, int64_t Lh,
+                                    double* out3) {
+  if (!X || !Z || !b || !out3) { set_error("rff_kernel_error: null argument"); return GPT_ERR_BAD_DIMS; }
+  if (n < 1 || n > kKerrNMax) { set_error("rff_kernel_error: n must be in 1..8192"); return GPT_ERR_BAD_DIMS; }
+  if (N < 1 || N > kKerrRowsMax) { set_error("rff_kernel_error: N must be in 1..65536"); return GPT_ERR_BAD_DIMS; }
+  if (D < 1 || D > kDMax) { set_error("rff_kernel_error: D must be in 1..16"); return GPT_ERR_BAD_DIMS; }
+  if (8 * n * N > kKerrPhiBytes) {
+    set_error("rff_kernel_error: phi (n x N doubles) must not exceed 2 GiB"); return GPT_ERR_BAD_DIMS;
+  }
+  if (!nlml_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
+  double lsv[kDMax];
+  for (int k = 0; k < D; ++k) lsv[k] = hyper[Lh == D + 2 ? k : 0];
+  const double sigma = hyper[Lh - 2];
+  const long long nb = (N + kKerrTile - 1) / kKerrTile, ntiles = nb * (nb + 1) / 2;
+  DevSet mem;
+  double *dX = nullptr, *dZ = nullptr, *db = nullptr, *dls = nullptr, *dphi = nullptr,
+         *dpart = nullptr, *dout = nullptr;
+  GPT_HIPCHK(mem.upload(&dX, X, (size_t)N * D));
+  GPT_HIPCHK(mem.upload(&dZ, Z, (size_t)n * D));
+  GPT_HIPCHK(mem.upload(&db, b, (size_t)n));
+  GPT_HIPCHK(mem.upload(&dls, (const double*)lsv, (size_t)D));
+  GPT_HIPCHK(mem.alloc(&dphi, (size_t)n * N));
+  GPT_HIPCHK(mem.alloc(&dpart, 3 * (size_t)ntiles));
+  GPT_HIPCHK(mem.alloc(&dout, 4));
+  hipStream_t st = nullptr;
+  const long long total = (long long)n * N;
+  EventTimer tf(&g_rff_ms[0], st);
+  hipLaunchKernelGGL(nlml_feature_kernel, dim3((unsigned)std::min((total + 255) / 256, 4096LL)),
+                     dim3(256), 0, st, dX, (long long)N, (int)D, dls,
+                     std::sqrt(2.0 / (double)n) * sigma, dZ, db, (int)n, dphi, (double*)nullptr);
+  tf.stop();
+  EventTimer tt(&g_rff_ms[1], st);
+  if (n % 2 == 0)
+    hipLaunchKernelGGL(kerr_tile_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, st, dphi, dX,
+                       dls, (int)n, (int)N, (int)D, sigma * sigma, dpart);
+  else
+    hipLaunchKernelGGL(kerr_tile_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, st, dphi, dX,
+                       dls, (int)n, (int)N, (int)D, sigma * sigma, dpart);
+  hipLaunchKernelGGL(kerr_finish_kernel, dim3(1), dim3(64), 0, st, dpart, ntiles, dout);
+  tt.stop();
+  GPT_HIPCHK(hipGetLastError());
+  GPT_HIPCHK(hipMemcpyAsync(out3, dout, 8 * 3, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipStreamSynchronize(st));
+  return GPT_OK;
 }

@@ -504,6 +504,42 @@ int gpt_gpnt_nlogmarginal(const double* X, int64_t N, int64_t D, const double* y
                           const double* b, int64_t n, const double* hyper, int64_t Lh,
                           int64_t want_grad, double* nlml_out, double* grad_out);
 
+/* ---- full-theta model: closed-form predictive and kernel approximation error ---------- */
+/* The posterior of GPNT_nlogmarginal's model (y = phi(x)'theta + eps, theta ~ N(0, I), eps ~
+ * N(0, signal_var)) is theta | y ~ N(l, signal_var*A^-1) with A = phi*phi' + signal_var*I = L*L'
+ * and l = A^-1 phi y.  For Xtest (Ntest, D) column-major and phis = featureNotensor(Xtest):
+ *   fmu = phis'l,  fs2 = signal_var * colsum((L^-1 phis)^2)   (ymu = fmu, ys2 = fs2 + signal_var)
+ * and, with ytest and lp, lp = -(ytest - fmu)^2/(2 ys2) - log(2 pi ys2)/2: GPkit's prediction
+ * with LikGauss, the outputs of gpt_egp_predict.  fs2 is a sum of squares: positive, no clamp.
+ * The test rows go through the device in chunks of `chunk` columns (0: the library's choice; at
+ * most 4096); a row's results depend neither on the chunking, nor on Ntest, nor on the row's
+ * position.  The factor of the last successful evaluation is reused when hyper equals its hyper
+ * bit for bit, otherwise the call evaluates first; the results are the same bits either way.
+ * Ntest < 1 or a NULL array is GPT_ERR_BAD_DIMS; a failed Cholesky returns GPT_ERR_NOT_SPD with
+ * NaN-filled outputs and leaves the handle usable. */
+int gpt_nlml_predict(gpt_nlml* h, const double* hyper, int64_t Lh, const double* Xtest,
+                     int64_t Ntest, const double* ytest, int64_t chunk, double* fmu, double* fs2,
+                     double* lp);
+/* One-shot host-pointer form (create, predict, destroy). */
+int gpt_gpnt_predict(const double* X, int64_t N, int64_t D, const double* y, const double* Z,
+                     const double* b, int64_t n, const double* hyper, int64_t Lh,
+                     const double* Xtest, int64_t Ntest, const double* ytest, double* fmu,
+                     double* fs2, double* lp);
+/* The live code of PowerPlantDataExperiment.jl:47-97: with K_ij = sigma_RBF^2 exp(-1/2 sum_k
+ * ((x_ik - x_jk)/l_k)^2) (the exact GP's covariance, no noise term) and K_rff = phi'phi,
+ * phi = featureNotensor(X), over all N^2 entries
+ *   out3 = { |K - K_rff|_F (the reference's FrobError), |K|_F, max |K - K_rff| }.
+ * Neither matrix is stored (phi is: n*N doubles).  X (N, D), Z (n, D), b (n); hyper as above
+ * (signal_var is validated and unused).  No Cholesky, so n may exceed 1024: n <= 8192,
+ * N <= 65536, D <= 16 and 8*n*N <= 2 GiB; beyond them GPT_ERR_BAD_DIMS.  Equal inputs give
+ * equal bits. */
+int gpt_rff_kernel_error(const double* X, int64_t N, int64_t D, const double* Z, const double* b,
+                         int64_t n, const double* hyper, int64_t Lh, double* out3);
+/* Diagnostics (scripts/time_rffgp.py): device-event times in ms of this thread's last calls:
+ * ms[0] gpt_rff_kernel_error's features, ms[1] its tile pass and finish, ms[2] the chunks of
+ * gpt_nlml_predict (the uploads of their rows included). */
+int gpt_rff_last_timing(double* ms, int32_t len);
+
 /* ---- hyper-parameter learning of the softmax classifier: the joint likelihood ---------- */
 /* neglogjointlkhd / gradneglogjointlkhd (ImageExperiment.jl:135-204), the objective of
  * GPNT_hyperparameters_ng (GPT_SGLD.jl:1005-1063): with phi = featureNotensor(X) at

@@ -12,7 +12,7 @@ module GPT_SGLD_HIP
 export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTregression, GPTregression_chains,
        GPTregression_chains_x, GPT_SGLDERM, pred, RMSE,
        GPNT_SGLD, GPNT_SGLD_chains, GPNT_SGLD_chains_x, GPNT_pred, GPNT_pred_x, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
-       init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal, GP_nlogmarginal, GP_gradnlogmarginal, GP_predict,
+       init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal, GP_nlogmarginal, GP_gradnlogmarginal, GP_predict, GPNT_predict, RFF_kernel_error,
        GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class,
        neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores
 
@@ -598,6 +598,50 @@ function gpnt_marginal(X::Array{Float64,2}, y::Array{Float64}, Z::Array{Float64,
 end
 GPNT_nlogmarginal(X, y, Z, b, hyperparams) = gpnt_marginal(X, y, Z, b, hyperparams, false)[1]
 GPNT_gradnlogmarginal(X, y, Z, b, hyperparams) = gpnt_marginal(X, y, Z, b, hyperparams, true)[2]
+
+# The closed-form predictive of the same model at hyperparams: (ymu, ys2, fmu, fs2, lp) as
+# GP_predict returns it, with fmu = phi*'l and fs2 = signal_var * colsum((L^-1 phi*).^2);
+# lp is nothing without ytest
+function GPNT_predict(X::Array{Float64,2}, y::Array{Float64}, Z::Array{Float64,2},
+                      b::Array{Float64}, hyperparams::Vector{Float64}, Xtest::Array{Float64,2},
+                      ytest=nothing)
+    N, D = size(X); n = size(Z, 1); Ntest = size(Xtest, 1)
+    size(Z, 2) == D || error("Z must be (n, D)")
+    length(b) == n || error("b must have n entries")
+    length(y) == N || error("y must have N entries")
+    size(Xtest, 2) == D || error("Xtest must be (Ntest, D)")
+    fmu = Array{Float64}(undef, Ntest); fs2 = Array{Float64}(undef, Ntest)
+    yt = ytest === nothing ? Float64[] : Vector{Float64}(vec(ytest))
+    (ytest === nothing || length(yt) == Ntest) || error("ytest must have Ntest entries")
+    lpv = Array{Float64}(undef, ytest === nothing ? 0 : Ntest)
+    GC.@preserve yt lpv begin
+        yp = ytest === nothing ? Ptr{Float64}(C_NULL) : pointer(yt)
+        lpp = ytest === nothing ? Ptr{Float64}(C_NULL) : pointer(lpv)
+        check(ccall((:gpt_gpnt_predict, LIB), Cint,
+                    (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}),
+                    X, N, D, vec(y), Z, vec(b), n, hyperparams, length(hyperparams), Xtest, Ntest,
+                    yp, fmu, fs2, lpp))
+    end
+    lp = ytest === nothing ? nothing : lpv
+    return fmu, fs2 .+ hyperparams[end], fmu, fs2, lp
+end
+
+# PowerPlantDataExperiment.jl:47-97: (FrobError = |K - phi'phi|_F, |K|_F, max|K - phi'phi|) with K
+# the exact squared-exponential kernel matrix of X at hyperparams and phi = featureNotensor(X, ...)
+function RFF_kernel_error(X::Array{Float64,2}, Z::Array{Float64,2}, b::Array{Float64},
+                          hyperparams::Vector{Float64})
+    N, D = size(X); n = size(Z, 1)
+    size(Z, 2) == D || error("Z must be (n, D)")
+    length(b) == n || error("b must have n entries")
+    out = Array{Float64}(undef, 3)
+    check(ccall((:gpt_rff_kernel_error, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64},
+                 Int64, Ptr{Float64}),
+                X, N, D, Z, vec(b), n, hyperparams, length(hyperparams), out))
+    return out[1], out[2], out[3]
+end
 
 # Exact GP regression (GP_nlogmarginal GPT_SGLD.jl:905-915; GPkit InfExact / prediction with
 # CovSEiso or CovSEard, LikGauss, zero mean).  hyperparams = [length_scale (D entries, or one);
