@@ -17,7 +17,6 @@ namespace gpt {
 
 constexpr int kCfNT = 1024;
 constexpr int kCfNW = kCfNT / 64;
-typedef double pd4 __attribute__((ext_vector_type(4)));
 
 // Diagnostic phase stamps of the epoch kernel (P.stamps, gpt_cf_last_stamps): thread 0 of chain 0
 // records s_memtime after the barrier closing each phase of the first kCfStampSteps steps.
@@ -718,9 +717,9 @@ __global__ __launch_bounds__(kCfNT) void cf_epoch_kernel(CfParams P, const CfCha
         const double* S = (side ? sV : sU) + zo;
         const double* wz = w_l + zo;
         const int arow = min(m0 + rl, B - 1);
-        pd4 acc[NTc];
+        d4 acc[NTc];
 #pragma unroll
-        for (int nt = 0; nt < NTc; ++nt) acc[nt] = pd4{0.0, 0.0, 0.0, 0.0};
+        for (int nt = 0; nt < NTc; ++nt) acc[nt] = d4{0.0, 0.0, 0.0, 0.0};
         // every operand read before the first MFMA (KS·(1 + NTc) reads in flight; the scheduling
         // barrier keeps the compiler from pairing each MFMA with a read and its wait)
         constexpr int KS = (R + 3) / 4;
@@ -786,7 +785,7 @@ __global__ __launch_bounds__(kCfNT) void cf_epoch_kernel(CfParams P, const CfCha
         const double* sUz = sU + zo;
         const double* sVz = sV + zo;
         const double* erz = er + zo;
-        pd4 acc = pd4{0.0, 0.0, 0.0, 0.0};
+        d4 acc = d4{0.0, 0.0, 0.0, 0.0};
         // four K steps per pass, every LDS read of the pass issued before its MFMAs (reads
         // unconditional at clamped rows, the operand past B selected to zero: no branch around
         // a read, which had left each step's read latency in front of its MFMA)
@@ -848,7 +847,7 @@ __global__ __launch_bounds__(kCfNT) void cf_epoch_kernel(CfParams P, const CfCha
         const double* T = (side ? tU : tV) + zo;
         const double* erz = er + zo;
         const int fa = f0 + rl, lb = min(lt * 16 + rl, R - 1);
-        pd4 acc = pd4{0.0, 0.0, 0.0, 0.0};
+        d4 acc = d4{0.0, 0.0, 0.0, 0.0};
         for (int k0 = 0; k0 < B; k0 += 16) {            // (four K steps per pass, as gradw's)
           // the pass's twelve reads issued together, then the operands, then the MFMAs (the
           // scheduling barriers keep the compiler from interleaving them one step at a time)

@@ -14,6 +14,19 @@ __device__ __forceinline__ T* uni_ptr(T* p) {
   return (T*)(((unsigned long long)hi << 32) | lo);
 }
 
+// fp64 vectors: an MFMA 16×16×4 f64 accumulator, and a 16-byte pair for one load or store.
+typedef double d4 __attribute__((ext_vector_type(4)));
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+// pair index t -> (a, b), a >= b, t = a(a+1)/2 + b
+__device__ __forceinline__ void tri_pair(long long t, int& a, int& b) {
+  int ta = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) / 2.0);
+  while ((long long)ta * (ta + 1) / 2 > t) --ta;
+  while ((long long)(ta + 1) * (ta + 2) / 2 <= t) ++ta;
+  a = ta;
+  b = (int)(t - (long long)ta * (ta + 1) / 2);
+}
+
 // Lane id (0..63) from v_mbcnt, formed where it is used: nothing has to keep threadIdx.x (v0)
 // alive, which long kernels would otherwise spill to scratch and reload — each reload a vmcnt(0)
 // wait behind every load still in flight.

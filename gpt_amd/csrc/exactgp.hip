@@ -27,8 +27,6 @@
 
 namespace gpt {
 
-typedef double ed4 __attribute__((ext_vector_type(4)));
-
 constexpr int kEgpNMax = 16384;     // three N × N fp64 buffers: 6.4 GB
 constexpr int kEgpNB = 64;          // panel width (chosen from 16, 32, 64, 128)
 constexpr int kEgpLs = kEgpNB + 1;  // LDS row stride of a diagonal block
@@ -53,15 +51,6 @@ __device__ __forceinline__ double egp_kern(const double* __restrict__ Xa, size_t
     s = fma(d, d, s);
   }
   return H.sig2 * exp(-0.5 * s);
-}
-
-// pair index t -> (a, b), a >= b, t = a(a+1)/2 + b
-__device__ __forceinline__ void egp_tri(long long t, int& a, int& b) {
-  int ta = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) / 2.0);
-  while ((long long)ta * (ta + 1) / 2 > t) --ta;
-  while ((long long)(ta + 1) * (ta + 2) / 2 <= t) ++ta;
-  a = ta;
-  b = (int)(t - (long long)ta * (ta + 1) / 2);
 }
 
 // 1. A (lower 64 × 64 blocks) = K + σ²I from X.  grid (nblk, nblk); blocks above the diagonal leave.
@@ -189,11 +178,11 @@ __device__ __forceinline__ void egp_gemm_tile(const double* __restrict__ pa, siz
     ar[t] = pa + (size_t)min(i0 + 16 * t + li, ilim - 1) + lda * kl;
     bc[t] = pb + (size_t)min(c0 + 16 * t + li, clim - 1) * sbc + sbk * kl;
   }
-  ed4 acc[2][2];
+  d4 acc[2][2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int u = 0; u < 2; ++u) acc[t][u] = ed4{0.0, 0.0, 0.0, 0.0};
+    for (int u = 0; u < 2; ++u) acc[t][u] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
   for (int s = 0; s < kEgpNB / 4; ++s) {
     double a[2], b[2];
@@ -226,7 +215,7 @@ __device__ __forceinline__ void egp_gemm_tile(const double* __restrict__ pa, siz
 // pair, a 32 × 32 tile per wave.
 __global__ __launch_bounds__(256) void egp_syrk_kernel(double* __restrict__ A, int N, int j0) {
   int bi, bj;
-  egp_tri(blockIdx.x, bi, bj);
+  tri_pair(blockIdx.x, bi, bj);
   const int wv = uni(threadIdx.x >> 6), wi = wv & 1, wj = wv >> 1;
   const int r0 = j0 + kEgpNB, i0 = r0 + 64 * bi + 32 * wi, c0 = r0 + 64 * bj + 32 * wj;
   if (i0 >= N || c0 >= N || (bi == bj && wj > wi)) return;
@@ -384,7 +373,7 @@ __global__ __launch_bounds__(256) void egp_ptp_kernel(const double* __restrict__
   const long long task = (long long)blockIdx.x * 4 + uni(threadIdx.x >> 6);
   if (task >= (long long)T * (T + 1) / 2) return;
   int ba, bb;
-  egp_tri(task, ba, bb);
+  tri_pair(task, ba, bb);
   const int a0 = 32 * ba, b0 = 32 * bb;
   const double* wa[2];
   const double* wb[2];
@@ -393,11 +382,11 @@ __global__ __launch_bounds__(256) void egp_ptp_kernel(const double* __restrict__
     wa[t] = W + (size_t)N * min(a0 + 16 * t + li, N - 1);
     wb[t] = W + (size_t)N * min(b0 + 16 * t + li, N - 1);
   }
-  ed4 acc[2][2];
+  d4 acc[2][2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int u = 0; u < 2; ++u) acc[t][u] = ed4{0.0, 0.0, 0.0, 0.0};
+    for (int u = 0; u < 2; ++u) acc[t][u] = d4{0.0, 0.0, 0.0, 0.0};
   for (int ib = a0; ib < N; ib += 8) {
     const int i1 = ib + 2 * kl, i2 = i1 + 1;
     const int c1 = min(i1, N - 1), c2 = min(i2, N - 1);
@@ -442,7 +431,7 @@ __global__ __launch_bounds__(kNT) void egp_grad_kernel(const double* __restrict_
   __shared__ double aj[64];
   __shared__ double red[kNW];
   int bi, bj;
-  egp_tri(blockIdx.x, bi, bj);
+  tri_pair(blockIdx.x, bi, bj);
   const int tid = threadIdx.x, i = 64 * bi + (tid & 63), j0 = 64 * bj;
   for (int e = tid; e < 64 * DP; e += kNT) {
     const int jj = e & 63, k = e >> 6, j = j0 + jj;

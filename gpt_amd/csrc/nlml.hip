@@ -23,11 +23,9 @@
 
 #include "device_util.h"
 #include "host_util.h"
+#include "mfma_tile.h"
 
 namespace gpt {
-
-typedef double nd4 __attribute__((ext_vector_type(4)));
-typedef double nd2 __attribute__((ext_vector_type(2)));
 
 constexpr int kNlmlNMax = 1024;      // the blocked single-workgroup Cholesky's limit
 
@@ -144,11 +142,9 @@ __global__ __launch_bounds__(256) void nlml_mirror_kernel(double* __restrict__ P
 // and its second P (columns ↔ features j; P is symmetric, so row j is contiguous in K), so lane λ
 // receives D[i = (λ>>4) + 4·reg][j = λ&15]: the sum over i of T[j,i]·X[i,k] runs inside the lane
 // over reg and over the tiles of the block (g[·][k], D <= DP registers), and only the four lane
-// groups λ>>4 are combined at the end (two exchange rounds).  Both operands are K-contiguous:
-// lane λ loads the K pair 2(λ>>4) + {0,1} of its row as one 16-B load (n even) and the halves go
-// to two MFMAs, two operand sets in flight, addresses clamped in-row so the loop has no branch
-// (pred_temp_mfma_kernel's scheme).  Lanes of rows i >= N or features j >= n read row 0 and their
-// T is selected to an exact zero.  part[(cb·n + j)·D + k] = Σ_{i in block cb} T[j,i]·X[i,k].
+// groups λ>>4 are combined at the end (two exchange rounds).  Both operands are K-contiguous: the
+// K loop is mfma_kpair_tile (mfma_tile.h).  Lanes of rows i >= N or features j >= n read row 0 and
+// their T is selected to an exact zero.  part[(cb·n + j)·D + k] = Σ_{i in block cb} T[j,i]·X[i,k].
 template <bool V2, int DP>
 __global__ __launch_bounds__(256) void nlml_grad_kernel(
     const double* __restrict__ P, const double* __restrict__ phi, const double* __restrict__ S,
@@ -177,18 +173,6 @@ __global__ __launch_bounds__(256) void nlml_grad_kernel(
 #pragma unroll
     for (int k = 0; k < DP; ++k) g[u][k] = 0.0;
 
-  auto ld = [&](const double* p, int j, double& x0, double& x1) {
-    if constexpr (V2) {              // n even: j even, rows 16-B aligned
-      const nd2 v = *(const nd2*)(p + min(j, n - 2));
-      x0 = v[0]; x1 = v[1];
-    } else {
-      x0 = p[min(j, n - 1)];
-      x1 = p[min(j + 1, n - 1)];
-    }
-  };
-  struct Ops { double a0[2], a1[2], b0[2], b1[2]; };
-  const int nfull = n & ~15;
-
   for (long long it = i_begin; it < i_end; it += 32) {
     const double* pa[2];
 #pragma unroll
@@ -196,51 +180,12 @@ __global__ __launch_bounds__(256) void nlml_grad_kernel(
       const long long i = it + 16 * t + li;
       pa[t] = phi + (size_t)n * (i < i_end ? i : i_begin);
     }
-    nd4 acc[2][2];
+    d4 acc[2][2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int u = 0; u < 2; ++u) acc[t][u] = nd4{0.0, 0.0, 0.0, 0.0};
-    auto load = [&](int j, Ops& o) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) ld(pa[t], j, o.a0[t], o.a1[t]);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) ld(pb[u], j, o.b0[u], o.b1[u]);
-    };
-    auto ktail = [&](int j, Ops& o) {    // zero the phi halves past n (one operand suffices)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        o.a0[t] = j < n ? o.a0[t] : 0.0;
-        o.a1[t] = j + 1 < n ? o.a1[t] : 0.0;
-      }
-    };
-    auto mma = [&](const Ops& o) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-          acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0[t], o.b0[u], acc[t][u], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-          acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1[t], o.b1[u], acc[t][u], 0, 0, 0);
-    };
-    Ops Xo, Yo;
-    load(2 * kl, Xo);
-    for (int k0 = 0; k0 < nfull; k0 += 16) {
-      load(k0 + 8 + 2 * kl, Yo);
-      mma(Xo);
-      load(k0 + 16 + 2 * kl, Xo);
-      mma(Yo);
-    }
-    if (nfull < n) {
-      load(nfull + 8 + 2 * kl, Yo);
-      ktail(nfull + 2 * kl, Xo);
-      ktail(nfull + 8 + 2 * kl, Yo);
-      mma(Xo);
-      mma(Yo);
-    }
+      for (int u = 0; u < 2; ++u) acc[t][u] = d4{0.0, 0.0, 0.0, 0.0};
+    mfma_kpair_tile<V2, 2, 2>(pa, pb, n, n, kl, acc);
     // epilogue in the MFMA output layout: acc[t][u][reg] = W[j0 + 16u + li, it + 16t + kl + 4reg]
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -349,9 +294,9 @@ __global__ __launch_bounds__(256) void nlml_pmean_kernel(const double* __restric
 // 32 test columns; its four waves take the 32-row tiles of L⁻¹ round robin (tile rt to wave
 // rt mod 4, which evens out the triangle).  The MFMA's first operand is L⁻¹ (rows ↔ features r;
 // row r is Xt + n·r, contiguous in K, and zero past k = r, so the K loop of tile rt stops at
-// min(n, 32 rt + 32)) and its second phis (columns ↔ test columns i, contiguous in K): lane λ
-// receives V[r = (λ>>4) + 4·reg][i = λ&15].  Operand loads, clamps and the K tail are
-// nlml_grad_kernel's.  The squares are summed in a fixed order: in the lane over reg, the two row
+// kend = min(n, 32 rt + 32)) and its second phis (columns ↔ test columns i, contiguous in K): lane
+// λ receives V[r = (λ>>4) + 4·reg][i = λ&15].  The K loop is mfma_kpair_tile (mfma_tile.h) up to
+// kend.  The squares are summed in a fixed order: in the lane over reg, the two row
 // halves and the wave's tiles, then over the four lane groups λ>>4 (two exchange rounds), then
 // over the waves in wave order through LDS.  A column's sum depends on n alone: not on the chunk,
 // on nc or on its place in the tile.  Rows r >= n read row 0 and are selected to an exact zero;
@@ -371,71 +316,22 @@ __global__ __launch_bounds__(256) void nlml_pvar_kernel(
     const int i = i0 + 16 * u + li;
     pb[u] = phis + (size_t)n * (i < nc ? i : 0);
   }
-  auto ld = [&](const double* p, int j, double& x0, double& x1) {
-    if constexpr (V2) {              // n even: j even, rows 16-B aligned
-      const nd2 v = *(const nd2*)(p + min(j, n - 2));
-      x0 = v[0]; x1 = v[1];
-    } else {
-      x0 = p[min(j, n - 1)];
-      x1 = p[min(j + 1, n - 1)];
-    }
-  };
-  struct Ops { double a0[2], a1[2], b0[2], b1[2]; };
   double ss[2] = {0.0, 0.0};
   for (int rt = wv; rt < nrt; rt += 4) {
     const int r0 = 32 * rt;
-    const int kend = min(n, r0 + 32), nfull = kend & ~15;
+    const int kend = min(n, r0 + 32);
     const double* pa[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int r = r0 + 16 * t + li;
       pa[t] = Xt + (size_t)n * (r < n ? r : 0);
     }
-    nd4 acc[2][2];
+    d4 acc[2][2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int u = 0; u < 2; ++u) acc[t][u] = nd4{0.0, 0.0, 0.0, 0.0};
-    auto load = [&](int j, Ops& o) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) ld(pa[t], j, o.a0[t], o.a1[t]);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) ld(pb[u], j, o.b0[u], o.b1[u]);
-    };
-    auto ktail = [&](int j, Ops& o) {    // zero the L⁻¹ halves past n (one operand suffices)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        o.a0[t] = j < n ? o.a0[t] : 0.0;
-        o.a1[t] = j + 1 < n ? o.a1[t] : 0.0;
-      }
-    };
-    auto mma = [&](const Ops& o) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-          acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0[t], o.b0[u], acc[t][u], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-          acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1[t], o.b1[u], acc[t][u], 0, 0, 0);
-    };
-    Ops Xo, Yo;
-    load(2 * kl, Xo);
-    for (int k0 = 0; k0 < nfull; k0 += 16) {
-      load(k0 + 8 + 2 * kl, Yo);
-      mma(Xo);
-      load(k0 + 16 + 2 * kl, Xo);
-      mma(Yo);
-    }
-    if (nfull < kend) {                  // kend = n, not a multiple of 16
-      load(nfull + 8 + 2 * kl, Yo);
-      ktail(nfull + 2 * kl, Xo);
-      ktail(nfull + 8 + 2 * kl, Yo);
-      mma(Xo);
-      mma(Yo);
-    }
+      for (int u = 0; u < 2; ++u) acc[t][u] = d4{0.0, 0.0, 0.0, 0.0};
+    mfma_kpair_tile<V2, 2, 2>(pa, pb, n, kend, kl, acc);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -473,8 +369,8 @@ __global__ __launch_bounds__(256) void nlml_pvar_kernel(
 // workgroup per lower 64 × 64 tile t = bi(bi+1)/2 + bj (bi >= bj); wave w owns the 32 × 32
 // sub-tile (w>>1, w&1) as 2 × 2 MFMA 16×16×4 f64 accumulators, K loop over n.  Both operands are
 // columns of phi (contiguous in K): the first the rows i, the second the columns j, so lane λ
-// receives K_rff[i = (λ>>4) + 4·reg][j = λ&15]; loads, clamps and the K tail are
-// nlml_grad_kernel's.  Epilogue: the tile's X rows and columns and 1/ℓ are staged in LDS; every
+// receives K_rff[i = (λ>>4) + 4·reg][j = λ&15]; the K loop is mfma_kpair_tile (mfma_tile.h), the
+// tile index tri_pair.  Epilogue: the tile's X rows and columns and 1/ℓ are staged in LDS; every
 // accumulator entry forms k(x_i, x_j) as exactgp.hip's egp_cov does, ((x_ik − x_jk)·(1/ℓ_k))² summed
 // in k order and the device exp (dividing the rows by ℓ first would lose the difference's low
 // digits at a small ℓ), and adds d², k² and max|d| in the lane (entries with i >= N or j >= N are selected to an exact zero).  Diagonal tiles are
@@ -482,14 +378,6 @@ __global__ __launch_bounds__(256) void nlml_pvar_kernel(
 // waves in wave order -> part[3 t + {0, 1, 2}]; kerr_finish_kernel adds the tiles in tile order.
 constexpr int kKerrTile = 64;
 constexpr int kKerrLd = kDMax + 1;     // LDS row stride of the staged inputs
-
-__device__ __forceinline__ void kerr_tile_of(long long t, int& bi, int& bj) {
-  long long a = (long long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-  while (a * (a + 1) / 2 > t) --a;
-  while ((a + 1) * (a + 2) / 2 <= t) ++a;
-  bi = (int)a;
-  bj = (int)(t - a * (a + 1) / 2);
-}
 
 template <bool V2>
 __global__ __launch_bounds__(256) void kerr_tile_kernel(const double* __restrict__ phi,
@@ -502,7 +390,7 @@ __global__ __launch_bounds__(256) void kerr_tile_kernel(const double* __restrict
   __shared__ double red[4][3];
   const int tid = threadIdx.x, lane = tid & 63, wv = uni(tid >> 6), kl = lane >> 4, li = lane & 15;
   int bi, bj;
-  kerr_tile_of((long long)blockIdx.x, bi, bj);
+  tri_pair((long long)blockIdx.x, bi, bj);
   for (int x = tid; x < 2 * kKerrTile * D; x += 256) {
     const int side = x / (kKerrTile * D), rem = x - side * kKerrTile * D;
     const int k = rem / kKerrTile, r = rem - k * kKerrTile;
@@ -518,62 +406,12 @@ __global__ __launch_bounds__(256) void kerr_tile_kernel(const double* __restrict
     pa[t] = phi + (size_t)n * (i < N ? i : 0);
     pb[t] = phi + (size_t)n * (j < N ? j : 0);
   }
-  auto ld = [&](const double* p, int j, double& x0, double& x1) {
-    if constexpr (V2) {              // n even: j even, columns 16-B aligned
-      const nd2 v = *(const nd2*)(p + min(j, n - 2));
-      x0 = v[0]; x1 = v[1];
-    } else {
-      x0 = p[min(j, n - 1)];
-      x1 = p[min(j + 1, n - 1)];
-    }
-  };
-  struct Ops { double a0[2], a1[2], b0[2], b1[2]; };
-  const int nfull = n & ~15;
-  nd4 acc[2][2];
+  d4 acc[2][2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int u = 0; u < 2; ++u) acc[t][u] = nd4{0.0, 0.0, 0.0, 0.0};
-  auto load = [&](int j, Ops& o) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) ld(pa[t], j, o.a0[t], o.a1[t]);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) ld(pb[u], j, o.b0[u], o.b1[u]);
-  };
-  auto ktail = [&](int j, Ops& o) {      // zero the first operand's halves past n
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      o.a0[t] = j < n ? o.a0[t] : 0.0;
-      o.a1[t] = j + 1 < n ? o.a1[t] : 0.0;
-    }
-  };
-  auto mma = [&](const Ops& o) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0[t], o.b0[u], acc[t][u], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1[t], o.b1[u], acc[t][u], 0, 0, 0);
-  };
-  Ops Xo, Yo;
-  load(2 * kl, Xo);
-  for (int k0 = 0; k0 < nfull; k0 += 16) {
-    load(k0 + 8 + 2 * kl, Yo);
-    mma(Xo);
-    load(k0 + 16 + 2 * kl, Xo);
-    mma(Yo);
-  }
-  if (nfull < n) {
-    load(nfull + 8 + 2 * kl, Yo);
-    ktail(nfull + 2 * kl, Xo);
-    ktail(nfull + 8 + 2 * kl, Yo);
-    mma(Xo);
-    mma(Yo);
-  }
+    for (int u = 0; u < 2; ++u) acc[t][u] = d4{0.0, 0.0, 0.0, 0.0};
+  mfma_kpair_tile<V2, 2, 2>(pa, pb, n, n, kl, acc);
   __syncthreads();                       // the staged inputs
   double sd = 0.0, sk = 0.0, mx = 0.0;
 #pragma unroll

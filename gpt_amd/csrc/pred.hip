@@ -4,6 +4,7 @@
 
 #include "device_util.h"
 #include "host_util.h"
+#include "mfma_tile.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -202,14 +203,12 @@ __global__ __launch_bounds__(kNT) void mean_sse_kernel(const double* __restrict_
 //   T[s][i/64][k·R + l][i%64] = Σ_j U_s[j, l, k] · phi[j, k, i]     (M = S·R, N = Ntest, K = n)
 // (tile-contiguous: the V-phase reads a (sample, 64 rows) tile's D·R rows as one block)
 // run on v_mfma_f64_16x16x4f64, then the V-phase (computeV / computefhat) per (sample, 64-row tile)
-// reads its R·D temp rows.  Both operands are K(j)-contiguous; lane λ feeds the K pair
-// j0 + 2(λ>>4) + {0,1} of row/column λ&15 as one 16-B load and the two halves go to two MFMAs
-// (any K order common to A and B is the same sum).  A workgroup = 4 waves = a 64(c) × 64(i)
+// reads its R·D temp rows.  Both operands are K(j)-contiguous: the K loop is mfma_kpair_tile
+// (mfma_tile.h), A's rows ↔ c = (s, l), B's ↔ i.  Lanes of columns c >= S·R or rows i >= Ntest
+// read row 0 and only feed outputs that are never stored.  A workgroup = 4 waves = a 64(c) × 64(i)
 // tile, each wave 2 × 2 MFMA tiles.  Workgroups are numbered so that the c-tiles of one
 // (i-tile, k) land on the same XCD (dispatch is round-robin over the 8 XCDs): phi[:, k, tile] is
 // then fetched into one L2 and reused there by every c-tile.
-typedef double pd4 __attribute__((ext_vector_type(4)));
-typedef double pd2 __attribute__((ext_vector_type(2)));
 constexpr int kXcds = 8;
 
 template <bool V2, int TM, int TN>
@@ -247,70 +246,12 @@ __global__ __launch_bounds__(256) void pred_temp_mfma_kernel(const double* __res
     const long long i = iw + 16 * u + (lane & 15);
     pb[u] = gptr(phi + (size_t)n * (k + (size_t)D * (i < Ntest ? i : 0)));
   }
-  pd4 acc[TM][TN];
+  d4 acc[TM][TN];
 #pragma unroll
   for (int t = 0; t < TM; ++t)
 #pragma unroll
-    for (int u = 0; u < TN; ++u) acc[t][u] = pd4{0.0, 0.0, 0.0, 0.0};
-  // Branch- and select-free operand loads in the K loop (address clamped in-row): lanes of
-  // columns c >= S·R or rows i >= Ntest read row 0 and only feed outputs that are never stored,
-  // so the loaded values go straight into the MFMAs and the loads of one step stay in flight
-  // across the other step's MFMAs.  Only the K tail (j >= n) is zeroed, after the loop.
-  auto ld = [&](const __attribute__((address_space(1))) double* p, int j, double& x0, double& x1) {
-    if constexpr (V2) {              // n even: j even, rows 16-B aligned
-      const pd2 v = *(const __attribute__((address_space(1))) pd2*)(p + min(j, n - 2));
-      x0 = v[0]; x1 = v[1];
-    } else {
-      x0 = p[min(j, n - 1)];
-      x1 = p[min(j + 1, n - 1)];
-    }
-  };
-  struct Ops { double a0[TM], a1[TM], b0[TN], b1[TN]; };
-  auto load = [&](int j, Ops& o) {
-#pragma unroll
-    for (int t = 0; t < TM; ++t) ld(pa[t], j, o.a0[t], o.a1[t]);
-#pragma unroll
-    for (int u = 0; u < TN; ++u) ld(pb[u], j, o.b0[u], o.b1[u]);
-  };
-  auto ktail = [&](int j, Ops& o) {    // zero the A halves past n (one operand suffices)
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      o.a0[t] = j < n ? o.a0[t] : 0.0;
-      o.a1[t] = j + 1 < n ? o.a1[t] : 0.0;
-    }
-  };
-  // every accumulator with the even K half, then with the odd one (TM·TN >= 4 independent MFMAs
-  // between two on one accumulator)
-  auto mma = [&](const Ops& o) {
-#pragma unroll
-    for (int t = 0; t < TM; ++t)
-#pragma unroll
-      for (int u = 0; u < TN; ++u)
-        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a0[t], o.b0[u], acc[t][u], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < TM; ++t)
-#pragma unroll
-      for (int u = 0; u < TN; ++u)
-        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a1[t], o.b1[u], acc[t][u], 0, 0, 0);
-  };
-  // two K steps of 8 per iteration over the full 16-blocks, ping-ponging two operand sets: one
-  // step's loads are in flight while the other step's MFMAs run; then the masked tail
-  const int nfull = n & ~15;
-  Ops X, Y;
-  load(2 * kl, X);
-  for (int j0 = 0; j0 < nfull; j0 += 16) {
-    load(j0 + 8 + 2 * kl, Y);
-    mma(X);
-    load(j0 + 16 + 2 * kl, X);
-    mma(Y);
-  }
-  if (nfull < n) {
-    load(nfull + 8 + 2 * kl, Y);
-    ktail(nfull + 2 * kl, X);
-    ktail(nfull + 8 + 2 * kl, Y);
-    mma(X);
-    mma(Y);
-  }
+    for (int u = 0; u < TN; ++u) acc[t][u] = d4{0.0, 0.0, 0.0, 0.0};
+  mfma_kpair_tile<V2, TM, TN>(pa, pb, n, n, kl, acc);
   // D[row = (λ>>4) + 4·reg][col = λ&15]: row ↔ c, col ↔ i (16 consecutive i per store)
 #pragma unroll
   for (int t = 0; t < TM; ++t)

@@ -11,8 +11,6 @@
 
 namespace gpt {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 // temp[(d·R + l)·N + i] = U_dᵀ b[:, d, i] for d = d0 + blockIdx.y, rows i of a 64-row tile.
 template <int R>
 __global__ __launch_bounds__(kNT) void tgp_temp_kernel(const double* __restrict__ U,
@@ -95,10 +93,8 @@ __global__ __launch_bounds__(256) void syrk_mfma_kernel(const double* __restrict
   const long long pair = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int T = (p + 15) / 16;
   if (pair >= (long long)T * (T + 1) / 2) return;
-  int ta = (int)((sqrt(8.0 * (double)pair + 1.0) - 1.0) / 2.0);
-  while ((long long)ta * (ta + 1) / 2 > pair) --ta;
-  while ((long long)(ta + 1) * (ta + 2) / 2 <= pair) ++ta;
-  const int tb = (int)(pair - (long long)ta * (ta + 1) / 2);
+  int ta, tb;
+  tri_pair(pair, ta, tb);
   const int ra = ta * 16 + (lane & 15), rb = tb * 16 + (lane & 15), kl = lane >> 4;
   const bool oka = ra < p, okb = rb < p;
   const double* pa = A + (oka ? ra : 0);

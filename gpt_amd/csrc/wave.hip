@@ -352,12 +352,11 @@ __device__ __forceinline__ void copy_to_lds(T* dst, const T* src, int cnt, int t
 
 // copy_to_lds of doubles as 16-B pairs when the count and both addresses allow (half the loads,
 // half the memory round trips for the same UNR)
-typedef double dpair __attribute__((ext_vector_type(2)));
 template <int UNR>
 __device__ __forceinline__ void copy_to_lds_d2(double* dst, const double* src, int cnt, int t,
                                                int nth) {
   if (((cnt | (int)((uintptr_t)src >> 3) | (int)((uintptr_t)dst >> 3)) & 1) == 0)
-    copy_to_lds<UNR>((dpair*)dst, (const dpair*)src, cnt / 2, t, nth);
+    copy_to_lds<UNR>((d2*)dst, (const d2*)src, cnt / 2, t, nth);
   else
     copy_to_lds<UNR>(dst, src, cnt, t, nth);
 }
@@ -591,8 +590,6 @@ __global__ __launch_bounds__(512) void wv_vphase_kernel(StepParams P,
 
 // ---------------------------------------------------------------------------- dimension launch
 // init != 0: only temp of the batch of step t with the stored U (the first step of a run).
-typedef double pd4 __attribute__((ext_vector_type(4)));
-typedef double pd2 __attribute__((ext_vector_type(2)));
 // the dimension wave's U^(k) staging slot (column-major, stride n) at the start of its LDS
 __device__ __forceinline__ double* U_lds_base(double* sm) { return sm; }
 
@@ -673,8 +670,9 @@ __global__ __launch_bounds__(64, 1) void wv_dim_kernel(StepParams P,
   // ⌈R/16⌉ × 4 tiles of v_mfma_f64_16x16x4f64 (M = l, N = the ≤ 64 batch rows, K = j); A = Uᵀ from
   // U^(k) staged in LDS (column-major, stride n), B = φ rows straight from memory.  Lane λ feeds
   // the K pair j0 + 2(λ>>4) + {0,1} of row / column λ&15 as one 16-B read, the halves to two
-  // MFMAs (as pred_temp_mfma_kernel); columns l >= R and rows i >= Bn read clamped addresses and
-  // only feed outputs that are never stored, the K tail j >= n is zeroed on the A side.
+  // MFMAs (as mfma_tile.h's mfma_kpair_tile); columns l >= R and rows i >= Bn read clamped
+  // addresses and only feed outputs that are never stored, the K tail j >= n is zeroed on the A
+  // side.
   constexpr int TT = (R + 15) / 16;
   auto phidotU_mfma = [&](const int32_t* ordn, int Bn, double* tdst) {
     const int kl = lane >> 4, c16 = lane & 15;
@@ -685,22 +683,22 @@ __global__ __launch_bounds__(64, 1) void wv_dim_kernel(StepParams P,
 #pragma unroll
     for (int uu = 0; uu < 4; ++uu)
       pb[uu] = gptr(phik + (size_t)gptr(ordn)[min(16 * uu + c16, Bn - 1)] * rstride);
-    struct Ops { pd2 a[TT], b[4]; };
+    struct Ops { d2 a[TT], b[4]; };
     auto load = [&](int j, Ops& o) {
       const int jj = min(j, n - 2);
 #pragma unroll
       for (int tt = 0; tt < TT; ++tt) {
-        const pd2 v = *(const pd2*)(pa[tt] + jj);
-        o.a[tt] = pd2{j < n ? v[0] : 0.0, j + 1 < n ? v[1] : 0.0};
+        const d2 v = *(const d2*)(pa[tt] + jj);
+        o.a[tt] = d2{j < n ? v[0] : 0.0, j + 1 < n ? v[1] : 0.0};
       }
 #pragma unroll
-      for (int uu = 0; uu < 4; ++uu) o.b[uu] = *(const __attribute__((address_space(1))) pd2*)(pb[uu] + jj);
+      for (int uu = 0; uu < 4; ++uu) o.b[uu] = *(const __attribute__((address_space(1))) d2*)(pb[uu] + jj);
     };
-    pd4 acc[TT][4];
+    d4 acc[TT][4];
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
-      for (int uu = 0; uu < 4; ++uu) acc[tt][uu] = pd4{0.0, 0.0, 0.0, 0.0};
+      for (int uu = 0; uu < 4; ++uu) acc[tt][uu] = d4{0.0, 0.0, 0.0, 0.0};
     auto mma = [&](const Ops& o) {
 #pragma unroll
       for (int h = 0; h < 2; ++h)
