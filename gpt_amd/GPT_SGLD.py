@@ -749,6 +749,177 @@ def GPNT_pred_x(theta_store, Xtest, ytest, length_scale, sigma_RBF, Z, b, cols=N
                           bool(scores))
 
 
+# ------------------------------------------------------------------ posterior predictive of the samples
+class PredictiveEval:
+    """Posterior predictive of stored regression samples over a window of S of them, at noise
+    variance ``signal_var`` (predictive.hip).  Arrays are in the model's units:
+
+    ``gp``          GPPrediction(ymu, ys2, fmu, fs2, lp): fmu the window's mean prediction, fs2 its
+                    variance over the samples (divisor S), ymu = fmu, ys2 = fs2 + signal_var (the
+                    mean and variance of the equal-weight mixture of the S Gaussians) and lp the
+                    moment-matched log density of ytest, ExactGP.predict's formula
+    ``lp_mix``      log((1/S) Σ_s N(ytest | f_s, signal_var)), the Monte-Carlo predictive density
+    ``mnlp``, ``mnlp_mix``   −mean(lp) + log(scale), −mean(lp_mix) + log(scale): per target in the
+                    units of the unstandardised targets
+    ``coverage95``  the share of rows with |ytest − ymu| <= 1.959963984540054·sqrt(ys2)
+    ``rmse``, ``sample_rmse``   scale·RMSE of fmu and of every stored sample, as GPNT_pred's
+    ``sample_loglik``   −SSE_s/(2 signal_var) − (Ntest/2) log(2π signal_var) of every sample
+    ``mean_fhat``   fmu;  ``window`` the half-open 0-based sample range."""
+    __slots__ = ("gp", "lp_mix", "mnlp", "mnlp_mix", "coverage95", "rmse", "sample_rmse",
+                 "sample_loglik", "window")
+
+    @property
+    def mean_fhat(self):
+        return self.gp.fmu
+
+    def __repr__(self):
+        return "PredictiveEval(T=%d, rmse=%.6g, mnlp=%.6g, mnlp_mix=%.6g, coverage95=%.4g, window=%r)" % (
+            self.sample_rmse.size, self.rmse, self.mnlp, self.mnlp_mix, self.coverage95, self.window)
+
+
+def _predictive_call(fn, head, Nt, T, first, last, scale, signal_var, scale_in_call=True):
+    """fn(*head, [scale,] first, last, ..., the eight outputs) into a PredictiveEval; ``head``
+    ends where the C entry's ``scale`` (or, without one, ``first``) begins."""
+    if not 0 <= first < last <= T:
+        raise ValueError("the window must satisfy 0 <= first < last <= %d" % T)
+    scale, nv = float(scale), float(signal_var)
+    fmu, fs2, lp, lpmix = (np.empty(Nt) for _ in range(4))
+    sums, covered, rmse, srm = np.empty(2), np.empty(1), np.empty(1), np.empty(T)
+    check(fn(*(head + [_ptr(fmu), _ptr(fs2), _ptr(lp), _ptr(lpmix), _ptr(sums), _ptr(covered),
+                       _ptr(rmse), _ptr(srm)])))
+    if not scale_in_call:
+        rmse *= scale
+        srm *= scale
+    res = PredictiveEval()
+    res.gp = GPPrediction(fmu, fs2 + nv, fmu, fs2, lp)
+    res.lp_mix = lpmix
+    res.mnlp = -float(sums[0]) / Nt + math.log(scale)
+    res.mnlp_mix = -float(sums[1]) / Nt + math.log(scale)
+    res.coverage95 = float(covered[0]) / Nt
+    res.rmse = float(rmse[0])
+    res.sample_rmse = srm
+    sse = Nt * (srm / scale) ** 2
+    res.sample_loglik = -sse / (2.0 * nv) - 0.5 * Nt * math.log(2.0 * math.pi * nv)
+    res.window = (first, last)
+    return res
+
+
+def predictive(scores, ytest, signal_var, window=None, scale=1.0):
+    """The predictive of predictions ``scores`` (Ntest, T), one column per sample (what
+    ``GPNT_pred(..., scores=True).scores`` or a stack of ``pred`` columns holds), against ytest.
+    ``window=(a, b)`` is the half-open 0-based range of the columns that enter (Julia's a+1:b;
+    default all); the per-sample figures cover all T.  Returns a PredictiveEval."""
+    F = _f64(scores)
+    if F.ndim == 1:
+        F = F.reshape((-1, 1), order="F")
+    if F.ndim != 2:
+        raise ValueError("scores must be (Ntest, T)")
+    Nt, T = F.shape
+    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+    if yt.size != Nt:
+        raise ValueError("ytest must have one target per test row")
+    first, last = _window(window, T)
+    return _predictive_call(lib().gpt_predictive,
+                            [_ptr(F), _ptr(yt), Nt, T, first, last, float(signal_var)], Nt, T,
+                            first, last, scale, signal_var, scale_in_call=False)
+
+
+def _tensor_samples(w_store, U_store, I, cols, n, D):
+    w = np.asarray(w_store, dtype=np.float64)
+    U = np.asarray(U_store, dtype=np.float64)
+    if w.ndim == 1:
+        w = w.reshape(w.shape + (1,))
+        U = U.reshape(U.shape + (1,))
+    if cols is not None:
+        cols = np.asarray(cols, dtype=np.int64)
+        w, U = w[:, cols], U[:, :, :, cols]
+    w, U = _f64(w), _f64(U)
+    Q, S = w.shape
+    r = U.shape[1]
+    if U.shape != (n, r, D, S):
+        raise ValueError("U_store must be (n, r, D, S)")
+    I = np.asfortranarray(np.asarray(I, dtype=np.int32))
+    if I.shape != (Q, D):
+        raise ValueError("I must be (Q, D)")
+    return w, U, I, r, Q, S
+
+
+def pred_predictive(w_store, U_store, I, phitest, ytest, signal_var, cols=None, window=None,
+                    scale=1.0):
+    """The predictive of GPTregression's stored samples w_store (Q, S), U_store (n, r, D, S) on
+    phitest (n, D, Ntest): pred_mean's prediction, evaluated on the device where it lies.  ``cols``
+    selects stored samples (0-based) on the host before the call, ``window`` a range of the
+    selected ones, ``scale`` (ytrainStd) enters the scalars only.  Returns a PredictiveEval."""
+    phitest = _f64(phitest)
+    n, D, Nt = phitest.shape
+    w, U, I, r, Q, S = _tensor_samples(w_store, U_store, I, cols, n, D)
+    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+    if yt.size != Nt:
+        raise ValueError("ytest must have one target per test row")
+    first, last = _window(window, S)
+    return _predictive_call(lib().gpt_pred_predictive,
+                            [_ptr(w), _ptr(U), _ptr(I, P_I32), _ptr(phitest), _ptr(yt), n, D, Nt, r,
+                             Q, S, float(scale), first, last, float(signal_var)], Nt, S, first, last,
+                            scale, signal_var)
+
+
+def pred_predictive_x(w_store, U_store, I, Xtest, ytest, length_scale, sigma_RBF, phi_scale, Z, b,
+                      signal_var, cols=None, window=None, scale=1.0):
+    """pred_predictive with the test features formed on the device from Xtest, as pred_mean_x
+    (the same doubles as ``feature(Xtest, length_scale, sigma_RBF, phi_scale, Z, b)``)."""
+    X = _f64(Xtest)
+    Nt, D = X.shape
+    Z = _f64(Z)
+    n = Z.shape[0]
+    b = _f64(np.asarray(b, dtype=np.float64).reshape((n, D), order="F"))
+    ls = _f64(np.atleast_1d(length_scale))
+    w, U, I, r, Q, S = _tensor_samples(w_store, U_store, I, cols, n, D)
+    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+    if yt.size != Nt:
+        raise ValueError("ytest must have one target per test row")
+    first, last = _window(window, S)
+    return _predictive_call(lib().gpt_pred_predictive_x,
+                            [_ptr(w), _ptr(U), _ptr(I, P_I32), _ptr(X), _ptr(yt), Nt, D, _ptr(ls),
+                             ls.size, float(sigma_RBF), float(phi_scale), _ptr(Z), _ptr(b), n, r, Q,
+                             S, float(scale), first, last, float(signal_var)], Nt, S, first, last,
+                            scale, signal_var)
+
+
+def GPNT_predictive(theta_store, phitest, ytest, signal_var, cols=None, window=None, scale=1.0):
+    """The predictive of GPNT_SGLD samples theta_store (n, T) on phitest (n, Ntest): GPNT_pred's
+    scores, evaluated on the device where they lie.  ``cols``, ``window`` and ``scale`` as in
+    GPNT_pred.  Returns a PredictiveEval."""
+    phitest = _f64(phitest)
+    if phitest.ndim != 2:
+        raise ValueError("phitest must be (n, Ntest)")
+    n, Nt = phitest.shape
+    theta, yt, T, first, last = _reg_samples(theta_store, cols, n, ytest, Nt, window)
+    return _predictive_call(lib().gpt_gpnt_predictive,
+                            [_ptr(theta), _ptr(phitest), _ptr(yt), n, Nt, T, first, last,
+                             float(scale), float(signal_var)], Nt, T, first, last, scale, signal_var)
+
+
+def GPNT_predictive_x(theta_store, Xtest, ytest, length_scale, sigma_RBF, Z, b, signal_var,
+                      cols=None, window=None, scale=1.0):
+    """GPNT_predictive on phitest = featureNotensor(Xtest, length_scale, sigma_RBF, Z, b) formed on
+    the device."""
+    Xtest, ls, Z, b, n = _notensor_inputs(Xtest, length_scale, Z, b)
+    Nt, D = Xtest.shape
+    theta, yt, T, first, last = _reg_samples(theta_store, cols, n, ytest, Nt, window)
+    return _predictive_call(lib().gpt_gpnt_predictive_x,
+                            [_ptr(theta), _ptr(Xtest), _ptr(yt), Nt, D, _ptr(ls), ls.size,
+                             float(sigma_RBF), _ptr(Z), _ptr(b), n, T, first, last, float(scale),
+                             float(signal_var)], Nt, T, first, last, scale, signal_var)
+
+
+def predictive_last_timing():
+    """Device-event ms of the evaluator's kernels alone in the last *predictive* call on this
+    thread (gpt_predictive_last_timing)."""
+    out = np.zeros(1)
+    check(lib().gpt_predictive_last_timing(_ptr(out)))
+    return float(out[0])
+
+
 # ------------------------------------------------------------------ classification
 def GPNT_SGLDclass(phi, y, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch, param_seed=0):
     """Full-theta softmax SGLD (GPT_SGLD.jl:851-901), labels y in 1..C.  Returns theta_store

@@ -123,6 +123,23 @@ SIGNATURES = {
                                   P_D, P_D, P_D, P_D]),
     "gpt_gpnt_last_route": (C.c_int, [P_I32, C.c_int32]),
     "gpt_gpnt_last_timing": (C.c_int, [P_D, C.c_int32]),
+    "gpt_predictive_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, P_D, P_D, C.c_void_p]),
+    "gpt_predictive": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double]
+                       + [P_D] * 8),
+    "gpt_pred_predictive": (C.c_int, [P_D, P_D, P_I32, P_D, P_D] + [C.c_int64] * 6
+                            + [C.c_double, C.c_int64, C.c_int64, C.c_double] + [P_D] * 8),
+    "gpt_pred_predictive_x": (C.c_int, [P_D, P_D, P_I32, P_D, P_D, C.c_int64, C.c_int64, P_D,
+                                        C.c_int64, C.c_double, C.c_double, P_D, P_D, C.c_int64,
+                                        C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64,
+                                        C.c_int64, C.c_double] + [P_D] * 8),
+    "gpt_gpnt_predictive": (C.c_int, [P_D, P_D, P_D] + [C.c_int64] * 5 + [C.c_double, C.c_double]
+                            + [P_D] * 8),
+    "gpt_gpnt_predictive_x": (C.c_int, [P_D, P_D, P_D, C.c_int64, C.c_int64, P_D, C.c_int64,
+                                        C.c_double, P_D, P_D, C.c_int64, C.c_int64, C.c_int64,
+                                        C.c_int64, C.c_double, C.c_double] + [P_D] * 8),
+    "gpt_predictive_last_timing": (C.c_int, [P_D]),
     "gpt_gpnt_sgld_class": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_double, C.c_int64,
                                       C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_uint64,
                                       P_D]),

@@ -154,8 +154,8 @@ extern "C" int gpt_gpnt_sgld_chains(const double* phi, const double* y, int64_t 
                           decay_rate, seeds, nchains, store_every, R, theta_store, status);
 }
 
-static bool valid_feature_args(const double* ls, int64_t ls_len, int64_t D, const double* Z,
-                               const double* b) {
+bool gpt::valid_feature_args(const double* ls, int64_t ls_len, int64_t D, const double* Z,
+                             const double* b) {
   if (!ls || !Z || !b || D < 1 || D > (1 << 20)) { set_error("bad feature arguments"); return false; }
   if (ls_len != 1 && ls_len != D) {
     set_error("dimensions of X and length_scale do not match"); return false;
@@ -165,9 +165,9 @@ static bool valid_feature_args(const double* ls, int64_t ls_len, int64_t D, cons
 
 // dphi (n, rows) = featureNotensor(X, length_scale, sigma_rbf, Z, b) formed on the device: the
 // doubles gpt_feature_notensor makes, with no n x rows host array.
-static int device_features(const double* X, int64_t rows, int64_t D, const double* ls,
-                           int64_t ls_len, double sigma_rbf, const double* Z, const double* b,
-                           int64_t n, DevMem& dphi) {
+int gpt::device_features(const double* X, int64_t rows, int64_t D, const double* ls,
+                         int64_t ls_len, double sigma_rbf, const double* Z, const double* b,
+                         int64_t n, DevMem& dphi) {
   std::vector<double> lsv(D);
   for (int64_t k = 0; k < D; ++k) lsv[k] = ls[ls_len == 1 ? 0 : k];
   DevMem dX, dls, dZ, db;

@@ -107,21 +107,33 @@ extern "C" int gpt_pred_dev_timed(const double* w_dev, const double* U_dev, cons
   return GPT_OK;
 }
 
-static int pred_host(const double* w, const double* U, const int32_t* I, const double* phitest,
-                     const double* ytest, int64_t n, int64_t D, int64_t Ntest, int64_t r,
-                     int64_t Q, int64_t S, double scale, double* fhat_out, double* mean_out,
-                     double* rmse_out) {
+// fhat (Ntest, S) of S stored samples into df, from host arrays (I 1-based): the prediction of
+// gpt_pred_mean.  The uploads are freed on return, after the stream has drained.
+int gpt::pred_store_fhat(const double* w, const double* U, const int32_t* I, const double* phitest,
+                         int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q, int64_t S,
+                         DevMem& df) {
   if (!valid_pred(n, D, Ntest, r, Q) || S < 1) return GPT_ERR_BAD_DIMS;
   std::vector<int32_t> I0;
   if (!zero_based_I(I, Q, D, r, I0)) return GPT_ERR_BAD_DIMS;
-  DevMem dw, dU, dI, dphi, df, dy, dmean, dsse;
+  DevMem dw, dU, dI, dphi;
   GPT_HIPCHK(dw.upload(w, (size_t)Q * S));
   GPT_HIPCHK(dU.upload(U, (size_t)n * r * D * S));
   GPT_HIPCHK(dI.upload(I0.data(), I0.size()));
   GPT_HIPCHK(dphi.upload(phitest, (size_t)n * D * Ntest));
   GPT_HIPCHK(df.alloc<double>((size_t)Ntest * S));
-  int rc = gpt_pred_dev(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(), n,
-                        D, Ntest, r, Q, S, df.as<double>(), nullptr);
+  const int rc = gpt_pred_dev(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(),
+                              n, D, Ntest, r, Q, S, df.as<double>(), nullptr);
+  if (rc != GPT_OK) return rc;
+  GPT_HIPCHK(hipStreamSynchronize(nullptr));
+  return GPT_OK;
+}
+
+static int pred_host(const double* w, const double* U, const int32_t* I, const double* phitest,
+                     const double* ytest, int64_t n, int64_t D, int64_t Ntest, int64_t r,
+                     int64_t Q, int64_t S, double scale, double* fhat_out, double* mean_out,
+                     double* rmse_out) {
+  DevMem df, dy, dmean, dsse;
+  const int rc = pred_store_fhat(w, U, I, phitest, n, D, Ntest, r, Q, S, df);
   if (rc != GPT_OK) return rc;
   if (fhat_out) GPT_HIPCHK(df.download(fhat_out, (size_t)Ntest * S));
   if (ytest) {
@@ -154,12 +166,13 @@ extern "C" int gpt_pred_mean(const double* w_store, const double* U_store, const
                    mean_out, rmse_out);
 }
 
-extern "C" int gpt_pred_mean_x(const double* w_store, const double* U_store, const int32_t* I,
-                               const double* Xtest, const double* ytest, int64_t Ntest, int64_t D,
-                               const double* length_scale, int64_t ls_len, double sigma_rbf,
-                               double phi_scale, const double* Z, const double* b, int64_t n,
-                               int64_t r, int64_t Q, int64_t S, double scale, double* mean_out,
-                               double* rmse_out, double* sample_rmse_out) {
+// fhat (Ntest, S) of S stored samples into df with the test features formed on the device from
+// Xtest: the prediction of gpt_pred_mean_x, its checks included.
+int gpt::pred_store_fhat_x(const double* w_store, const double* U_store, const int32_t* I,
+                           const double* Xtest, const double* ytest, int64_t Ntest, int64_t D,
+                           const double* length_scale, int64_t ls_len, double sigma_rbf,
+                           double phi_scale, const double* Z, const double* b, int64_t n, int64_t r,
+                           int64_t Q, int64_t S, DevMem& df) {
   if (!w_store || !U_store || !I || !Xtest || !ytest || !length_scale || !Z || !b || S < 1) {
     set_error("bad pred_mean_x arguments"); return GPT_ERR_BAD_DIMS;
   }
@@ -175,7 +188,7 @@ extern "C" int gpt_pred_mean_x(const double* w_store, const double* U_store, con
   std::vector<double> lsv(D);
   for (int64_t k = 0; k < D; ++k) lsv[k] = length_scale[ls_len == 1 ? 0 : k];
   const double c = phi_scale * std::pow(sigma_rbf, 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
-  DevMem dw, dU, dI, dX, dls, dZ, db, df, dy, dmean, dsse;
+  DevMem dw, dU, dI, dX, dls, dZ, db;
   GPT_HIPCHK(dw.upload(w_store, (size_t)Q * S));
   GPT_HIPCHK(dU.upload(U_store, (size_t)n * r * D * S));
   GPT_HIPCHK(dI.upload(I0.data(), I0.size()));
@@ -183,10 +196,7 @@ extern "C" int gpt_pred_mean_x(const double* w_store, const double* U_store, con
   GPT_HIPCHK(dls.upload(lsv.data(), lsv.size()));
   GPT_HIPCHK(dZ.upload(Z, (size_t)n * D));
   GPT_HIPCHK(db.upload(b, (size_t)n * D));
-  GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
   GPT_HIPCHK(df.alloc<double>((size_t)Ntest * S));
-  GPT_HIPCHK(dmean.alloc<double>((size_t)Ntest));
-  GPT_HIPCHK(dsse.alloc<double>((size_t)(S + 1)));
   // Default: the test features are formed once on the device (feature_kernel, the same doubles
   // as gpt_feature) and every sample is predicted by the stacked-sample MFMA path, which reads
   // them through L2 per group of samples.  GPTSGLD_PRED=direct: pred_x_kernel, which forms the
@@ -208,8 +218,25 @@ extern "C" int gpt_pred_mean_x(const double* w_store, const double* U_store, con
                     (int)D, Ntest, (int)r, (int)Q, (int)S, df.as<double>(), nullptr);
     if (e != hipSuccess) return hip_fail(e, "pred kernels");
   }
-  e = launch_mean_rmse(df.as<double>(), dy.as<double>(), Ntest, (int)S, dmean.as<double>(),
-                       dsse.as<double>(), nullptr);
+  GPT_HIPCHK(hipStreamSynchronize(nullptr));
+  return GPT_OK;
+}
+
+extern "C" int gpt_pred_mean_x(const double* w_store, const double* U_store, const int32_t* I,
+                               const double* Xtest, const double* ytest, int64_t Ntest, int64_t D,
+                               const double* length_scale, int64_t ls_len, double sigma_rbf,
+                               double phi_scale, const double* Z, const double* b, int64_t n,
+                               int64_t r, int64_t Q, int64_t S, double scale, double* mean_out,
+                               double* rmse_out, double* sample_rmse_out) {
+  DevMem df, dy, dmean, dsse;
+  const int rc = pred_store_fhat_x(w_store, U_store, I, Xtest, ytest, Ntest, D, length_scale, ls_len,
+                                   sigma_rbf, phi_scale, Z, b, n, r, Q, S, df);
+  if (rc != GPT_OK) return rc;
+  GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
+  GPT_HIPCHK(dmean.alloc<double>((size_t)Ntest));
+  GPT_HIPCHK(dsse.alloc<double>((size_t)(S + 1)));
+  hipError_t e = launch_mean_rmse(df.as<double>(), dy.as<double>(), Ntest, (int)S,
+                                  dmean.as<double>(), dsse.as<double>(), nullptr);
   if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
   std::vector<double> sse((size_t)S + 1);
   GPT_HIPCHK(dsse.download(sse.data(), sse.size()));

@@ -405,6 +405,16 @@ hipError_t launch_class_eval(const double* scores, const int32_t* y, long long N
 hipError_t launch_class_mean(const double* scores, long long Ntest, int C, int first, int last,
                              double* mean_out, hipStream_t st);
 
+// Posterior predictive of stored predictions F (Ntest, S) against y at noise variance noise_var
+// (predictive.hip): fmu, fs2, lp, lpmix (Ntest, each optional); part (2 per tile) and part_cov
+// (1 per tile) hold the predictive_tiles(Ntest) partial sums; sums[0..1] = Σ lp, Σ lpmix and
+// *covered = the rows inside the 95 % interval, added in tile order.
+size_t predictive_tiles(long long Ntest);
+hipError_t launch_predictive(const double* F, const double* y, long long Ntest, int S,
+                             double noise_var, double* fmu, double* fs2, double* lp, double* lpmix,
+                             double* part, int32_t* part_cov, double* sums, double* covered,
+                             hipStream_t st);
+
 // Joint likelihood of the full-theta softmax classifier and its gradient (cjoint.hip).
 struct CjLayout {
   int CC, TI, theta_lds, nblk;   // CC: C rounded up to 2, 4, 8, 16, 32; TI: data columns per tile;

@@ -270,6 +270,26 @@ def pred_device(w_ptr, U_ptr, I0_dev, phitest, n, D, Ntest, r, Q, S, fhat_out, s
                              C.c_void_p(fhat_out.data_ptr()), C.c_void_p(stream) if stream else None))
 
 
+def predictive_device(fhat, ytest, signal_var, window=None, stream=None, rows=True):
+    """The posterior predictive (gpt_predictive_dev) of device predictions ``fhat``, a torch
+    (S, Ntest) tensor as pred_device fills it [Julia (Ntest, S)], against the device targets
+    ``ytest`` at noise variance ``signal_var``, over the half-open 0-based sample ``window``
+    (default all).  Nothing but three scalars visits the host.  Returns (fmu, fs2, lp, lp_mix,
+    sum_lp, sum_lp_mix, covered): device tensors (None with ``rows=False``), the sums of the two
+    log densities over the rows and the number of rows inside the 95 % interval."""
+    import torch
+    T, Nt = fhat.shape
+    first, last = (0, T) if window is None else (int(window[0]), int(window[1]))
+    out = [torch.empty(Nt, dtype=torch.float64, device=fhat.device) if rows else None for _ in range(4)]
+    sums, covered = np.zeros(2), np.zeros(1)
+    check(lib().gpt_predictive_dev(C.c_void_p(fhat.data_ptr()), C.c_void_p(ytest.data_ptr()), Nt, T,
+                                   first, last, float(signal_var),
+                                   *[C.c_void_p(t.data_ptr()) if rows else None for t in out],
+                                   sums.ctypes.data_as(_lib.P_D), covered.ctypes.data_as(_lib.P_D),
+                                   C.c_void_p(stream) if stream else None))
+    return tuple(out) + (float(sums[0]), float(sums[1]), int(covered[0]))
+
+
 VPHASE_KERNELS = {0: "pred_vphase_pairs_kernel", 1: "pred_vphase_rows_pf_kernel",
                   2: "pred_vphase_rows_kernel", 4: "pred_kernel (direct, no separate V-phase)"}
 

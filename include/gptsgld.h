@@ -406,6 +406,73 @@ int gpt_gpnt_last_route(int32_t* out, int32_t len);
  * gpt_gpnt_pred*.  Entries past 2 are set to 0. */
 int gpt_gpnt_last_timing(double* ms, int32_t len);
 
+/* ---- posterior predictive of the sampled regression models ---------------------------- */
+/* The predictive of stored predictions F (Ntest, T) column-major (column s at F + s*Ntest, as
+ * gpt_pred_dev and the scores of gpt_gpnt_pred write them) against y (Ntest), over the S = last -
+ * first columns first <= s < last (0-based, half open), with Gaussian noise variance noise_var
+ * (the model's signal_var).  Per row, in sample order:
+ *   fmu   = (sum_s f_s)/S            the bits of gpt_pred_mean / gpt_gpnt_pred's mean on the columns
+ *   fs2   = (sum_s (f_s - fmu)^2)/S  two passes, divisor S, the deviations taken about the window's
+ *                                    first column; >= 0, and exactly 0 where the columns agree
+ *   ymu = fmu, ys2 = fs2 + noise_var  (the equal-weight mixture's mean and variance; not stored)
+ *   lp    = -(y - ymu)^2/(2 ys2) - log(2 pi ys2)/2                 GPkit's moment-matched lp
+ *   lpmix = log((1/S) sum_s N(y | f_s, noise_var))                 max-shifted logsumexp
+ * sums[0] = sum_i lp, sums[1] = sum_i lpmix, *covered = the number of rows with
+ * |y - ymu| <= 1.959963984540054 sqrt(ys2) (an integer value): fixed 256-row tiles added in tile
+ * order, no atomics, so a repeated call returns the same bits.  A row's outputs depend on its own
+ * S values, y and noise_var alone.  The per-row outputs may be NULL.  A null required pointer,
+ * Ntest < 1, T outside 1..2^22, an empty window or one outside [0, T], or a noise_var that is not
+ * finite and > 0 is GPT_ERR_BAD_DIMS before any device work.
+ * The _dev form takes device pointers for F, y and the per-row outputs, writes sums and covered
+ * to the host and synchronises hip_stream.  The host form also returns, where asked (both may be
+ * NULL), sample_rmse_out[t] = ||y - F[:, t]||/sqrt(Ntest) of all T columns and *rmse_out, the same
+ * figure of fmu, from the kernel of gpt_pred_mean. */
+int gpt_predictive_dev(const double* F_dev, const double* y_dev, int64_t Ntest, int64_t T,
+                       int64_t first, int64_t last, double noise_var, double* fmu_dev,
+                       double* fs2_dev, double* lp_dev, double* lpmix_dev, double* sums_host,
+                       double* covered_host, void* hip_stream);
+int gpt_predictive(const double* F, const double* y, int64_t Ntest, int64_t T, int64_t first,
+                   int64_t last, double noise_var, double* fmu_out, double* fs2_out, double* lp_out,
+                   double* lpmix_out, double* sums_out, double* covered_out, double* rmse_out,
+                   double* sample_rmse_out);
+/* gpt_pred_mean's prediction of the S stored tensor samples (the same kernels and routes), then
+ * gpt_predictive_dev on the window first <= s < last of them without a copy to the host.
+ * sample_rmse_out (S) = scale*||ytest - pred(sample s)||/sqrt(Ntest) and *rmse_out the same figure
+ * of fmu are required. */
+int gpt_pred_predictive(const double* w_store, const double* U_store, const int32_t* I,
+                        const double* phitest, const double* ytest, int64_t n, int64_t D,
+                        int64_t Ntest, int64_t r, int64_t Q, int64_t S, double scale, int64_t first,
+                        int64_t last, double noise_var, double* fmu_out, double* fs2_out,
+                        double* lp_out, double* lpmix_out, double* sums_out, double* covered_out,
+                        double* rmse_out, double* sample_rmse_out);
+/* The same beside gpt_pred_mean_x: the test features are formed on the device from Xtest
+ * (GPTSGLD_PRED=direct as there). */
+int gpt_pred_predictive_x(const double* w_store, const double* U_store, const int32_t* I,
+                          const double* Xtest, const double* ytest, int64_t Ntest, int64_t D,
+                          const double* length_scale, int64_t ls_len, double sigma_rbf,
+                          double phi_scale, const double* Z, const double* b, int64_t n, int64_t r,
+                          int64_t Q, int64_t S, double scale, int64_t first, int64_t last,
+                          double noise_var, double* fmu_out, double* fs2_out, double* lp_out,
+                          double* lpmix_out, double* sums_out, double* covered_out,
+                          double* rmse_out, double* sample_rmse_out);
+/* The same for T stored full-theta samples theta (n, T), beside gpt_gpnt_pred / gpt_gpnt_pred_x:
+ * the scores stay on the device; sample_rmse_out (T) and *rmse_out as there. */
+int gpt_gpnt_predictive(const double* theta, const double* phitest, const double* ytest, int64_t n,
+                        int64_t Ntest, int64_t T, int64_t first, int64_t last, double scale,
+                        double noise_var, double* fmu_out, double* fs2_out, double* lp_out,
+                        double* lpmix_out, double* sums_out, double* covered_out, double* rmse_out,
+                        double* sample_rmse_out);
+int gpt_gpnt_predictive_x(const double* theta, const double* Xtest, const double* ytest,
+                          int64_t Ntest, int64_t D, const double* length_scale, int64_t ls_len,
+                          double sigma_rbf, const double* Z, const double* b, int64_t n, int64_t T,
+                          int64_t first, int64_t last, double scale, double noise_var,
+                          double* fmu_out, double* fs2_out, double* lp_out, double* lpmix_out,
+                          double* sums_out, double* covered_out, double* rmse_out,
+                          double* sample_rmse_out);
+/* Device-event time in ms of the evaluator's two kernels alone in the last gpt_*predictive* call
+ * on this thread (measurement, scripts/time_predictive.py). */
+int gpt_predictive_last_timing(double* ms);
+
 /* ---- classification: the full-theta softmax sampler and the evaluation of scores ------ */
 /* GPNT_SGLDclass(phi,y,sigma_theta,m,eps_theta,decay_rate,burnin,maxepoch,param_seed)
  * GPT_SGLD.jl:851-901.  phi (n, N); y (N) integer labels in 1..C, C = max(y) - min(y) + 1 <= 32

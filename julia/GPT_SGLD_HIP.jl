@@ -14,7 +14,8 @@ export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTreg
        GPNT_SGLD, GPNT_SGLD_chains, GPNT_SGLD_chains_x, GPNT_pred, GPNT_pred_x, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
        init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal, GP_nlogmarginal, GP_gradnlogmarginal, GP_predict, GPNT_predict, RFF_kernel_error,
        GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class,
-       neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores
+       neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores,
+       predictive, pred_predictive, pred_predictive_x, GPNT_predictive, GPNT_predictive_x
 
 const LIB = get(ENV, "GPTSGLD_LIB", joinpath(@__DIR__, "..", "gpt_amd", "libgptsgld.so"))
 
@@ -479,6 +480,135 @@ function GPNT_pred_x(theta_store::Array{Float64,2}, Xtest::Array{Float64,2}, yte
                 theta_store, Xtest, vec(ytest), Nt, D, ls, length(ls), sigma_RBF, Z, vec(bfeat), n,
                 T, a, b, scale, sr, mf, rm, sc))
     return RegEval(sr, mf, rm[1], sc)
+end
+
+# The posterior predictive of stored regression samples over `window` (1-based, inclusive) at noise
+# variance signal_var: ymu = fmu and fs2 the mean and variance of the predictions over the window,
+# ys2 = fs2 + signal_var, lp the moment-matched and lp_mix the Monte-Carlo log density of ytest
+# (arrays in the model's units); mnlp, mnlp_mix = -mean(lp), -mean(lp_mix) + log(scale); coverage95
+# the share of rows within 1.96 sqrt(ys2) of ymu; rmse, sample_rmse as GPNT_pred's; sample_loglik
+# the Gaussian log likelihood of ytest under every sample (lkhdLearningCurve.jl:53)
+struct PredictiveEval
+    ymu::Vector{Float64}; ys2::Vector{Float64}; fmu::Vector{Float64}; fs2::Vector{Float64}
+    lp::Vector{Float64}; lp_mix::Vector{Float64}; mnlp::Float64; mnlp_mix::Float64
+    coverage95::Float64; rmse::Float64; sample_rmse::Vector{Float64}; sample_loglik::Vector{Float64}
+end
+
+struct PredictiveOut
+    fmu::Vector{Float64}; fs2::Vector{Float64}; lp::Vector{Float64}; lpmix::Vector{Float64}
+    sums::Vector{Float64}; covered::Vector{Float64}; rmse::Vector{Float64}; srm::Vector{Float64}
+end
+PredictiveOut(Nt, T) = PredictiveOut(zeros(Nt), zeros(Nt), zeros(Nt), zeros(Nt), zeros(2), zeros(1),
+                                     zeros(1), zeros(T))
+
+function predictive_result(o::PredictiveOut, Nt, signal_var, scale)
+    sse = Nt .* (o.srm ./ scale) .^ 2
+    return PredictiveEval(o.fmu, o.fs2 .+ signal_var, o.fmu, o.fs2, o.lp, o.lpmix,
+                          -o.sums[1] / Nt + log(scale), -o.sums[2] / Nt + log(scale),
+                          o.covered[1] / Nt, o.rmse[1], o.srm,
+                          -sse ./ (2 * signal_var) .- Nt / 2 * log(2 * pi * signal_var))
+end
+
+# scores (Ntest, T): one column of predictions per sample
+function predictive(scores::Array{Float64,2}, ytest::Array{Float64}, signal_var::Real;
+                    window=nothing, scale::Real=1.0)
+    Nt, T = size(scores); a, b = class_window(window, T)
+    length(ytest) == Nt || error("ytest must have one target per test row")
+    0 <= a < b <= T || error("the window must lie in 1:$T")
+    o = PredictiveOut(Nt, T)
+    check(ccall((:gpt_predictive, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Float64, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}),
+                scores, vec(ytest), Nt, T, a, b, signal_var, o.fmu, o.fs2, o.lp, o.lpmix, o.sums,
+                o.covered, o.rmse, o.srm))
+    o.rmse .*= scale; o.srm .*= scale
+    return predictive_result(o, Nt, signal_var, scale)
+end
+
+# GPTregression's stored samples w_store (Q, S), U_store (n, r, D, S) on phitest (n, D, Ntest)
+function pred_predictive(w_store::Array{Float64,2}, U_store::Array{Float64,4}, I::Array{Int32,2},
+                         phitest::Array{Float64,3}, ytest::Array{Float64}, signal_var::Real;
+                         window=nothing, scale::Real=1.0)
+    n, D, Nt = size(phitest); r = size(U_store, 2); Q, S = size(w_store); a, b = class_window(window, S)
+    size(U_store) == (n, r, D, S) || error("U_store must be (n, r, D, S)")
+    size(I) == (Q, D) || error("I must be (Q, D)")
+    length(ytest) == Nt || error("ytest must have one target per test row")
+    0 <= a < b <= S || error("the window must lie in 1:$S")
+    o = PredictiveOut(Nt, S)
+    check(ccall((:gpt_pred_predictive, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+                 Int64, Int64, Int64, Int64, Float64, Int64, Int64, Float64, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}),
+                w_store, U_store, I, phitest, vec(ytest), n, D, Nt, r, Q, S, scale, a, b, signal_var,
+                o.fmu, o.fs2, o.lp, o.lpmix, o.sums, o.covered, o.rmse, o.srm))
+    return predictive_result(o, Nt, signal_var, scale)
+end
+
+# The same with the test features formed on the device from Xtest, as pred_mean_x
+function pred_predictive_x(w_store::Array{Float64,2}, U_store::Array{Float64,4}, I::Array{Int32,2},
+                           Xtest::Array{Float64,2}, ytest::Array{Float64}, length_scale,
+                           sigma_RBF::Real, phi_scale::Real, Z::Array{Float64,2}, bfeat::Array{Float64},
+                           signal_var::Real; window=nothing, scale::Real=1.0)
+    Nt, D = size(Xtest); n = size(Z, 1); r = size(U_store, 2); Q, S = size(w_store)
+    a, b = class_window(window, S)
+    ls = collect(Float64, length_scale isa Real ? [length_scale] : length_scale)
+    size(U_store) == (n, r, D, S) || error("U_store must be (n, r, D, S)")
+    size(I) == (Q, D) || error("I must be (Q, D)")
+    (size(Z, 2) == D && length(bfeat) == n * D) || error("Z and b must be (n, D)")
+    (length(ls) == 1 || length(ls) == D) || error("dimensions of Xtest and length_scale do not match")
+    length(ytest) == Nt || error("ytest must have one target per test row")
+    0 <= a < b <= S || error("the window must lie in 1:$S")
+    o = PredictiveOut(Nt, S)
+    check(ccall((:gpt_pred_predictive_x, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+                 Ptr{Float64}, Int64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+                 Int64, Int64, Float64, Int64, Int64, Float64, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                w_store, U_store, I, Xtest, vec(ytest), Nt, D, ls, length(ls), sigma_RBF, phi_scale,
+                Z, vec(bfeat), n, r, Q, S, scale, a, b, signal_var, o.fmu, o.fs2, o.lp, o.lpmix,
+                o.sums, o.covered, o.rmse, o.srm))
+    return predictive_result(o, Nt, signal_var, scale)
+end
+
+# GPNT_SGLD's stored samples theta_store (n, T) on phitest (n, Ntest), beside GPNT_pred
+function GPNT_predictive(theta_store::Array{Float64,2}, phitest::Array{Float64,2},
+                         ytest::Array{Float64}, signal_var::Real; window=nothing, scale::Real=1.0)
+    n, T = size(theta_store); Nt = size(phitest, 2); a, b = class_window(window, T)
+    size(phitest, 1) == n || error("theta_store and phitest disagree on n")
+    length(ytest) == Nt || error("ytest must have one target per test row")
+    0 <= a < b <= T || error("the window must lie in 1:$T")
+    o = PredictiveOut(Nt, T)
+    check(ccall((:gpt_gpnt_predictive, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Int64,
+                 Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                theta_store, phitest, vec(ytest), n, Nt, T, a, b, scale, signal_var, o.fmu, o.fs2,
+                o.lp, o.lpmix, o.sums, o.covered, o.rmse, o.srm))
+    return predictive_result(o, Nt, signal_var, scale)
+end
+
+# The same with phitest = featureNotensor(Xtest, length_scale, sigma_RBF, Z, b) formed on the device
+function GPNT_predictive_x(theta_store::Array{Float64,2}, Xtest::Array{Float64,2},
+                           ytest::Array{Float64}, length_scale, sigma_RBF::Real, Z::Array{Float64,2},
+                           bfeat::Array{Float64}, signal_var::Real; window=nothing, scale::Real=1.0)
+    n, T = size(theta_store); Nt, D = size(Xtest); a, b = class_window(window, T)
+    ls = collect(Float64, length_scale isa Real ? [length_scale] : length_scale)
+    (size(Z) == (n, D) && length(bfeat) == n) || error("Z must be (n, D) and b of length n")
+    (length(ls) == 1 || length(ls) == D) || error("dimensions of Xtest and length_scale do not match")
+    length(ytest) == Nt || error("ytest must have one target per test row")
+    0 <= a < b <= T || error("the window must lie in 1:$T")
+    o = PredictiveOut(Nt, T)
+    check(ccall((:gpt_gpnt_predictive_x, LIB), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                 Float64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Float64, Float64,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}),
+                theta_store, Xtest, vec(ytest), Nt, D, ls, length(ls), sigma_RBF, Z, vec(bfeat), n,
+                T, a, b, scale, signal_var, o.fmu, o.fs2, o.lp, o.lpmix, o.sums, o.covered, o.rmse,
+                o.srm))
+    return predictive_result(o, Nt, signal_var, scale)
 end
 
 # GPNT_SGLDclass(phi,y,sigma_theta,m,eps_theta,decay_rate,burnin,maxepoch,param_seed)
