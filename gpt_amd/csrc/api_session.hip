@@ -902,7 +902,7 @@ extern "C" void gpt_sgld_session_destroy(gpt_sgld_session* s) {
 
 // ====================================================================== test entries
 // expm of `count` row-major nn × nn host matrices on the device, by the wave engine's
-// register-blocked Padé (modes 0 and 4) or the grid engine's wave_expm (modes 1 and 3); the
+// register-blocked Padé (modes 0 and 4) or the grid engine's wave_expm (modes 1, 3 and 5); the
 // (mode, nn) pairs are listed at wv_expm_check_kernel (wave.hip).
 extern "C" int gpt_debug_expm(int32_t nn, int32_t count, int32_t mode, const double* A, double* E,
                               int32_t* bad) {

@@ -37,10 +37,13 @@ constexpr int kChainQS = 264;     // w·V row stride; slot kChainQP of a row is 
 
 constexpr int kChainMMax = 256;   // largest minibatch the engine takes
 
-// Per-wave scratch after the batch: S0 = max(expm<2r> scratch, noise slots) | E[:,1:r] | grams.
-GPT_HD constexpr int chain_scratch_dbl(int r) {
+// Per-wave scratch after the batch: S0 = max(expm<2r> scratch, noise slots) | X1 | grams.
+// X1 is expm(−tA)'s own 7r² scratch where the carve has the room (own_x1: the wide build), so
+// that E stays where the 2r × 2r expm left it; otherwise the 2r·r slot E[:,1:r] is copied to
+// before expm(−tA) reuses S0.
+GPT_HD constexpr int chain_scratch_dbl(int r, bool own_x1) {
   const int s0a = 7 * 4 * r * r, s0b = 64 * 8;     // expm scratch | noise slots (8 row blocks)
-  return (s0a > s0b ? s0a : s0b) + 2 * r * r + 3 * r * r + r;
+  return (s0a > s0b ? s0a : s0b) + (own_x1 ? 7 : 2) * r * r + 3 * r * r + r;
 }
 GPT_HD constexpr int al16c(int x) { return (x + 15) & ~15; }
 
@@ -67,7 +70,10 @@ struct ChainLds {
   // (per-wave parts sized for the WV waves of the build: at WV = 4 the carve plus the row staging
   // stays under 80 KB, two chains per CU)
   static constexpr int L_dbl = G * kChainQS + WV * G * R * kChainRunS;
-  static constexpr int x_dbl = chain_scratch_dbl(R);
+  // expm(−tA) has scratch of its own in the wide build; the WV = 4 carve (two chains per CU, under
+  // 80 KB with the row staging) has no room for it
+  static constexpr bool own_x1 = WV == kChainDMax;
+  static constexpr int x_dbl = chain_scratch_dbl(R, own_x1);
   // after the union: the U noise's (sin, cos)(2πi/256) table (WV = 8 builds; the WV = 4 carve
   // stays under 80 KB for two chains per CU and draws its angles by polynomial)
   static constexpr int o_tab = al16c(o_un + 8 * (L_dbl > x_dbl * WV ? L_dbl : x_dbl * WV));
@@ -607,9 +613,11 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   {
     constexpr int NN = 2 * R;
     constexpr int S0 = (7 * NN * NN > 64 * 8) ? 7 * NN * NN : 64 * 8;
-    double* X0 = X;                          // expm scratch (7·NN²), reused for expm(−tA)
-    double* Ec = X + S0;                     // E[:, 0:r]  (NN × R)
-    double* Mg = Ec + NN * R;                // UᵀW, then Ag | Sg | nrm
+    constexpr bool kOwnX1 = L::own_x1;
+    double* X0 = X;                          // expm scratch (7·NN²)
+    double* Ec = X + S0;                     // E[:, 0:r] (NN × R) where expm(−tA) reuses X0, or
+    double* X1 = kOwnX1 ? X + S0 : X0;       // expm(−tA)'s own scratch (7·R²)
+    double* Mg = X + S0 + (kOwnX1 ? 7 * R * R : NN * R);   // UᵀW, then Ag | Sg | nrm
     double* Ag = Mg + R * R;
     double* Sg = Ag + R * R;
     double* nr = Sg + R * R;
@@ -663,35 +671,36 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
           }
           wave_sum_to_lds<R>(v, Sg + a * R);    // S[a][b] valid for b >= a
         }
-        wave_sync();
-        for (int o = lane; o < R * R; o += 64) {
-          const int i = o / R, b = o - i * R;
-          Ag[o] = (Mg[o] - Mg[b * R + i]) / 2;
-          if (i > b) Sg[o] = Sg[b * R + i];
-        }
       }
       wave_sync();
+      // t·[A −S; I A] (and −t·A, where expm(−tA) has its own scratch) straight from the Grams:
+      // A = (M − Mᵀ)/2, S from its upper triangle
       const double tt = sq;
       for (int o = lane; o < NN * NN; o += 64) {
         const int i = o / NN, j = o - i * NN;
+        const int ia = i < R ? i : i - R, ja = j < R ? j : j - R;
+        const double a = (Mg[ia * R + ja] - Mg[ja * R + ia]) / 2;
         double v;
-        if (i < R) v = j < R ? Ag[i * R + j] : -Sg[i * R + (j - R)];
-        else v = j < R ? (i - R == j ? 1.0 : 0.0) : Ag[(i - R) * R + (j - R)];
+        if (i < R) v = j < R ? a : -Sg[ia <= ja ? ia * R + ja : ja * R + ia];
+        else v = j < R ? (ia == j ? 1.0 : 0.0) : a;
         X0[o] = tt * v;
+        if (kOwnX1 && i < R && j < R) X1[ia * R + ja] = -tt * a;
+        if (!kOwnX1 && i < R && j < R) Ag[ia * R + ja] = a;
       }
       wave_sync();
       long long* xst = (CHAIN_SSTAMP && P.stamps && k == 0)
                            ? P.stamps + (size_t)(4 * gridDim.x + blockIdx.x) * kStamps : nullptr;
       const bool bad = wave_expm<NN>(X0, xst);
       SSTAMP(7);
-      for (int o = lane; o < NN * R; o += 64) {
-        const int a = o / R, l = o - a * R;
-        Ec[o] = X0[NN * NN + a * NN + l];
+      if constexpr (!kOwnX1) {                // expm(−tA) in the same scratch: E[:, 0:r] moves out
+        for (int o = lane; o < NN * R; o += 64) {
+          const int a = o / R, l = o - a * R;
+          Ec[o] = X0[NN * NN + a * NN + l];
+        }
+        wave_sync();
+        for (int o = lane; o < R * R; o += 64) X1[o] = -tt * Ag[o];
+        wave_sync();
       }
-      wave_sync();
-      double* X1 = X0;                        // expm(−tA) in the same scratch
-      for (int o = lane; o < R * R; o += 64) X1[o] = -tt * Ag[o];
-      wave_sync();
       wave_expm<R>(X1, xst ? xst + (size_t)gridDim.x * kStamps : nullptr);
       if (bad && lane == 0) flag[0] = 1;
       CSTAMP(6);
@@ -700,12 +709,14 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
       // F = E[:,1:r]·expm(−tA) (NN × R, on the wave), then tmpU = [U mom]·F row by row
       // (GPT_SGLD.jl:35 with the two products associated the other way), then normalisation
       double* F = Mg;                         // grams are dead: reuse their slots
+      const double* El = kOwnX1 ? X0 + NN * NN : Ec;   // E[:, 0:r], row stride
+      constexpr int ES = kOwnX1 ? NN : R;
       wave_sync();
       for (int o = lane; o < NN * R; o += 64) {
         const int a = o / R, l = o - a * R;
         double s = 0.0;
 #pragma unroll
-        for (int c2 = 0; c2 < R; ++c2) s = fma(Ec[a * R + c2], mx[c2 * R + l], s);
+        for (int c2 = 0; c2 < R; ++c2) s = fma(El[a * ES + c2], mx[c2 * R + l], s);
         F[o] = s;
       }
       wave_sync();

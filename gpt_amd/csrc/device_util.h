@@ -804,7 +804,7 @@ __device__ __forceinline__ double readlane_d(double v, int lane) {
 // rows and multipliers are broadcast with v_readlane (no LDS round trips).  Returns false
 // (nothing written) when M is not diagonally dominant — the caller then pivots.
 template <int NN>
-__device__ __forceinline__ bool wave_solve_dd(const double* M, double* X) {
+__device__ __forceinline__ bool wave_solve_dd(const double* M, double* X, bool* nan = nullptr) {
   const int lane = threadIdx.x & 63;
   bool dd = true;
   if (lane < NN) {
@@ -850,6 +850,12 @@ __device__ __forceinline__ bool wave_solve_dd(const double* M, double* X) {
   if (lane >= NN && lane < 2 * NN) {
 #pragma unroll
     for (int i = 0; i < NN; ++i) X[i * NN + lane - NN] = col[i];
+  }
+  if (nan) {                                  // a NaN in the solution, from the lanes that hold it
+    bool b = false;
+#pragma unroll
+    for (int i = 0; i < NN; ++i) b |= (col[i] != col[i]);
+    *nan = __any(b && lane >= NN && lane < 2 * NN);
   }
   wave_sync();
   return true;
@@ -924,14 +930,117 @@ __device__ __noinline__ bool wave_solve_dd2(const double* Mg, double* Xg, double
   return true;
 }
 
+// ---- register-resident Padé polynomial of wave_expm (degrees 3..9) for NN <= 10.
+// Each working lane keeps its entries of the current power P and of U and V in registers through
+// the whole polynomial: one entry per lane up to NN = 8, a 1 × 2 block (two adjacent columns of a
+// row) on 50 lanes at NN = 10 (NN = 9 has neither and keeps the LDS form).  Only product operands
+// go through LDS.  (wave_mm's 2 × 2 blocks on 25 lanes would hold two rows and two column pairs,
+// 80 VGPRs of operands, in flight per product: more than the chain kernel leaves this function.)
+template <int NN>
+struct PadeReg {
+  static constexpr int BC = NN > 8 ? 2 : 1, NL = NN * NN / BC;   // block width, working lanes
+  static constexpr bool ok = NN <= 10 && NN % BC == 0 && NL <= 64;
+};
+
+// Entries (i, j0 .. j0+BC-1) of A·B, the operand reads in NH groups over t: the reads of a group
+// are issued together before its FMA chains start, so a product costs NH LDS latencies.  (One
+// group at NN = 10, 30 operand doubles in flight, put wave_expm<10> above what the chain kernel
+// leaves it beside U and its accumulator, and the kernel spilled.)  Each entry is
+// Σ_t A[i,t]·B[t,j] accumulated in t order, the doubles of wave_mm.
+template <int NN, int BC, int NH>
+__device__ __forceinline__ void wave_mm_reg(const double* A, const double* B, int i, int j0,
+                                            double (&c)[BC]) {
+  constexpr int TH = (NN + NH - 1) / NH;
+#pragma unroll
+  for (int y = 0; y < BC; ++y) c[y] = 0.0;
+#pragma unroll
+  for (int h = 0; h < NH; ++h) {
+    if (h) __builtin_amdgcn_sched_barrier(0);   // a group's reads stay behind the last group's FMAs
+    double a[TH], b[TH][BC];
+#pragma unroll
+    for (int t = 0; t < TH; ++t)
+      if (h * TH + t < NN) a[t] = A[i * NN + h * TH + t];
+#pragma unroll
+    for (int t = 0; t < TH; ++t)
+#pragma unroll
+      for (int y = 0; y < BC; ++y)
+        if (h * TH + t < NN) b[t][y] = B[(h * TH + t) * NN + j0 + y];
+#pragma unroll
+    for (int y = 0; y < BC; ++y)
+#pragma unroll
+      for (int t = 0; t < TH; ++t)
+        if (h * TH + t < NN) c[y] = fma(a[t], b[t][y], c[y]);
+  }
+}
+
+// U = A·(b1 I + b3 A² + …), V = b0 I + b2 A² + … of the degree-(2K+1) Padé approximant with
+// coefficients C, for A in S[0..NN²); leaves M = V − U at S + 2NN² and X = V + U at S + NN²
+// (where wave_expm's solve takes them), ordered by a wave_sync().  LDS traffic: A is read; A²,
+// the higher powers and the inner polynomial of U are written once each as product operands, with
+// one wave_sync() per product; the identity terms, the updates and M, X are register work in the
+// product epilogues.  The doubles are those of wave_expm's LDS form.
+template <int NN>
+__device__ __forceinline__ void wave_pade_reg(double* S, const double* C, int K) {
+  constexpr int BC = PadeReg<NN>::BC, NL = PadeReg<NN>::NL, q = NN * NN;
+  const int lane = threadIdx.x & 63;
+  // idle lanes shadow lane 0, its stores included (the same doubles to the same addresses), so
+  // the polynomial is straight-line code
+  const int o0 = lane < NL ? lane * BC : 0;
+  const int i = o0 / NN, j0 = o0 - i * NN;
+  double* A2 = S + q;
+  // read groups per product: two at NN = 10, three in the power loop, whose products run with P,
+  // U and V live (it is entered from degree 5 on; the geodesic's matrices mostly take 3 and 5)
+  constexpr int NH = NN > 8 ? 2 : 1, NHL = NN > 8 ? 3 : 1;
+  double P[BC], U[BC], V[BC];
+  wave_mm_reg<NN, BC, NH>(S, S, i, j0, P);
+  {
+    const double c0 = C[0], c1 = C[1], cv = C[2], cu = C[3];
+#pragma unroll
+    for (int y = 0; y < BC; ++y) {
+      const bool d = i == j0 + y;
+      const double u0 = d ? c1 : 0.0, v0 = d ? c0 : 0.0;
+      U[y] = u0 + cu * P[y];
+      V[y] = v0 + cv * P[y];
+    }
+  }
+  double* Pk = A2;                            // where the power of the last product goes
+  for (int kk = 2; kk <= K; ++kk) {
+#pragma unroll
+    for (int y = 0; y < BC; ++y) Pk[o0 + y] = P[y];
+    wave_sync();
+    wave_mm_reg<NN, BC, NHL>(Pk, A2, i, j0, P);    // P = P·A2
+    const double cu = C[2 * kk + 1], cv = C[2 * kk];
+#pragma unroll
+    for (int y = 0; y < BC; ++y) {
+      U[y] = U[y] + cu * P[y];
+      V[y] = V[y] + cv * P[y];
+    }
+    Pk = kk == 2 ? S + 2 * q : S + 6 * q;
+  }
+  double* Ub = S + 4 * q;
+#pragma unroll
+  for (int y = 0; y < BC; ++y) Ub[o0 + y] = U[y];
+  wave_sync();
+  wave_mm_reg<NN, BC, NH>(S, Ub, i, j0, U);       // U = A·U
+#pragma unroll
+  for (int y = 0; y < BC; ++y) {
+    S[2 * q + o0 + y] = V[y] - U[y];
+    S[q + o0 + y] = V[y] + U[y];
+  }
+  wave_sync();
+}
+
 // expm(A) for an NN×NN matrix held in S[0..NN²) (row-major; overwritten).  Padé
 // scaling-and-squaring of Julia Base 0.3 expm! (Higham 2005; thresholds 0.015/0.25/0.95/2.1,
 // 13th order above, θ13 = 5.4).  Scratch S: 7 NN² doubles; the result is left at S + NN².
 // Returns true if the result contains a NaN (the geod bail-out of GPT_SGLD.jl:23-26).
 // kRegLU2 = false keeps the LDS GEPP for 32 < NN <= 64 (callers at a 128-VGPR budget, where the
-// two-pass register LU spills).
-template <int NN, bool kRegLU2 = true>
+// two-pass register LU spills).  kRegPoly = false keeps the LDS form of the degree 3..9 polynomial
+// at the sizes that otherwise take the register-resident one (PadeReg; the unit check compares
+// the two on the device).
+template <int NN, bool kRegLU2 = true, bool kRegPoly = true>
 __device__ bool wave_expm(double* S, long long* st = nullptr) {
+  constexpr bool kReg = kRegPoly && PadeReg<NN>::ok;
   // S is LDS (every caller's expm scratch): said so, the compiler infers the local address space
   // for everything derived from it and emits ds_* instead of flat_* (this function is compiled
   // out of line, where the caller's address space is not visible)
@@ -966,34 +1075,40 @@ __device__ bool wave_expm(double* S, long long* st = nullptr) {
   }
   const double nA = wave_max(cs);
   int si = 0;
+  bool mx = false;                            // M = V − U and X = V + U are formed already
   if (nA <= 2.1) {
     const int deg = nA > 0.95 ? 9 : (nA > 0.25 ? 7 : (nA > 0.015 ? 5 : 3));
     if (st && lane == 0) st[10] = deg;
     const double* C = kPade[(deg - 3) / 2];   // wave-uniform: scalar loads from constant memory
-    wave_mm<NN>(A, A, A2);
-    const double c0 = C[0], c1 = C[1];
-    for (int o = lane; o < q; o += 64) {
-      const double id = (o / NN == o - (o / NN) * NN) ? 1.0 : 0.0;
-      T[o] = id;
-      U[o] = c1 * id;
-      V[o] = c0 * id;
-    }
-    wave_sync();
-    for (int kk = 1; kk <= (deg - 1) / 2; ++kk) {
-      if (kk > 1) wave_mm<NN>(T, A2, A4);   // P = P·A2 (A4 is free scratch here); P1 = A2
-      const double* Pk = kk > 1 ? A4 : A2;
-      const double cu = C[2 * kk + 1], cv = C[2 * kk];
+    if constexpr (kReg) {
+      wave_pade_reg<NN>(S, C, (deg - 1) / 2);
+      mx = true;
+    } else {
+      wave_mm<NN>(A, A, A2);
+      const double c0 = C[0], c1 = C[1];
       for (int o = lane; o < q; o += 64) {
-        const double p = Pk[o];
-        T[o] = p;
-        U[o] = U[o] + cu * p;
-        V[o] = V[o] + cv * p;
+        const double id = (o / NN == o - (o / NN) * NN) ? 1.0 : 0.0;
+        T[o] = id;
+        U[o] = c1 * id;
+        V[o] = c0 * id;
       }
       wave_sync();
+      for (int kk = 1; kk <= (deg - 1) / 2; ++kk) {
+        if (kk > 1) wave_mm<NN>(T, A2, A4);   // P = P·A2 (A4 is free scratch here); P1 = A2
+        const double* Pk = kk > 1 ? A4 : A2;
+        const double cu = C[2 * kk + 1], cv = C[2 * kk];
+        for (int o = lane; o < q; o += 64) {
+          const double p = Pk[o];
+          T[o] = p;
+          U[o] = U[o] + cu * p;
+          V[o] = V[o] + cv * p;
+        }
+        wave_sync();
+      }
+      wave_mm<NN>(A, U, A6);
+      for (int o = lane; o < q; o += 64) U[o] = A6[o];
+      wave_sync();
     }
-    wave_mm<NN>(A, U, A6);
-    for (int o = lane; o < q; o += 64) U[o] = A6[o];
-    wave_sync();
   } else {
     // as many squarings as Julia's expm! takes (no cap; ‖A‖₁ <= DBL_MAX bounds si by 1022)
     const double s = log2(nA / 5.4);
@@ -1031,13 +1146,15 @@ __device__ bool wave_expm(double* S, long long* st = nullptr) {
   GPT_XST(12);
   double* M = A4;      // dead from here on
   double* X = A2;
-  for (int o = lane; o < q; o += 64) {
-    M[o] = V[o] - U[o];
-    X[o] = V[o] + U[o];
+  if (!mx) {
+    for (int o = lane; o < q; o += 64) {
+      M[o] = V[o] - U[o];
+      X[o] = V[o] + U[o];
+    }
+    wave_sync();
   }
-  wave_sync();
-  bool solved = false;
-  if constexpr (2 * NN <= 64) solved = wave_solve_dd<NN>(M, X);
+  bool solved = false, nanx = false;
+  if constexpr (2 * NN <= 64) solved = wave_solve_dd<NN>(M, X, kReg ? &nanx : nullptr);
   else if constexpr (kRegLU2 && NN <= 64) solved = wave_solve_dd2<NN>(M, X, U);   // U, V dead here
   if (!solved) wave_solve<NN>(M, X, st);
   GPT_XST(13);
@@ -1048,6 +1165,7 @@ __device__ bool wave_expm(double* S, long long* st = nullptr) {
   }
   GPT_XST(14);
 #undef GPT_XST
+  if (kReg && solved && si == 0) return nanx;   // the solve's lanes hold X: no LDS pass over it
   bool bad = false;
   for (int o = lane; o < q; o += 64) bad |= (X[o] != X[o]);
   return __any(bad);

@@ -1160,6 +1160,8 @@ namespace gpt {
 //   3  wave_expm<NN, false> (the LDS GEPP of the 1024-thread kernels)          NN = 40
 //   4  wv_expm<NN> with ncols = NN/2, as geod calls it; the whole slot is copied out and
 //      columns [0, NN/2) are the result                   NN in {12,16,20,24,30,32,40}
+//   5  wave_expm<NN, true, false>: the LDS form of the degree 3..9 polynomial at the sizes where
+//      mode 1 takes the register-resident one             NN in {1,2,3,4,5,6,8,10}
 template <int NN, int MODE>
 __global__ __launch_bounds__(64) void wv_expm_check_kernel(const double* A, double* E, int32_t* bad,
                                                            long long* st) {
@@ -1182,6 +1184,8 @@ __global__ __launch_bounds__(64) void wv_expm_check_kernel(const double* A, doub
     b = wv_expm<NN>(S0, S0 + NN * NN, S0 + 2 * NN * NN, lane, nullptr, NN / 2);
   } else if constexpr (MODE == 3) {
     b = wave_expm<NN, false>(S0);
+  } else if constexpr (MODE == 5) {
+    b = wave_expm<NN, true, false>(S0);
   } else {
     b = wave_expm<NN>(S0);
   }
@@ -1194,7 +1198,7 @@ template <int NN, int MODE>
 static hipError_t expm_check_launch(int count, const double* A, double* E, int32_t* bad,
                                     hipStream_t st, long long* stamps) {
   // wave_expm's scratch is seven NN² blocks, wv_expm's the three slots geod gives it
-  const size_t lds = 8 * (size_t)(MODE == 1 || MODE == 3 ? 7 : 3) * NN * NN;
+  const size_t lds = 8 * (size_t)(MODE == 1 || MODE == 3 || MODE == 5 ? 7 : 3) * NN * NN;
   hipError_t e = hipFuncSetAttribute((const void*)wv_expm_check_kernel<NN, MODE>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return e;
@@ -1218,6 +1222,7 @@ hipError_t launch_expm_check(int nn, int count, const double* A, double* E, int3
     case 2: return go(Int<2>{}, Geod{});
     case 3: return go(Int<3>{}, IntList<40>{});
     case 4: return go(Int<4>{}, Geod{});
+    case 5: return go(Int<5>{}, IntList<1, 2, 3, 4, 5, 6, 8, 10>{});
     default: return hipErrorInvalidValue;
   }
 }

@@ -224,6 +224,8 @@ int64_t gpt_sgld_timeline_slots(void);
  *   mode 4  wv_expm asked for the first nn/2 result columns only, as the wave engine's geodesic
  *           calls it; E_c is the whole result slot, of which columns [0, nn/2) are defined;
  *           nn in {12,16,20,24,30,32,40}
+ *   mode 5  wave_expm with the degree 3..9 polynomial kept in its LDS form, at the sizes where
+ *           mode 1 runs it register-resident (the two must agree bitwise); nn in {1,2,3,4,5,6,8,10}
  * (mode 2 is gpt_debug_expm_stamps' timing run.)  Any other (mode, nn) is GPT_ERR_BAD_DIMS.
  * bad[c] = 1 when E_c holds a NaN (the geodesic bail-out test); for an A_c with an Inf or NaN
  * entry bad[c] = 1 and E_c is all NaN. */
