@@ -50,6 +50,7 @@ GPT_HD constexpr int al16c(int x) { return (x + 15) & ~15; }
 // LDS carve of chain_kernel<R, J, G>, fixed at compile time: every table is sized for the
 // engine's maxima (kChainDMax dimensions, Q <= kChainQP, m <= kChainMMax), so every LDS address
 // is a constant and none of them occupies a scalar register (the kernel sits at the SGPR limit).
+// The batch's row indices are not in the carve: they are a static array beside the row staging.
 template <int R, int G, int WV = kChainDMax>
 struct ChainLds {
   static constexpr int DRG = kChainDMax * R * G;          // temp entries of a slot
@@ -57,8 +58,7 @@ struct ChainLds {
   static constexpr int NTMAX = kChainQPL * G;             // V tasks at Q = kChainQP
   static constexpr int o_IT = 0;                                         // int[kChainDMax][Q]
   static constexpr int o_w = al16c(o_IT + 4 * kChainQP * kChainDMax);    // double[Q]
-  static constexpr int o_idx = al16c(o_w + 8 * kChainQP);                // int[m]
-  static constexpr int o_y = al16c(o_idx + 4 * kChainMMax);              // double[m]
+  static constexpr int o_y = al16c(o_w + 8 * kChainQP);                  // double[m]
   static constexpr int o_temp = al16c(o_y + 8 * kChainMMax);             // 2 slots
   static constexpr int o_fp = al16c(o_temp + 8 * 2 * TS);
   static constexpr int o_gwp = al16c(o_fp + 8 * kChainQPL * G);
@@ -178,6 +178,13 @@ struct ChainLds {
                (slot) % 8] = (long long)__builtin_amdgcn_s_memtime();                       \
   } while (0)
 
+// Row j = lane + 64·jj of a U^(k) held J rows per lane is inside the n rows.  chain_J picks J with
+// n > 64·J/2 for J >= 2, so the lower half of the row blocks needs no compare.
+template <int J>
+__device__ __forceinline__ bool row_in(int jj, int j, int n) {
+  return (J >= 2 && jj < J / 2) || j < n;
+}
+
 // Workgroup barrier that orders LDS only: an LDS-DMA prefetch stays in flight across it
 // (__syncthreads() would also drain vmcnt).
 __device__ __forceinline__ void lds_barrier() {
@@ -194,6 +201,11 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
                                                                 int t_local, int nsteps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ __attribute__((aligned(16))) double pbuf[kChainBufs * WV * G * 64 * J];   // row staging
+  // Row indices of two batches: batch t's in slot t & 1 and batch t + 1's in the other; at the end
+  // of step t batch t + 2's go by LDS-DMA into the slot batch t has left.  An array of its own, not
+  // a piece of smem: the compiler orders the LDS reads of an array behind the pending DMA into that
+  // array only, and the whole Stiefel phase reads smem with the row DMA in flight.
+  __shared__ __attribute__((aligned(16))) int ibuf[2 * kChainMMax];
   // Chain fields are read through Cp at their point of use (scalar loads) rather than held in
   // SGPRs across the batch loop, where SGPR pressure spills into VGPR lanes.
   const ChainDesc* Cp = chains + blockIdx.x;
@@ -203,7 +215,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   const int NCH = (Q + 63) / 64, NT = NCH * G;                  // q chunks of 64, V tasks
   int* IT_l = (int*)(smem + L::o_IT);
   double* w_l = (double*)(smem + L::o_w);
-  int* idx_l = (int*)(smem + L::o_idx);
+  int* idx_l = ibuf;                                            // set at the top of every step
   double* y_l = (double*)(smem + L::o_y);
   double* temp_l = (double*)(smem + L::o_temp);
   double* fp_l = (double*)(smem + L::o_fp);
@@ -233,15 +245,41 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   CSTAMP(0);
   const long long tend = min(P.total_steps, t0 + (long long)nsteps);
 
-  // batch of step tt: its rows of the epoch order and its length
-  auto batch_of = [&](long long tt, int& bt) -> const int32_t* {
-    const int ee = (int)(tt / P.nb), bb = (int)(tt - (long long)ee * P.nb);
-    bt = min(m, P.N - bb * m);
-    return Cp->order + (size_t)(ee & 1) * P.N + (size_t)bb * m;
+  // Batch bb of the epoch with parity ep: its rows of the epoch order and its length.  The
+  // position (ep, bb) of step t and the store schedule are formed here once and carried from step
+  // to step, so the step loop has no integer division.
+  auto batch_at = [&](const int32_t* order, int ep_, int bb_, int& bt) -> const int32_t* {
+    bt = min(m, P.N - bb_ * m);
+    return order + (size_t)ep_ * P.N + (size_t)bb_ * m;
+  };
+  auto next_pos = [&](int& ep_, int& bb_) {      // a launch stays in its epoch; wrap all the same
+    if (++bb_ == P.nb) { bb_ = 0; ep_ ^= 1; }
   };
   long long t = t0;
+  int ep, bb;
+  {
+    const int ee = (int)(t0 / P.nb);
+    bb = (int)(t0 - (long long)ee * P.nb);
+    ep = ee & 1;
+  }
+  // steps until the next stored sample (0: this step stores) and that sample's slot
+  int st_cd;
+  long long st_slot;
+  {
+    const long long post0 = t0 - P.burnin_steps;
+    long long cd;
+    if (post0 < 0) {
+      cd = P.store_every - 1 - post0;
+      st_slot = 0;
+    } else {
+      const long long rem = (post0 + 1) % P.store_every;
+      cd = rem ? P.store_every - rem : 0;
+      st_slot = (post0 + 1 + cd) / P.store_every - 1;
+    }
+    st_cd = (int)min(cd, (long long)0x7fffffff);   // a launch has fewer steps than that
+  }
   int Bt;
-  const int32_t* ord = batch_of(t, Bt);
+  const int32_t* ord = batch_at(Cp->order, ep, bb, Bt);
   const long long koff = (long long)n * k, rstride = (long long)n * D;
   const double* phi_k = uni_ptr(Cp->phi) + koff;
   // Stage rows g0n .. g0n+G-1 of this wave's dimension into pw (lane-linear LDS image: double j
@@ -308,10 +346,18 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   if (tid == 0) flag[0] = 0;
   {
     const double* yv = Cp->y;
+    int* i0_l = ibuf + ((int)t0 & 1) * kChainMMax;
     for (int i = tid; i < Bt; i += NTH) {
       const int row = gptr(ord)[i];
-      idx_l[i] = row;
+      i0_l[i] = row;
       y_l[i] = gptr(yv)[row];
+    }
+    if (t0 + 1 < tend) {                 // the second batch's row indices (later ones: by DMA)
+      int e1 = ep, b1 = bb, B1;
+      next_pos(e1, b1);
+      const int32_t* ord1 = batch_at(Cp->order, e1, b1, B1);
+      int* i1_l = ibuf + ((int)(t0 + 1) & 1) * kChainMMax;
+      for (int i = tid; i < B1; i += NTH) i1_l[i] = gptr(ord1)[i];
     }
   }
   double u[J][R];
@@ -341,6 +387,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   // it and reload it (and values derived from it) in the Stiefel phase, each reload a vmcnt(0)
   // wait behind the next batch's row DMA (−4 % step time)
   const int lane = lane_id(), tid = 64 * k + lane;
+  idx_l = ibuf + ((int)t & 1) * kChainMMax;
   for (int o = tid; o < G; o += NTH) wVr[o * kChainQS + kChainQP] = 0.0;   // gather zero slots
   // (re-derived every step rather than held across the Stiefel phase, where registers are short)
   // this wave's V-task temp indices (< 256, four per register), fixed for the step
@@ -503,11 +550,24 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   // that the load is not hoisted out of the step loop (the fields would then hold ~40 SGPRs)
   const ChainDesc* Cq = Cp;
   asm volatile("" : "+s"(Cq));
-  const ChainDesc C = *Cq;
-  const double cN = (double)P.N / (double)Bt;
-  const long long post = t - P.burnin_steps;
-  const bool store = post >= 0 && ((post + 1) % P.store_every) == 0;
-  const long long slot_s = store ? (post + 1) / P.store_every - 1 : 0;
+  // the fields in use, through the constant address space: scalar loads into SGPRs (as a plain
+  // struct copy behind the opaque pointer they came by vector loads, one uniform copy per lane,
+  // and the ones that live to the end of the step were spilled to scratch)
+  ChainDesc C;
+  {
+    const auto* Cc = cptr(Cq);
+    C.y = Cc->y; C.order = Cc->order; C.w = Cc->w; C.U = Cc->U;
+    C.w_store = Cc->w_store; C.U_store = Cc->U_store; C.diag = Cc->diag; C.status = Cc->status;
+    C.seed = Cc->seed; C.epsw = Cc->epsw; C.epsU = Cc->epsU; C.signal_var = Cc->signal_var;
+    C.sigma_w = Cc->sigma_w;
+  }
+  // N converted here, from a copy the compiler cannot see through: hoisted out of the step loop
+  // the double was spilled, and its reload waited on the loads in flight
+  int Nn = P.N;
+  asm volatile("" : "+s"(Nn));
+  const double cN = (double)Nn / (double)Bt;
+  const bool store = st_cd == 0;
+  const long long slot_s = store ? st_slot : 0;
 
   // ---- w: gradw and the Langevin step (GPT_SGLD.jl:393, 411-414)
 #pragma unroll
@@ -520,6 +580,17 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   __syncthreads();
   SSTAMP(1);
   CHAIN_SETPRIO(true);
+  // Next batch: its position and length from the carried one, and this thread's target, gathered
+  // through the row index that is already in LDS.  The load is in flight across the w update and
+  // written to y_l behind it (every wave is past the batch loop, the last reader of y_l).
+  int ep1 = ep, bb1 = bb, Bn = 0;
+  next_pos(ep1, bb1);
+  const int* idx_n = ibuf + ((int)(t + 1) & 1) * kChainMMax;
+  double y_n = 0.0;
+  if (t + 1 < tend) {
+    Bn = min(m, P.N - bb1 * m);
+    y_n = gptr(C.y)[idx_n[min(tid, Bn - 1)]];
+  }
   {
     const double inv_sw2 = 1.0 / (C.sigma_w * C.sigma_w);
     const double sqe = sqrt(C.epsw);
@@ -545,20 +616,35 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
     }
   }
   SSTAMP(2);
-  int Bn = 0;
-  const int32_t* ordn = nullptr;
+  // y_n is taken here on every path: left to the branch below, the compiler's wait for a load it
+  // still counts as pending where that branch is skipped lands behind the row DMA
+  asm volatile("" : "+v"(y_n));
   if (t + 1 < tend) {
-    // every wave is past the batch loop: the next batch's indices, targets and first rows
-    ordn = batch_of(t + 1, Bn);
-    for (int i = tid; i < Bn; i += NTH) {
-      const int row = gptr(ordn)[i];
-      idx_l[i] = row;
-      y_l[i] = gptr(Cp->y)[row];
-    }
+    // written by every lane, no exec-masked block: lanes past the batch hold the last row's
+    // target and write it to the last row's slot again
+    y_l[min(tid, Bn - 1)] = y_n;
+    for (int i = tid + NTH; i < Bn; i += NTH) y_l[i] = gptr(C.y)[idx_n[i]];   // m > 64·D only
+    // the next batch's first rows, their indices from LDS: no global load in front of the DMA
     int rows0[G];
 #pragma unroll
-    for (int gg = 0; gg < G; ++gg) rows0[gg] = gptr(ordn)[min(gg, Bn - 1)];
+    for (int gg = 0; gg < G; ++gg) rows0[gg] = uni(idx_n[min(gg, Bn - 1)]);
     stage_rows(rows0, lane, pw0);
+    // The row indices of the batch after that go by LDS-DMA (4-byte pieces, any alignment) into
+    // the slot this step's batch has left; the DMA is complete at the next step's first
+    // vmcnt(0) and visible to every wave at its first barrier, a step before the first read.
+    if (t + 2 < tend) {
+      int ep2 = ep1, bb2 = bb1, B2;
+      next_pos(ep2, bb2);
+      const int32_t* ord2 = batch_at(C.order, ep2, bb2, B2);
+#pragma unroll
+      for (int x = 0; x < kChainMMax / 64; ++x) {     // chunk 64·k + x·NTH, uniform guards
+        const int c0 = 64 * k + x * NTH;
+        if (c0 < B2)
+          __builtin_amdgcn_global_load_lds(
+              (const __attribute__((address_space(1))) void*)(ord2 + min(c0 + lane, B2 - 1)),
+              (__attribute__((address_space(3))) void*)(idx_l + c0), 4, 0, 0);
+      }
+    }
   }
   CSTAMP(3);
   SSTAMP(3);
@@ -593,12 +679,18 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
 #pragma unroll
       for (int L = 0; L < R; ++L) {
         if (l == L) {
+          // the column's noise slots read by every lane, all in flight behind one wait (slot
+          // indices are always in range): read under the row predicate, each slot compiled to an
+          // exec-masked block with an LDS round trip of its own
+          double xv[J];
+#pragma unroll
+          for (int jj = 0; jj < J; ++jj) xv[jj] = xi_l[jj * 64 + lane];
 #pragma unroll
           for (int jj = 0; jj < J; ++jj) {
-            const int j = lane + 64 * jj;
-            const double Gv = j < n ? acc[jj][L] * cU : 0.0;
+            const bool in = row_in<J>(jj, lane + 64 * jj, n);
+            const double Gv = in ? acc[jj][L] * cU : 0.0;
             gu2 = fma(Gv, Gv, gu2);
-            acc[jj][L] = j < n ? sq * Gv / 2 + xi_l[jj * 64 + lane] : 0.0;    // :420 drive
+            acc[jj][L] = in ? sq * Gv / 2 + xv[jj] : 0.0;    // :420 drive
           }
         }
       }
@@ -783,23 +875,31 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
       if (tid == 0) __hip_atomic_store(C.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       return;
     }
-    double* Uk = (t + 1 == tend) ? C.U + (size_t)n * R * k : nullptr;
-    double* Us = (store && C.U_store) ? C.U_store + ((size_t)slot_s * D + k) * n * R : nullptr;
+    // both targets are uniform and null on a step that neither ends the launch nor stores: held
+    // as scalars, such a step passes the write-back with one scalar branch (not one exec-masked
+    // block per (jj, l) and pointer)
+    double* Uk = uni_ptr((t + 1 == tend) ? C.U + (size_t)n * R * k : nullptr);
+    double* Us =
+        uni_ptr((store && C.U_store) ? C.U_store + ((size_t)slot_s * D + k) * n * R : nullptr);
+    if (Uk || Us) {
 #pragma unroll
-    for (int jj = 0; jj < J; ++jj) {
-      const int j = lane + 64 * jj;
-      if (j < n)
+      for (int jj = 0; jj < J; ++jj) {
+        const int j = lane + 64 * jj;
+        if (row_in<J>(jj, j, n))
 #pragma unroll
-        for (int l = 0; l < R; ++l) {
-          if (Uk) gptr_w(Uk)[j + (size_t)n * l] = u[jj][l];
-          if (Us) gptr_w(Us)[j + (size_t)n * l] = u[jj][l];
-        }
+          for (int l = 0; l < R; ++l) {
+            if (Uk) gptr_w(Uk)[j + (size_t)n * l] = u[jj][l];
+            if (Us) gptr_w(Us)[j + (size_t)n * l] = u[jj][l];
+          }
+      }
     }
     CSTAMP(7);
     SSTAMP(15);
     TSTAMP(2 + (int)(t - t0));
+    if (store) { st_cd = P.store_every - 1; ++st_slot; } else --st_cd;
     if (++t >= tend) break;
-    ord = ordn;
+    ep = ep1;
+    bb = bb1;
     Bt = Bn;
   }
 #if CHAIN_TIMELINE == 2
@@ -810,9 +910,11 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
 // ------------------------------------------------------------------------------ host side
 static_assert(contains(ChainWVs{}, kChainDMax), "the wide U phase has one wave per dimension");
 
-// Static LDS of chain_kernel<R, J, G>: the row staging buffer.
+// Static LDS of chain_kernel<R, J, G>: the row staging buffer and the two row-index slots.
 static int chain_wv(int D) { return D <= 4 ? 4 : kChainDMax; }
-static size_t chain_static_lds(int J, int WV) { return 8 * (size_t)kChainBufs * WV * kChainG * 64 * J; }
+static size_t chain_static_lds(int J, int WV) {
+  return 8 * (size_t)kChainBufs * WV * kChainG * 64 * J + 2 * 4 * kChainMMax;   // pbuf + ibuf
+}
 
 static int chain_J(int n) { return n <= 64 ? 1 : (n <= 128 ? 2 : (n <= 256 ? 4 : (n <= 512 ? 8 : 0))); }
 
