@@ -20,8 +20,10 @@ Held elsewhere (tests/<file>::<test>):
   pred_x_kernel r 1 5 20             the same (gpt_pred_mean_x launches it under GPTSGLD_PRED=direct only)
   pairs NT 1..8, rows-pf D cases     test_gpu_pred.py::test_pred_golden_parity and
                                      oracle/pred_cases.py HELD_ELSEWHERE
-  tgp_temp r 3 5                     test_gpu_tgp.py::test_gibbs_matches_oracle
-  GMC kick, geodesic r 2 5           test_gpu_parity.py::test_gmc_matches_oracle
+  tgp_temp r 3 5                     test_gpu_tgp.py::test_gibbs_matches_oracle; r 2 3 5 against mpmath:
+                                     test_gpu_gibbs.py::test_sampler_against_mpmath[tgp-*]
+  GMC kick, geodesic r 2 5           test_gpu_parity.py::test_gmc_matches_oracle; r 1 2 3 5 against
+                                     mpmath: test_gpu_gibbs.py::test_sampler_against_mpmath[gmc-*]
   cf_epoch domove 2 r 1 4 15 20      test_gpu_movielens.py::test_fullw_sideinfo_matches_oracle,
                                      ::test_fullw_sideinfo_lazy_move_wide_batches,
                                      ::test_fullw_sideinfo_live_config_full_fold,
@@ -29,7 +31,8 @@ Held elsewhere (tests/<file>::<test>):
   cf_epoch domove 0, cf_move r 4 5 20   ::test_fullw_no_side_matches_oracle, ::..._lazy_equals_eager_move
   cf_epoch domove 1 r 3 4            ::test_fullw_sideinfo_matches_oracle[sgd_stiefel | sgld_stiefel]
   cf_eval                            every run of the above
-  cfg_rows, cfg_wsystem r 3 4 15     ::test_fullw_gibbs_matches_oracle
+  cfg_rows, cfg_wsystem r 3 4 15     ::test_fullw_gibbs_matches_oracle; r 3 4 8 10 against mpmath:
+                                     test_gpu_gibbs.py::test_sampler_against_mpmath[mlg-*]
   ntc CC 2 4 8 16                    test_gpu_cls.py::test_sampler_matches_the_restatement
   cjoint value, full, CC 2..32       test_gpu_cjoint.py::test_value_and_gradient_parity
   cjoint theta CC 4 8                test_gpu_cjoint.py::test_langevin_steps
