@@ -1169,8 +1169,36 @@ class NoTensorMarginal:
                                      _ptr(lp) if lp is not None else None))
         return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
 
+    def draw_theta(self, h, S, seed=0, z=None, return_z=False):
+        """``S`` exact draws from the posterior theta | y ~ N(l, signal_var A^-1) at ``h``:
+        (n, S) = l + sqrt(signal_var) L^-T z, the layout of a GPNT_SGLD store, so it goes straight
+        to GPNT_pred, GPNT_predictive and their ``_x`` forms.  ``z`` (n, S) replaces the Philox
+        normals (stream 25, kind 2); column s depends on column s of the normals only."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        S = int(S)
+        z = _draw_z(z, self.n, S)
+        theta = np.empty((self.n, max(S, 0)), order="F")
+        zout = np.empty_like(theta) if return_z else None
+        check(lib().gpt_nlml_draw_theta(self._h, _ptr(h), h.size, S, int(seed) & (2 ** 64 - 1),
+                                        _ptr(z) if z is not None else None, _ptr(theta),
+                                        _ptr(zout) if return_z else None))
+        return (theta, zout) if return_z else theta
+
+
+def _draw_z(z, M, S):
+    """The injected normals of a draw call as (M, S) column-major, or None."""
+    if z is None:
+        return None
+    z = _f64(z)
+    if z.ndim == 1:
+        z = _f64(z.reshape((-1, 1)))
+    if z.shape != (M, S):
+        raise GPTError(GPT_ERR_BAD_DIMS, "z must be (%d, S = %d)" % (M, S))
+    return z
+
 
 GPPrediction = collections.namedtuple("GPPrediction", "ymu ys2 fmu fs2 lp")
+GPPosteriorDraw = collections.namedtuple("GPPosteriorDraw", "fmu samples cov z")
 RFFKernelError = collections.namedtuple("RFFKernelError", "frob norm_K max_abs")
 
 
@@ -1360,6 +1388,53 @@ class ExactGP:
                                     _ptr(lp) if lp is not None else None))
         return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
 
+    def draw_prior(self, h, S=1, seed=0, jitter=1e-6, z=None, return_z=False):
+        """GPrand (GaussianProcess.jl:66-80) at the object's X: (N, S) = R'z with R = chol(K +
+        jitter I); signal_var in ``h`` is not used.  ``z`` (N, S) replaces the Philox normals
+        (stream 25, kind 0).  The next ``predict`` refits."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        S = int(S)
+        z = _draw_z(z, self.N, S)
+        F = np.empty((self.N, max(S, 0)), order="F")
+        zout = np.empty_like(F) if return_z else None
+        check(lib().gpt_egp_draw_prior(self._h, _ptr(h), h.size, float(jitter), S,
+                                       int(seed) & (2 ** 64 - 1),
+                                       _ptr(z) if z is not None else None, _ptr(F),
+                                       _ptr(zout) if return_z else None))
+        return (F, zout) if return_z else F
+
+    def _posterior(self, h, Xtest, S, seed, jitter, observed, z, want_f, want_cov, want_z):
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        Xtest = _f64(Xtest)
+        if Xtest.ndim != 2 or Xtest.shape[1] != self.D:
+            raise ValueError("Xtest must be (Ntest, D)")
+        Nt, S = Xtest.shape[0], int(S)
+        z = _draw_z(z, Nt, S) if want_f else None
+        fmu = np.empty(Nt)
+        F = np.empty((Nt, max(S, 0)), order="F") if want_f else None
+        cov = np.empty((Nt, Nt), order="F") if want_cov else None
+        zout = np.empty_like(F) if want_f and want_z else None
+        check(lib().gpt_egp_draw_posterior(
+            self._h, _ptr(h), h.size, _ptr(Xtest), Nt, float(jitter), 1 if observed else 0, S,
+            int(seed) & (2 ** 64 - 1), _ptr(z) if z is not None else None, _ptr(fmu),
+            _ptr(F) if F is not None else None, _ptr(cov) if cov is not None else None,
+            _ptr(zout) if zout is not None else None))
+        return GPPosteriorDraw(fmu, F, cov, zout)
+
+    def draw_posterior(self, h, Xtest, S=1, seed=0, jitter=1e-6, observed=False, z=None,
+                       return_cov=False, return_z=False):
+        """GPpost then GPrand (GaussianProcess.jl:82-122): ``S`` joint draws of the posterior GP
+        at ``Xtest`` (Ntest <= 8192, D).  Returns (fmu, samples (Ntest, S), cov, z): fmu is
+        ``predict``'s bit for bit, samples = fmu + L z with L L' = cov + jitter I (``observed``:
+        + signal_var I, draws of observations), cov the joint covariance without either (None
+        unless ``return_cov``).  ``z`` (Ntest, S) replaces the Philox normals (stream 25, kind 1)."""
+        return self._posterior(h, Xtest, S, seed, jitter, observed, z, True, return_cov, return_z)
+
+    def predict_cov(self, h, Xtest):
+        """The joint predictive covariance k(x,x') - k(x)'(K + signal_var I)^-1 k(x') of the
+        function values at ``Xtest``, (Ntest, Ntest); its diagonal is ``predict``'s fs2."""
+        return self._posterior(h, Xtest, 0, 0, 0.0, False, None, False, True, False).cov
+
 
 def _gp_hyper(signal_var, sigma_RBF2, length_scale):
     ls = np.atleast_1d(np.asarray(length_scale, dtype=np.float64)).ravel()
@@ -1393,6 +1468,97 @@ def gp_predict_oneshot(X, y, hyperparams, Xtest, ytest=None):
                                _ptr(yt) if yt is not None else None, _ptr(fmu), _ptr(fs2),
                                _ptr(lp) if lp is not None else None))
     return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+
+
+def gp_posterior_draw_oneshot(X, y, hyperparams, Xtest, S=1, seed=0, jitter=1e-6, observed=False,
+                              z=None, return_cov=False):
+    """The one-shot host-pointer posterior draw the Julia shim binds (gpt_gp_post_rand): what
+    ExactGP(X, y).draw_posterior returns, bit for bit."""
+    X, Xtest = _f64(X), _f64(Xtest)
+    if X.ndim != 2 or Xtest.ndim != 2 or Xtest.shape[1] != X.shape[1]:
+        raise _bad_dims("X must be (N, D) and Xtest (Ntest, D)")
+    N, D = X.shape
+    Nt, S = Xtest.shape[0], int(S)
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    if y.size != N:
+        raise _bad_dims("y must have length N")
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    z = _draw_z(z, Nt, S)
+    fmu = np.empty(Nt)
+    F = np.empty((Nt, max(S, 0)), order="F")
+    cov = np.empty((Nt, Nt), order="F") if return_cov else None
+    check(lib().gpt_gp_post_rand(_ptr(X), N, D, _ptr(y), _ptr(h), h.size, _ptr(Xtest), Nt,
+                                 float(jitter), 1 if observed else 0, S, int(seed) & (2 ** 64 - 1),
+                                 _ptr(z) if z is not None else None, _ptr(fmu), _ptr(F),
+                                 _ptr(cov) if return_cov else None))
+    return GPPosteriorDraw(fmu, F, cov, None)
+
+
+def gpnt_draw_theta_oneshot(X, y, Z, b, hyperparams, S, seed=0, z=None):
+    """The one-shot host-pointer theta draw the Julia shim binds (gpt_gpnt_draw_theta): what
+    NoTensorMarginal(X, y, Z, b).draw_theta returns, bit for bit."""
+    X, Z, b = _gpnt_feature_args(X, Z, b)
+    N, D = X.shape
+    n, S = Z.shape[0], int(S)
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    if y.size != N:
+        raise _bad_dims("y must have length N")
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    z = _draw_z(z, n, S)
+    theta = np.empty((n, max(S, 0)), order="F")
+    check(lib().gpt_gpnt_draw_theta(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), n, _ptr(h), h.size, S,
+                                    int(seed) & (2 ** 64 - 1), _ptr(z) if z is not None else None,
+                                    _ptr(theta)))
+    return theta
+
+
+def GPrand(X, length_scale, sigma_RBF, S=1, seed=0, jitter=1e-6):
+    """GPrand (GaussianProcess.jl:66-80) of the zero-mean squared-exponential GP at ``X`` (N, D):
+    (N, S) draws R'z, R = chol(K + jitter I), from Philox stream 25 (gpt_gp_rand).
+    ``length_scale`` is a scalar or D entries."""
+    X = _f64(X)
+    if X.ndim != 2:
+        raise ValueError("X must be (N, D)")
+    N, D = X.shape
+    h = _gp_hyper(1.0, float(sigma_RBF) ** 2, length_scale)
+    h[-2] = float(sigma_RBF)
+    S = int(S)
+    F = np.empty((N, max(S, 0)), order="F")
+    check(lib().gpt_gp_rand(_ptr(X), N, D, _ptr(h), h.size, float(jitter), S,
+                            int(seed) & (2 ** 64 - 1), _ptr(F)))
+    return F
+
+
+def createmesh(interval_start, interval_end, npts):
+    """GPT_SGLD.jl:289-301: ``(x, y, grid)`` with x = y = linspace(start, end, npts) and grid
+    (npts^2, 2) whose row i*npts + j is (x[i], y[j])."""
+    x = np.linspace(interval_start, interval_end, int(npts))
+    y = np.linspace(interval_start, interval_end, int(npts))
+    grid = np.empty((int(npts) ** 2, 2), order="F")
+    grid[:, 0] = np.repeat(x, int(npts))
+    grid[:, 1] = np.tile(y, int(npts))
+    return x, y, grid
+
+
+def fhatdraw(X, n, length_scale, sigma_RBF, r, Q, seed=0):
+    """GPT_SGLD.jl:304-342: a draw ``(y, w, U, I, phi)`` from the tensor model at ``X`` (N, D):
+    phi = feature(X, length_scale, sigma_RBF, sqrt(n/Q^(1/D)), Z, b) with Z, b =
+    feature_inputs(n, D, seed), w ~ N(0, I) and U uniform on the Stiefel manifolds (init_state),
+    I = samplenz(r, D, Q, seed), y = pred(w, U, I, phi).  ``length_scale`` is a scalar or D
+    entries; any other length is the reference's error."""
+    X = _f64(X)
+    if X.ndim != 2:
+        raise ValueError("X must be (N, D)")
+    D = X.shape[1]
+    if np.ndim(length_scale) > 0 and np.size(length_scale) != D:
+        raise ValueError("dimensions of X and length_scale do not match")
+    n, r, Q = int(n), int(r), int(Q)
+    phi_scale = math.sqrt(n / Q ** (1.0 / D))
+    Z, b = feature_inputs(n, D, seed)
+    phi = _feature_D(X, length_scale, sigma_RBF, phi_scale, Z, b)
+    w, U = init_state(n, r, D, Q, seed, stiefel=True, sigma_w=1.0)
+    I = samplenz(r, D, Q, seed)
+    return pred(w, U, I, phi), w, U, I, phi
 
 
 def GP_nlogmarginal(X, y, signal_var, sigma_RBF2, length_scale):

@@ -204,6 +204,21 @@ SIGNATURES = {
                                       P_D, P_D]),
     "gpt_gp_predict": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, C.c_int64, P_D, C.c_int64,
                                  P_D, P_D, P_D, P_D]),
+    "gpt_egp_draw_prior": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_double, C.c_int64, C.c_uint64,
+                                     P_D, P_D, P_D]),
+    "gpt_egp_draw_posterior": (C.c_int, [C.c_void_p, P_D, C.c_int64, P_D, C.c_int64, C.c_double,
+                                         C.c_int32, C.c_int64, C.c_uint64, P_D, P_D, P_D, P_D,
+                                         P_D]),
+    "gpt_nlml_draw_theta": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_int64, C.c_uint64, P_D, P_D,
+                                      P_D]),
+    "gpt_gp_rand": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, C.c_int64, C.c_double, C.c_int64,
+                              C.c_uint64, P_D]),
+    "gpt_gp_post_rand": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, C.c_int64, P_D, C.c_int64,
+                                   C.c_double, C.c_int32, C.c_int64, C.c_uint64, P_D, P_D, P_D,
+                                   P_D]),
+    "gpt_gpnt_draw_theta": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, P_D, P_D, C.c_int64, P_D,
+                                      C.c_int64, C.c_int64, C.c_uint64, P_D, P_D]),
+    "gpt_gpdraw_last_timing": (C.c_int, [P_D, C.c_int32]),
     "gpt_sgld_wonly": (C.c_int, [C.POINTER(SGLDConfig), P_D, P_D, P_I32, P_D, P_D, P_D, P_D, P_D]),
     "gpt_pred_mean_x": (C.c_int, [P_D, P_D, P_I32, P_D, P_D, C.c_int64, C.c_int64, P_D, C.c_int64,
                                   C.c_double, C.c_double, P_D, P_D, C.c_int64, C.c_int64, C.c_int64,

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "device_util.h"
+#include "exactgp.h"
 #include "host_util.h"
 
 namespace gpt {
@@ -34,24 +35,6 @@ constexpr int kEgpPart = kDMax + 2; // per-workgroup partial sums of the gradien
 constexpr int kEgpChunk = 1024;     // test columns per prediction chunk when the caller passes 0
 constexpr int kEgpChunkMax = 4096;
 static_assert(64 % kNW == 0, "egp_grad_kernel splits 64 columns over the waves");
-
-struct EgpHyp {
-  double invl[kDMax];   // 1/ℓ_k
-  double sig2, s2;      // σ_RBF², σ²
-  int D;
-};
-
-// k(a, b) for rows ia of Xa (stride sa between dimensions) and ib of Xb
-__device__ __forceinline__ double egp_kern(const double* __restrict__ Xa, size_t sa, size_t ia,
-                                           const double* __restrict__ Xb, size_t sb, size_t ib,
-                                           const EgpHyp& H) {
-  double s = 0.0;
-  for (int k = 0; k < H.D; ++k) {
-    const double d = (Xa[ia + sa * k] - Xb[ib + sb * k]) * H.invl[k];
-    s = fma(d, d, s);
-  }
-  return H.sig2 * exp(-0.5 * s);
-}
 
 // 1. A (lower 64 × 64 blocks) = K + σ²I from X.  grid (nblk, nblk); blocks above the diagonal leave.
 __global__ __launch_bounds__(256) void egp_build_kernel(const double* __restrict__ X, int N,
@@ -634,6 +617,23 @@ static hipError_t egp_trsm(const double* L, int N, double* B, int ncols, bool id
   return hipGetLastError();
 }
 
+// A (N × N, lower 64 × 64 blocks, leading dimension N) := its Cholesky factor, panel by panel:
+// the diagonal block, the rows below it, the trailing update.  *status = 1 at a pivot that is not
+// positive.  The factorisation of every matrix here: K + σ²I, and the draws' K + jitter·I and Σ.
+static hipError_t egp_chol(double* A, int N, int32_t* status, hipStream_t st) {
+  for (int j0 = 0; j0 < N; j0 += kEgpNB) {
+    hipLaunchKernelGGL(egp_potf2_kernel, dim3(1), dim3(256), 0, st, A, N, j0, status);
+    const int rem = N - j0 - kEgpNB;
+    if (rem > 0) {
+      hipLaunchKernelGGL(egp_panel_kernel, dim3((rem + 255) / 256), dim3(256), 0, st, A, N, j0);
+      const long long T = (rem + 63) / 64;
+      hipLaunchKernelGGL(egp_syrk_kernel, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, st, A,
+                         N, j0);
+    }
+  }
+  return hipGetLastError();
+}
+
 static void egp_nan_fill(double* p, int64_t n) {
   if (p) for (int64_t k = 0; k < n; ++k) p[k] = std::nan("");
 }
@@ -668,17 +668,7 @@ static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t wa
   hipLaunchKernelGGL(egp_build_kernel, dim3(nblk, nblk), dim3(256), 0, st, h->X, N, H, h->A);
   GPT_HIPCHK(hipGetLastError());
   mark();
-  for (int j0 = 0; j0 < N; j0 += kEgpNB) {
-    hipLaunchKernelGGL(egp_potf2_kernel, dim3(1), dim3(256), 0, st, h->A, N, j0, h->status);
-    const int rem = N - j0 - kEgpNB;
-    if (rem > 0) {
-      hipLaunchKernelGGL(egp_panel_kernel, dim3((rem + 255) / 256), dim3(256), 0, st, h->A, N, j0);
-      const long long T = (rem + 63) / 64;
-      hipLaunchKernelGGL(egp_syrk_kernel, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, st,
-                         h->A, N, j0);
-    }
-  }
-  GPT_HIPCHK(hipGetLastError());
+  GPT_HIPCHK(egp_chol(h->A, N, h->status, st));
   mark();
   GPT_HIPCHK(hipMemcpyAsync(h->r, h->y, 8 * (size_t)N, hipMemcpyDeviceToDevice, st));
   for (int j0 = 0; j0 < N; j0 += kEgpNB) {
@@ -833,6 +823,199 @@ extern "C" int gpt_egp_predict(gpt_egp* h, const double* hyper, int64_t Lh, cons
   if (lp) GPT_HIPCHK(hipMemcpyAsync(lp, dlp, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
   GPT_HIPCHK(hipStreamSynchronize(st));
   return GPT_OK;
+}
+
+// ------------------------------------------------------------------------------ function draws
+static bool egp_draw_ok(double jitter, int64_t S, int64_t Smin) {
+  if (!(jitter >= 0.0) || !std::isfinite(jitter)) {
+    set_error("exact GP draw: jitter must be >= 0 and finite"); return false;
+  }
+  if (S < Smin || S > kGpdSMax) {
+    set_error(Smin ? "exact GP draw: S must be in 1..4096"
+                   : "exact GP draw: S must be in 0..4096, and in 1..4096 with F");
+    return false;
+  }
+  return true;
+}
+
+static bool egp_post_ok(const void* Xtest, int64_t Ntest, double jitter, int32_t observed,
+                        int64_t S, const void* fmu, const void* F, const void* cov) {
+  if (!egp_draw_ok(jitter, S, F ? 1 : 0)) return false;
+  if (Ntest < 1 || Ntest > kGpdTestMax) {
+    set_error("exact GP draw: Ntest must be in 1..8192"); return false;
+  }
+  if (observed != 0 && observed != 1) {
+    set_error("exact GP draw: observed must be 0 or 1"); return false;
+  }
+  if (!fmu && !F && !cov) { set_error("exact GP draw: no output asked for"); return false; }
+  if (!Xtest) { set_error("exact GP draw: null test input"); return false; }
+  return true;
+}
+
+// GPrand (GaussianProcess.jl:66-80) at the handle's X: F (N, S) = L·Z, L·Lᵀ = K + jitter·I.  The
+// factor goes where the handle keeps that of K + σ²I, which the call therefore invalidates.
+extern "C" int gpt_egp_draw_prior(gpt_egp* h, const double* hyper, int64_t Lh, double jitter,
+                                  int64_t S, uint64_t seed, const double* Zin, double* F,
+                                  double* Zout) {
+  if (!egp_draw_ok(jitter, S, 1)) return GPT_ERR_BAD_DIMS;
+  if (!h || !F) { set_error("exact GP draw: null handle or output"); return GPT_ERR_BAD_DIMS; }
+  if (!egp_hyper_ok(hyper, Lh, h->D)) return GPT_ERR_BAD_DIMS;
+  const int N = h->N, nblk = (N + 63) / 64;
+  EgpHyp H = egp_hyp(hyper, Lh, h->D);
+  H.s2 = jitter;                                        // GPrand adds the jitter alone
+  hipStream_t st = nullptr;
+  h->have_factor = false;
+  DevSet tmp;
+  double *dZ = nullptr, *dF = nullptr;
+  const size_t NS = (size_t)N * S;
+  GPT_HIPCHK(tmp.alloc(&dZ, NS));
+  GPT_HIPCHK(tmp.alloc(&dF, NS));
+  GpdTimer tm(st);
+  GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
+  GPT_HIPCHK(gpd_normals(dZ, N, (int)S, seed, kGpdPrior, Zin, st));
+  tm.mark(0);
+  hipLaunchKernelGGL(egp_build_kernel, dim3(nblk, nblk), dim3(256), 0, st, h->X, N, H, h->A);
+  GPT_HIPCHK(hipGetLastError());
+  tm.mark(1);
+  GPT_HIPCHK(egp_chol(h->A, N, h->status, st));
+  tm.mark(4);
+  GPT_HIPCHK(gpd_trimm(h->A, (size_t)N, N, false, dZ, (int)S, nullptr, 1.0, dF, st));
+  tm.mark(5);
+  int32_t bad = 0;
+  GPT_HIPCHK(hipMemcpyAsync(&bad, h->status, 4, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipMemcpyAsync(F, dF, 8 * NS, hipMemcpyDeviceToHost, st));
+  if (Zout) GPT_HIPCHK(hipMemcpyAsync(Zout, dZ, 8 * NS, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipStreamSynchronize(st));
+  tm.read();
+  if (bad) {
+    egp_nan_fill(F, (int64_t)NS);
+    egp_nan_fill(Zout, (int64_t)NS);
+    set_error("exact GP draw: K + jitter*I is not positive definite (PosDefException)");
+    return GPT_ERR_NOT_SPD;
+  }
+  return GPT_OK;
+}
+
+// GPpost + GPrand (GaussianProcess.jl:82-122): the joint posterior at Xtest (Ntest, D) on the
+// factor of K + σ²I, fmu by gpt_egp_predict's kernels, Σ = K** − VᵀV with V = L⁻¹Ks, and
+// F (Ntest, S) = fmu·1ᵀ + L_Σ·Z, L_Σ·L_Σᵀ = Σ + (jitter [+ σ²])·I.  cov is Σ alone.
+extern "C" int gpt_egp_draw_posterior(gpt_egp* h, const double* hyper, int64_t Lh,
+                                      const double* Xtest, int64_t Ntest, double jitter,
+                                      int32_t observed, int64_t S, uint64_t seed,
+                                      const double* Zin, double* fmu, double* F, double* cov,
+                                      double* Zout) {
+  if (!egp_post_ok(Xtest, Ntest, jitter, observed, S, fmu, F, cov)) return GPT_ERR_BAD_DIMS;
+  if (!h) { set_error("exact GP draw: null handle"); return GPT_ERR_BAD_DIMS; }
+  if (!egp_hyper_ok(hyper, Lh, h->D)) return GPT_ERR_BAD_DIMS;
+  const int N = h->N, D = h->D, Nt = (int)Ntest, Sd = F ? (int)S : 0;
+  const size_t TS = (size_t)Nt * Sd, TT = (size_t)Nt * Nt;
+  auto nan_all = [&]() {
+    egp_nan_fill(fmu, Nt);
+    egp_nan_fill(F, (int64_t)TS);
+    egp_nan_fill(cov, (int64_t)TT);
+    if (F) egp_nan_fill(Zout, (int64_t)TS);
+  };
+  if (!(h->have_factor && h->last_Lh == Lh && std::memcmp(h->last, hyper, 8 * (size_t)Lh) == 0)) {
+    double val = 0.0;
+    const int rc = egp_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
+    if (rc != GPT_OK) { nan_all(); return rc; }
+  }
+  const EgpHyp H = egp_hyp(hyper, Lh, D);
+  hipStream_t st = nullptr;
+  if (h->ks_cols < (size_t)Nt) {
+    h->Ks = nullptr;
+    h->ks_cols = 0;
+    h->ks_mem = DevMem();
+    GPT_HIPCHK(h->ks_mem.alloc<double>((size_t)N * Nt));
+    h->Ks = h->ks_mem.as<double>();
+    h->ks_cols = (size_t)Nt;
+  }
+  DevSet tmp;
+  double *dX = nullptr, *dmu = nullptr, *dSig = nullptr, *dcov = nullptr, *dZ = nullptr,
+         *dF = nullptr;
+  GPT_HIPCHK(tmp.alloc(&dX, (size_t)Nt * D));
+  GPT_HIPCHK(tmp.alloc(&dmu, (size_t)Nt));
+  if (F) {
+    GPT_HIPCHK(tmp.alloc(&dSig, TT));
+    GPT_HIPCHK(tmp.alloc(&dZ, TS));
+    GPT_HIPCHK(tmp.alloc(&dF, TS));
+  }
+  if (cov) GPT_HIPCHK(tmp.alloc(&dcov, TT));
+  GpdTimer tm(st);
+  GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
+  GPT_HIPCHK(hipMemcpyAsync(dX, Xtest, 8 * (size_t)Nt * D, hipMemcpyHostToDevice, st));
+  if (F) GPT_HIPCHK(gpd_normals(dZ, Nt, Sd, seed, kGpdPosterior, Zin, st));
+  tm.mark(0);
+  hipLaunchKernelGGL(egp_cross_kernel, dim3((N + 63) / 64, (Nt + 15) / 16), dim3(256), 0, st, h->X,
+                     N, dX, (long long)Nt, 0LL, Nt, H, h->Ks);
+  hipLaunchKernelGGL(egp_pred_kernel, dim3((Nt + 3) / 4), dim3(256), 0, st, h->Ks, N, Nt, h->alpha,
+                     0, H.sig2, H.s2, (const double*)nullptr, dmu, (double*)nullptr,
+                     (double*)nullptr);
+  GPT_HIPCHK(hipGetLastError());
+  tm.mark(1);
+  if (F || cov) {
+    GPT_HIPCHK(egp_trsm(h->A, N, h->Ks, Nt, false, st));
+    tm.mark(2);
+    GPT_HIPCHK(gpd_postcov(h->Ks, N, dX, Nt, H, jitter + (observed ? H.s2 : 0.0), dSig, dcov, st));
+    tm.mark(3);
+  }
+  if (F) {
+    GPT_HIPCHK(egp_chol(dSig, Nt, h->status + 1, st));
+    tm.mark(4);
+    GPT_HIPCHK(gpd_trimm(dSig, (size_t)Nt, Nt, false, dZ, Sd, dmu, 1.0, dF, st));
+    tm.mark(5);
+  }
+  int32_t bad[2] = {0, 0};
+  GPT_HIPCHK(hipMemcpyAsync(bad, h->status, 8, hipMemcpyDeviceToHost, st));
+  if (fmu) GPT_HIPCHK(hipMemcpyAsync(fmu, dmu, 8 * (size_t)Nt, hipMemcpyDeviceToHost, st));
+  if (cov) GPT_HIPCHK(hipMemcpyAsync(cov, dcov, 8 * TT, hipMemcpyDeviceToHost, st));
+  if (F) {
+    GPT_HIPCHK(hipMemcpyAsync(F, dF, 8 * TS, hipMemcpyDeviceToHost, st));
+    if (Zout) GPT_HIPCHK(hipMemcpyAsync(Zout, dZ, 8 * TS, hipMemcpyDeviceToHost, st));
+  }
+  GPT_HIPCHK(hipStreamSynchronize(st));
+  tm.read();
+  if (bad[1]) {
+    nan_all();
+    set_error(observed ? "exact GP draw: the posterior covariance + (jitter + signal_var)*I is "
+                         "not positive definite (PosDefException)"
+                       : "exact GP draw: the posterior covariance + jitter*I is not positive "
+                         "definite (PosDefException)");
+    return GPT_ERR_NOT_SPD;
+  }
+  return GPT_OK;
+}
+
+// One-shot GPrand: create (with targets of zero, which no draw reads), draw, destroy.
+extern "C" int gpt_gp_rand(const double* X, int64_t N, int64_t D, const double* hyper, int64_t Lh,
+                           double jitter, int64_t S, uint64_t seed, double* F) {
+  if (!egp_dims_ok(X, N, D, X) || !egp_hyper_ok(hyper, Lh, D) || !egp_draw_ok(jitter, S, 1))
+    return GPT_ERR_BAD_DIMS;
+  if (!F) { set_error("exact GP draw: null output"); return GPT_ERR_BAD_DIMS; }
+  const std::vector<double> y((size_t)N, 0.0);
+  gpt_egp* h = nullptr;
+  int rc = gpt_egp_create(X, N, D, y.data(), &h);
+  if (rc != GPT_OK) return rc;
+  rc = gpt_egp_draw_prior(h, hyper, Lh, jitter, S, seed, nullptr, F, nullptr);
+  gpt_egp_destroy(h);
+  return rc;
+}
+
+// One-shot GPpost + GPrand: create, gpt_egp_draw_posterior, destroy.
+extern "C" int gpt_gp_post_rand(const double* X, int64_t N, int64_t D, const double* y,
+                                const double* hyper, int64_t Lh, const double* Xtest,
+                                int64_t Ntest, double jitter, int32_t observed, int64_t S,
+                                uint64_t seed, const double* Zin, double* fmu, double* F,
+                                double* cov) {
+  if (!egp_dims_ok(X, N, D, y) || !egp_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
+  if (!egp_post_ok(Xtest, Ntest, jitter, observed, S, fmu, F, cov)) return GPT_ERR_BAD_DIMS;
+  gpt_egp* h = nullptr;
+  int rc = gpt_egp_create(X, N, D, y, &h);
+  if (rc != GPT_OK) return rc;
+  rc = gpt_egp_draw_posterior(h, hyper, Lh, Xtest, Ntest, jitter, observed, S, seed, Zin, fmu, F,
+                              cov, nullptr);
+  gpt_egp_destroy(h);
+  return rc;
 }
 
 extern "C" int gpt_gp_nlogmarginal(const double* X, int64_t N, int64_t D, const double* y,

@@ -18,7 +18,11 @@ enum Stream : uint32_t {
   kTgpUInit = 11, kTgpI = 12, kTgpWNoise = 13, kTgpUNoise = 14,
   kGmcP = 15, kGmcMom = 16, kGmcU = 17,
   kCfUVInit = 18, kCfWNoise = 19, kCfUVNoise = 20,
-  kCfgInit = 21, kCfgU = 22, kCfgV = 23, kCfgW = 24
+  kCfgInit = 21, kCfgU = 22, kCfgV = 23, kCfgW = 24,
+  // gpdraw.hip: element (i, s) of a call's normals Z (M × S) is normal_at(seed, e = i, c1 = s,
+  // c2 = kGpDraw, c3 = kind), kind 0 = GP prior, 1 = GP posterior, 2 = RFF θ; on the host
+  // oracle.philox.normals(M, seed, s, 25, kind)[i].  Column s does not depend on S.
+  kGpDraw = 25
 };
 
 struct U4 { uint32_t x, y, z, w; };

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device_util.h"
+#include "exactgp.h"
 #include "host_util.h"
 #include "mfma_tile.h"
 
@@ -832,6 +833,67 @@ extern "C" int gpt_nlml_predict(gpt_nlml* h, const double* hyper, int64_t Lh, co
   if (lp) GPT_HIPCHK(hipMemcpyAsync(lp, dlp, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
   GPT_HIPCHK(hipStreamSynchronize(st));
   return GPT_OK;
+}
+
+// Exact draws from θ | y ~ N(l, σ²A⁻¹) (GPNT_nlogmarginal's model, GPT_SGLD.jl:921-933):
+// theta (n, S) = l·1ᵀ + σ·L⁻ᵀ·Z on the factor and the Xt = L⁻ᵀ that gpt_nlml_predict keeps.
+extern "C" int gpt_nlml_draw_theta(gpt_nlml* h, const double* hyper, int64_t Lh, int64_t S,
+                                   uint64_t seed, const double* Zin, double* theta, double* Zout) {
+  if (S < 1 || S > kGpdSMax) { set_error("nlml draw: S must be in 1..4096"); return GPT_ERR_BAD_DIMS; }
+  if (!h || !theta) { set_error("nlml draw: null handle or output"); return GPT_ERR_BAD_DIMS; }
+  if (!nlml_hyper_ok(hyper, Lh, h->D)) return GPT_ERR_BAD_DIMS;
+  const int n = h->n;
+  const size_t nS = (size_t)n * S;
+  if (!(h->have_factor && h->last_Lh == Lh && std::memcmp(h->last, hyper, 8 * (size_t)Lh) == 0)) {
+    double val = 0.0;
+    const int rc = nlml_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
+    if (rc != GPT_OK) {
+      const double q = std::nan("");
+      for (size_t x = 0; x < nS; ++x) {
+        theta[x] = q;
+        if (Zout) Zout[x] = q;
+      }
+      return rc;
+    }
+  }
+  hipStream_t st = nullptr;
+  DevSet tmp;
+  double *dZ = nullptr, *dT = nullptr;
+  GPT_HIPCHK(tmp.alloc(&dZ, nS));
+  GPT_HIPCHK(tmp.alloc(&dT, nS));
+  GpdTimer tm(st);
+  GPT_HIPCHK(gpd_normals(dZ, n, (int)S, seed, kGpdTheta, Zin, st));
+  tm.mark(0);
+  if (!h->have_xt) {
+    GPT_HIPCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
+    GPT_HIPCHK(launch_big_lds<nlml_trinv_kernel>(kMaxLds, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
+                                                 trinv_lds_bytes(n), st, h->A, n, h->Xt));
+    h->have_xt = true;
+  }
+  tm.mark(2);
+  GPT_HIPCHK(gpd_trimm(h->Xt, (size_t)n, n, true, dZ, (int)S, h->l, std::sqrt(hyper[Lh - 1]), dT, st));
+  tm.mark(5);
+  GPT_HIPCHK(hipMemcpyAsync(theta, dT, 8 * nS, hipMemcpyDeviceToHost, st));
+  if (Zout) GPT_HIPCHK(hipMemcpyAsync(Zout, dZ, 8 * nS, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(hipStreamSynchronize(st));
+  tm.read();
+  return GPT_OK;
+}
+
+// One-shot form: create, gpt_nlml_draw_theta, destroy.
+extern "C" int gpt_gpnt_draw_theta(const double* X, int64_t N, int64_t D, const double* y,
+                                   const double* Z, const double* b, int64_t n,
+                                   const double* hyper, int64_t Lh, int64_t S, uint64_t seed,
+                                   const double* Zin, double* theta) {
+  if (!nlml_dims_ok(X, N, D, y, Z, b, n) || !nlml_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
+  if (S < 1 || S > kGpdSMax) { set_error("nlml draw: S must be in 1..4096"); return GPT_ERR_BAD_DIMS; }
+  if (!theta) { set_error("nlml draw: null output"); return GPT_ERR_BAD_DIMS; }
+  gpt_nlml* h = nullptr;
+  int rc = gpt_nlml_create(X, N, D, y, Z, b, n, &h);
+  if (rc != GPT_OK) return rc;
+  rc = gpt_nlml_draw_theta(h, hyper, Lh, S, seed, Zin, theta, nullptr);
+  gpt_nlml_destroy(h);
+  return rc;
 }
 
 extern "C" int gpt_gpnt_predict(const double* X, int64_t N, int64_t D, const double* y,

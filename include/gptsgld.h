@@ -720,6 +720,56 @@ int gpt_gp_predict(const double* X, int64_t N, int64_t D, const double* y, const
                    int64_t Lh, const double* Xtest, int64_t Ntest, const double* ytest,
                    double* fmu, double* fs2, double* lp);
 
+/* ---- function draws: GP prior and posterior, RFF posterior weights --------------------- */
+/* Common to the draw entries below.  S draws come from M x S standard normals Z (column-major; M =
+ * N, Ntest or n): Zin (M*S, optional) when given, for common random numbers, else element (i, s) =
+ * the Philox normal (seed, e = i, c1 = s, c2 = 25, c3 = kind), kind 0 prior, 1 posterior, 2 theta,
+ * so that column s does not depend on S.  Zout (M*S, optional) receives the normals used.  A draw
+ * is its mean plus c*T*z for a triangular factor T, summed in an order fixed by M alone: column s
+ * of the result depends on column s of Z only, not on S or the other columns, and equal calls give
+ * equal bits.  S is in 1..4096, jitter >= 0 and finite; otherwise, and for a NULL required array,
+ * GPT_ERR_BAD_DIMS before any device call.  A factorisation that meets a pivot that is not
+ * positive returns GPT_ERR_NOT_SPD with every output NaN-filled and a message naming the matrix;
+ * the handle stays usable.  Calls on one handle interleave in any order with eval / predict. */
+/* GPrand (GaussianProcess.jl:66-80) at the handle's X: F (N, S) = R'z with R = chol(K +
+ * jitter*I).  hyper = [length_scale; sigma_RBF; signal_var] as everywhere; signal_var is validated
+ * and unused, GPrand adds the jitter alone.  The call invalidates the handle's factor (the next
+ * predict refits). */
+int gpt_egp_draw_prior(gpt_egp* h, const double* hyper, int64_t Lh, double jitter, int64_t S,
+                       uint64_t seed, const double* Zin, double* F, double* Zout);
+/* GPpost followed by GPrand (GaussianProcess.jl:82-122): the posterior GP at Xtest (Ntest, D),
+ * Ntest in 1..8192, on the factor of the last evaluation at hyper (as gpt_egp_predict; it fits
+ * otherwise).  fmu (Ntest, optional) is gpt_egp_predict's, bit for bit; cov (Ntest*Ntest,
+ * optional) the joint covariance k(x,x') - k(x)'(K + signal_var*I)^-1 k(x'), full symmetric,
+ * neither jitter nor signal_var included; F (Ntest, S, optional) = fmu + L*z with L*L' = cov +
+ * d*I, d = jitter (observed = 0: function values) or jitter + signal_var (observed = 1:
+ * observations).  With F NULL, S = 0 is allowed and Zin / Zout are ignored. */
+int gpt_egp_draw_posterior(gpt_egp* h, const double* hyper, int64_t Lh, const double* Xtest,
+                           int64_t Ntest, double jitter, int32_t observed, int64_t S,
+                           uint64_t seed, const double* Zin, double* fmu, double* F, double* cov,
+                           double* Zout);
+/* Exact draws from the posterior of GPNT_nlogmarginal's model (GPT_SGLD.jl:921-933), theta | y ~
+ * N(l, signal_var*A^-1): theta (n, S) = l + sqrt(signal_var)*L^-T z, in the layout of a GPNT_SGLD
+ * store.  The factor is reused or built as in gpt_nlml_predict. */
+int gpt_nlml_draw_theta(gpt_nlml* h, const double* hyper, int64_t Lh, int64_t S, uint64_t seed,
+                        const double* Zin, double* theta, double* Zout);
+/* One-shot GPrand (GaussianProcess.jl:66-80; MakeSynthData.jl:31-60 draws its regression set with
+ * it): create, gpt_egp_draw_prior, destroy.  F (N, S). */
+int gpt_gp_rand(const double* X, int64_t N, int64_t D, const double* hyper, int64_t Lh,
+                double jitter, int64_t S, uint64_t seed, double* F);
+/* One-shot host-pointer forms of the two above (create, one call, destroy), as gpt_gp_predict and
+ * gpt_gpnt_predict are of the predictions: the same bits as the handle forms. */
+int gpt_gp_post_rand(const double* X, int64_t N, int64_t D, const double* y, const double* hyper,
+                     int64_t Lh, const double* Xtest, int64_t Ntest, double jitter,
+                     int32_t observed, int64_t S, uint64_t seed, const double* Zin, double* fmu,
+                     double* F, double* cov);
+int gpt_gpnt_draw_theta(const double* X, int64_t N, int64_t D, const double* y, const double* Z,
+                        const double* b, int64_t n, const double* hyper, int64_t Lh, int64_t S,
+                        uint64_t seed, const double* Zin, double* theta);
+/* Diagnostics (scripts/time_gpdraw.py): device-event times in ms of this thread's last draw call:
+ * normals, kernel assembly, solves, covariance, Cholesky, triangular product. */
+int gpt_gpdraw_last_timing(double* ms, int32_t len);
+
 /* ---- tensor-GP Gibbs sampler (§8 a25) ----------------------------------------------- */
 /* GPT_inf(b,y,sigma,n,r,q,num_iterations,burnin) TGP.jl:37-86 on whitened data.
  * b (n, D, N) column-major feature array (TGP.feature, TGP.jl:6-14), y (N).

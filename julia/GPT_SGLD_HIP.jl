@@ -15,7 +15,8 @@ export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTreg
        init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal, GP_nlogmarginal, GP_gradnlogmarginal, GP_predict, GPNT_predict, RFF_kernel_error,
        GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class,
        neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores,
-       predictive, pred_predictive, pred_predictive_x, GPNT_predictive, GPNT_predictive_x
+       predictive, pred_predictive, pred_predictive_x, GPNT_predictive, GPNT_predictive_x,
+       GPrand, GPpost_rand, GPNT_draw_theta, fhatdraw, createmesh
 
 const LIB = get(ENV, "GPTSGLD_LIB", joinpath(@__DIR__, "..", "gpt_amd", "libgptsgld.so"))
 
@@ -811,6 +812,92 @@ function GP_predict(X::Array{Float64,2}, y::Array{Float64}, hyperparams::Vector{
     end
     lp = ytest === nothing ? nothing : lpv
     return fmu, fs2 .+ hyperparams[end], fmu, fs2, lp
+end
+
+# Function draws (GaussianProcess.jl:66-122).  GPrand: S draws R'z, R = chol(K + jitter*I), of the
+# zero-mean squared-exponential GP at X (N, D), from Philox stream 25; length_scale is a scalar or D
+# entries.  Returns (N, S).
+function GPrand(X::Array{Float64,2}, length_scale, sigma_RBF::Real; S::Integer=1, seed::Integer=0,
+                jitter::Real=1e-6)
+    N, D = size(X)
+    hyperparams = Float64[length_scale...; sigma_RBF; 1.0]
+    F = Array{Float64}(undef, N, S)
+    check(ccall((:gpt_gp_rand, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Float64, Int64, UInt64,
+                 Ptr{Float64}),
+                X, N, D, hyperparams, length(hyperparams), jitter, S, UInt64(seed), F))
+    return F
+end
+
+# GPpost followed by GPrand: (fmu, samples (Ntest, S), cov (Ntest, Ntest)) of the posterior GP at
+# Xtest; samples = fmu + L z, L L' = cov + jitter*I (observed: + signal_var*I); z (Ntest, S)
+# replaces the Philox normals
+function GPpost_rand(X::Array{Float64,2}, y::Array{Float64}, hyperparams::Vector{Float64},
+                     Xtest::Array{Float64,2}; S::Integer=1, seed::Integer=0, jitter::Real=1e-6,
+                     observed::Bool=false, z=nothing)
+    N, D = size(X); Ntest = size(Xtest, 1)
+    size(Xtest, 2) == D || error("Xtest must be (Ntest, D)")
+    length(y) == N || error("y must have N entries")
+    fmu = Array{Float64}(undef, Ntest); F = Array{Float64}(undef, Ntest, S)
+    cov = Array{Float64}(undef, Ntest, Ntest)
+    zin = z === nothing ? Float64[] : Array{Float64}(z)
+    z === nothing || size(zin) == (Ntest, S) || error("z must be (Ntest, S)")
+    GC.@preserve zin begin
+        zp = z === nothing ? Ptr{Float64}(C_NULL) : pointer(zin)
+        check(ccall((:gpt_gp_post_rand, LIB), Cint,
+                    (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64},
+                     Int64, Float64, Int32, Int64, UInt64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}),
+                    X, N, D, vec(y), hyperparams, length(hyperparams), Xtest, Ntest, jitter,
+                    Int32(observed), S, UInt64(seed), zp, fmu, F, cov))
+    end
+    return fmu, F, cov
+end
+
+# S exact draws (n, S) from the posterior theta | y ~ N(l, signal_var*A^-1) of GPNT_nlogmarginal's
+# model: a GPNT_SGLD store for GPNT_pred / GPNT_predictive
+function GPNT_draw_theta(X::Array{Float64,2}, y::Array{Float64}, Z::Array{Float64,2},
+                         b::Array{Float64}, hyperparams::Vector{Float64}, S::Integer;
+                         seed::Integer=0, z=nothing)
+    N, D = size(X); n = size(Z, 1)
+    size(Z, 2) == D || error("Z must be (n, D)")
+    length(b) == n || error("b must have n entries")
+    length(y) == N || error("y must have N entries")
+    theta = Array{Float64}(undef, n, S)
+    zin = z === nothing ? Float64[] : Array{Float64}(z)
+    z === nothing || size(zin) == (n, S) || error("z must be (n, S)")
+    GC.@preserve zin begin
+        zp = z === nothing ? Ptr{Float64}(C_NULL) : pointer(zin)
+        check(ccall((:gpt_gpnt_draw_theta, LIB), Cint,
+                    (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Int64, Int64, UInt64, Ptr{Float64}, Ptr{Float64}),
+                    X, N, D, vec(y), Z, vec(b), n, hyperparams, length(hyperparams), S,
+                    UInt64(seed), zp, theta))
+    end
+    return theta
+end
+
+# createmesh(interval_start,interval_end,npts)  GPT_SGLD.jl:289-301
+function createmesh(interval_start, interval_end, npts)
+    x = collect(range(interval_start, stop=interval_end, length=npts))
+    y = collect(range(interval_start, stop=interval_end, length=npts))
+    grid = Array{Float64}(undef, npts^2, 2); k = 1
+    for i = 1:npts, j = 1:npts
+        grid[k, 1] = x[i]; grid[k, 2] = y[j]; k += 1
+    end
+    return x, y, grid
+end
+
+# fhatdraw(X,n,length_scale,sigma_RBF,r,Q)  GPT_SGLD.jl:304-342, seeded: (y, w, U, I, phi)
+function fhatdraw(X::Array{Float64,2}, n::Integer, length_scale, sigma_RBF::Real, r::Integer,
+                  Q::Integer; seed::Integer=0)
+    N, D = size(X)
+    (length_scale isa Real || length(length_scale) == D) ||
+        error("dimensions of X and length_scale do not match")
+    phi = feature(X, n, length_scale, sigma_RBF, seed, sqrt(n / Q^(1 / D)))
+    w, U = init_state(n, r, D, Q, seed; stiefel=true, sigma_w=1.0)
+    I = samplenz(r, D, Q, seed)
+    return pred(w, U, I, phi), w, U, I, phi
 end
 
 # The joint likelihood of the full-theta softmax classifier (neglogjointlkhd /
