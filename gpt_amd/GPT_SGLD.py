@@ -35,6 +35,7 @@ Same function names, argument meaning, return values and error behaviour as the 
                                                               GPkit InfExact / prediction
     SoftmaxJoint(X, y, Z, b, C): neglogjointlkhd, gradneglogjointlkhd, langevin, scores, evaluate
                                                               ImageExperiment.jl:135-204
+        hmc, mala, leapfrog (HMCResult)                       BloodTransfusionExperiment.jl:255-278
     GPNT_hyperparameters_ng(init_theta, init_hyperparams, neglogjointlkhd, gradneglogjointlkhd,
                             Z, b; epsilon, num_sgld_iter, num_cg_iter)   GPT_SGLD.jl:1005
     datawhitening(X), proj, geod are not on the device path (host prep / inside the kernel).
@@ -1608,6 +1609,18 @@ def GPNT_hyperparameters_optim(nlogmarginal, gradnlogmarginal, init_hyperparams,
 
 
 # ------------------------------------------------------------------ softmax classifier: hyper-parameters
+class HMCResult:
+    """Result of ``SoftmaxJoint.hmc`` / ``mala``: ``theta_store`` (n, C, nsamples // thin), the
+    layout GPNT_pred_class takes; per transition, burn-in included, ``accept`` (int32, 0 / 1),
+    ``dH`` = H0 - H1 and ``value`` = U of the kept state; ``accept_rate`` their mean acceptance
+    and ``ndivergent`` the transitions rejected because H1 was not finite."""
+    __slots__ = ("theta_store", "accept", "dH", "value", "accept_rate", "ndivergent")
+
+    def __repr__(self):
+        return "HMCResult(T=%d, transitions=%d, accept_rate=%.3f, ndivergent=%d)" % (
+            self.theta_store.shape[2], self.accept.size, self.accept_rate, self.ndivergent)
+
+
 class SoftmaxJoint:
     """Device-resident joint likelihood -log p(y, theta; h) of the full-theta softmax classifier
     and its gradient (neglogjointlkhd / gradneglogjointlkhd, ImageExperiment.jl:135-204, with
@@ -1709,6 +1722,48 @@ class SoftmaxJoint:
         check(lib().gpt_cjoint_langevin(self._h, _ptr(h), h.size, float(eps), int(nsteps),
                                         int(seed), -1 if t0 is None else int(t0)))
 
+    def hmc(self, h, eps, L, nsamples, seed, burnin=0, thin=1, t0=None):
+        """``burnin + nsamples`` Hamiltonian Monte Carlo transitions on the resident theta at
+        ``h`` with no host round trip: ``L`` leapfrog steps of size sqrt(``eps``) (``eps`` is the
+        reference's squared step) and a Metropolis test on H = U + |p|^2/2, U the joint
+        likelihood with its |theta|^2/2 prior.  The momentum of 0-based transition t and class c
+        is normals(n, seed, t, 26, c) and the uniform of its test uniform(seed, t, 27, 0); the
+        counter is the one ``langevin`` uses (``t0`` sets it first, None continues).  Returns an
+        HMCResult.  A transition whose end Hamiltonian is not finite is rejected and counted in
+        ``ndivergent``; a non-finite starting theta raises GPTError (GPT_ERR_NAN_THETA)."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        burnin, nsamples, thin = int(burnin), int(nsamples), int(thin)
+        ntrans = max(burnin, 0) + max(nsamples, 0)
+        ncols = max(nsamples, 0) // thin if thin >= 1 else 0
+        res = HMCResult()
+        res.theta_store = np.empty((self.n, self.C, ncols), order="F")
+        res.accept = np.empty(ntrans, dtype=np.int32)
+        res.dH, res.value = np.empty(ntrans), np.empty(ntrans)
+        ndiv = _lib.C.c_int64()
+        check(lib().gpt_chmc_run(self._h, _ptr(h), h.size, float(eps), int(L), burnin, nsamples,
+                                   thin, int(seed), -1 if t0 is None else int(t0),
+                                   _ptr(res.theta_store), _ptr(res.accept, P_I32), _ptr(res.dH),
+                                   _ptr(res.value), _lib.C.byref(ndiv)))
+        res.ndivergent = ndiv.value
+        res.accept_rate = float(res.accept.mean()) if ntrans else float("nan")
+        return res
+
+    def mala(self, h, eps, nsamples, seed, burnin=0, thin=1, t0=None):
+        """``hmc`` with one leapfrog step: the full-batch MALA loop of
+        BloodTransfusionExperiment.jl:255-278."""
+        return self.hmc(h, eps, 1, nsamples, seed, burnin=burnin, thin=thin, t0=t0)
+
+    def leapfrog(self, h, eps, L, p):
+        """The integrator alone: ``L`` leapfrog steps of size sqrt(``eps``) from the resident theta
+        (left unchanged) on the momentum ``p`` (n, C).  Returns ``(q, p_new, H0, H1)``."""
+        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        pn = np.array(self._theta_arg(p), dtype=np.float64, order="F", copy=True)
+        q = np.empty((self.n, self.C), order="F")
+        H = np.empty(2)
+        check(lib().gpt_chmc_leapfrog(self._h, _ptr(h), h.size, float(eps), int(L), _ptr(pn),
+                                        _ptr(q), _ptr(H)))
+        return q, pn, float(H[0]), float(H[1])
+
     def _xtest(self, Xtest):
         Xtest = _f64(Xtest)
         if Xtest.ndim != 2 or Xtest.shape[1] != self.D:
@@ -1766,6 +1821,36 @@ def gpnt_neglogjoint_oneshot(X, y, Z, b, theta, hyperparams, C=None, want_grad=T
     return (val.value, grad) if want_grad else val.value
 
 
+def gpnt_joint_hmc_oneshot(X, y, Z, b, theta, hyperparams, eps, L, nsamples, seed, burnin=0, thin=1,
+                           t0=0, C=None):
+    """The one-shot host-pointer entry the Julia shim binds (gpt_gpnt_joint_hmc): create, run,
+    destroy.  Returns ``(theta (n, C) after the run, HMCResult)``."""
+    X = _f64(X)
+    N, D = X.shape
+    Z = _f64(Z)
+    n = Z.shape[0]
+    y = _f64(np.asarray(y, dtype=np.float64).ravel())
+    b = _f64(np.asarray(b, dtype=np.float64).ravel())
+    if C is None:
+        C = int(y.max() - y.min() + 1)
+    th = np.array(np.asarray(theta, dtype=np.float64).reshape((n, C), order="F"), order="F", copy=True)
+    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    burnin, nsamples, thin = int(burnin), int(nsamples), int(thin)
+    ntrans = max(burnin, 0) + max(nsamples, 0)
+    res = HMCResult()
+    res.theta_store = np.empty((n, C, max(nsamples, 0) // thin if thin >= 1 else 0), order="F")
+    res.accept = np.empty(ntrans, dtype=np.int32)
+    res.dH, res.value = np.empty(ntrans), np.empty(ntrans)
+    ndiv = _lib.C.c_int32()
+    check(lib().gpt_gpnt_joint_hmc(_ptr(X), N, D, _ptr(y), C, _ptr(Z), _ptr(b), n, _ptr(th), _ptr(h),
+                                   h.size, float(eps), int(L), burnin, nsamples, thin, int(seed),
+                                   int(t0), _ptr(res.theta_store), _ptr(res.accept, P_I32),
+                                   _ptr(res.dH), _ptr(res.value), _lib.C.byref(ndiv)))
+    res.ndivergent = ndiv.value
+    res.accept_rate = float(res.accept.mean()) if ntrans else float("nan")
+    return th, res
+
+
 def _joint(fn, what):
     obj = getattr(fn, "__self__", None)
     if not isinstance(obj, SoftmaxJoint) or getattr(fn, "__name__", "") != what:
@@ -1776,7 +1861,7 @@ def _joint(fn, what):
 
 def GPNT_hyperparameters_ng(init_theta, init_hyperparams, neglogjointlkhd, gradneglogjointlkhd, Z=None,
                             b=None, epsilon=1e-2, num_sgld_iter=10, num_cg_iter=10, seed=0, tol=1e-7,
-                            max_iter=200, trace=False):
+                            max_iter=200, trace=False, e_step="langevin", num_leapfrog=8):
     """GPT_SGLD.jl:1005-1063: stochastic EM on the non-Gaussian joint likelihood.  The two
     function arguments are the ``neglogjointlkhd`` and ``gradneglogjointlkhd`` methods of one
     SoftmaxJoint (which holds X, y, Z and b; ``Z`` and ``b`` are accepted for the reference's
@@ -1787,6 +1872,11 @@ def GPNT_hyperparameters_ng(init_theta, init_hyperparams, neglogjointlkhd, gradn
     ``norm(exp(old) - exp(new)) <= tol`` (:1052, 1e-7 there) or after ``max_iter`` rounds: the
     reference's loop has no cap, and a stochastic theta can keep it running for ever.
 
+    ``e_step="hmc"`` replaces the round's Langevin steps by a Metropolis-corrected E step, as the
+    reference's experiments run it (``mcmc(..., 10, burnin=9)``, ImageExperiment.jl:278-283):
+    ``num_sgld_iter`` HMC transitions of ``num_leapfrog`` leapfrog steps at squared step
+    ``epsilon`` (``SoftmaxJoint.hmc``), of which the last state is kept.
+
     Returns ``exp(loghyper)``; with ``trace=True`` also a list with, per round, the reference's
     printed ``(function_value_before, function_value_after, hyperparams)``.  theta stays resident
     (``SoftmaxJoint.theta()``).  Optim.jl's ``:cg`` is replaced by
@@ -1794,6 +1884,8 @@ def GPNT_hyperparameters_ng(init_theta, init_hyperparams, neglogjointlkhd, gradn
     objective and its gradient are parity-tested."""
     from scipy.optimize import minimize
 
+    if e_step not in ("langevin", "hmc"):
+        raise ValueError('e_step must be "langevin" or "hmc"')
     joint = _joint(neglogjointlkhd, "neglogjointlkhd")
     if _joint(gradneglogjointlkhd, "gradneglogjointlkhd") is not joint:
         raise TypeError("neglogjointlkhd and gradneglogjointlkhd must belong to one SoftmaxJoint")
@@ -1809,7 +1901,11 @@ def GPNT_hyperparameters_ng(init_theta, init_hyperparams, neglogjointlkhd, gradn
     t = 0
     for _ in range(int(max_iter)):
         if num_sgld_iter > 0:
-            joint.langevin(np.exp(lh), epsilon, num_sgld_iter, seed, t0=t)
+            if e_step == "hmc":
+                joint.hmc(np.exp(lh), epsilon, num_leapfrog, 1, seed, burnin=int(num_sgld_iter) - 1,
+                          t0=t)
+            else:
+                joint.langevin(np.exp(lh), epsilon, num_sgld_iter, seed, t0=t)
             t += int(num_sgld_iter)
         res = minimize(fun, lh, jac=True, method="CG", options={"maxiter": int(num_cg_iter)})
         new = np.asarray(res.x, dtype=np.float64)

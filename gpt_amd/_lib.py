@@ -180,6 +180,15 @@ SIGNATURES = {
     "gpt_cjoint_langevin": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_double, C.c_int64,
                                       C.c_uint64, C.c_int64]),
     "gpt_cjoint_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "gpt_chmc_run": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_double, C.c_int64, C.c_int64,
+                                 C.c_int64, C.c_int64, C.c_uint64, C.c_int64, P_D, P_I32, P_D, P_D,
+                                 C.POINTER(C.c_int64)]),
+    "gpt_chmc_leapfrog": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_double, C.c_int64, P_D, P_D,
+                                      P_D]),
+    "gpt_gpnt_joint_hmc": (C.c_int, [P_D, C.c_int64, C.c_int64, P_D, C.c_int64, P_D, P_D, C.c_int64,
+                                     P_D, P_D, C.c_int64, C.c_double, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int64, C.c_uint64, C.c_int64, P_D, P_I32, P_D,
+                                     P_D, P_I32]),
     "gpt_cjoint_scores": (C.c_int, [C.c_void_p, P_D, C.c_int64, P_D, C.c_int64, P_D]),
     "gpt_cjoint_scores_dev": (C.c_int, [C.c_void_p, P_D, C.c_int64, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_void_p]),

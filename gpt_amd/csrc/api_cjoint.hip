@@ -1,6 +1,6 @@
 // The joint likelihood of the full-theta softmax classifier from host arrays: the resident
-// evaluator gpt_cjoint (value, gradient, Langevin steps on theta, scores of test rows) and the
-// one-shot entries.  The kernels are in cjoint.hip.
+// evaluator gpt_cjoint (value, gradient, Langevin steps and HMC transitions on theta, scores of
+// test rows) and the one-shot entries.  The kernels are in cjoint.hip and chmc.hip.
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -17,7 +17,12 @@ struct gpt_cjoint {
   double *X = nullptr, *Z = nullptr, *b = nullptr, *ls = nullptr, *theta = nullptr,
          *part_theta = nullptr, *part_tx = nullptr, *part_sc = nullptr, *out = nullptr;
   int32_t *y0 = nullptr, *status = nullptr;
-  int64_t step = 0;                   // 0-based counter of the next Langevin step
+  int64_t step = 0;                   // 0-based counter of the next Langevin step / HMC transition
+  // HMC (chmc.hip), allocated by the first call that needs it.  cache_ok: sc[0] and g_cur hold U
+  // and grad U of the resident theta at cache_hyper (compared by bits).
+  HmcDev hmc = {};
+  bool hmc_alloc = false, cache_ok = false;
+  std::vector<double> cache_hyper;
   DevSet mem;
 };
 
@@ -87,6 +92,7 @@ extern "C" int gpt_cjoint_destroy(gpt_cjoint* h) {
 
 extern "C" int gpt_cjoint_set_theta(gpt_cjoint* h, const double* theta) {
   if (!h || !theta) { set_error("cjoint: null handle or theta"); return GPT_ERR_BAD_DIMS; }
+  h->cache_ok = false;
   GPT_HIPCHK(hipMemcpy(h->theta, theta, 8 * (size_t)h->n * h->C, hipMemcpyHostToDevice));
   return GPT_OK;
 }
@@ -178,6 +184,7 @@ extern "C" int gpt_cjoint_langevin(gpt_cjoint* h, const double* hyper, int64_t L
   if (rc != GPT_OK) return rc;
   GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
   A.status = h->status;
+  h->cache_ok = false;
   for (int64_t t = first; t < first + nsteps; ++t) {
     GPT_HIPCHK(launch_cjoint_eval(A, h->L, kCjTheta, st));
     GPT_HIPCHK(launch_cjoint_update(A, h->L, h->theta, eps, seed, (uint32_t)t, h->status, st));
@@ -186,6 +193,155 @@ extern "C" int gpt_cjoint_langevin(gpt_cjoint* h, const double* hyper, int64_t L
   GPT_HIPCHK(hipMemcpy(&bad, h->status, 4, hipMemcpyDeviceToHost));
   h->step = first + nsteps;
   if (bad) { set_error("Get NaN in theta. Try smaller epsilon"); return GPT_ERR_NAN_THETA; }
+  return GPT_OK;
+}
+
+// ---- Hamiltonian Monte Carlo on the resident theta (chmc.hip) -----------------------------------
+static int cj_hmc_buffers(gpt_cjoint* h) {
+  if (h->hmc_alloc) return GPT_OK;
+  DevSet& M = h->mem;
+  HmcDev& S = h->hmc;
+  const size_t nC = (size_t)h->n * h->C, nb = (size_t)hmc_blocks(h->n, h->C);
+  GPT_HIPCHK(M.alloc(&S.q, nC));
+  GPT_HIPCHK(M.alloc(&S.p, nC));
+  GPT_HIPCHK(M.alloc(&S.g_cur, nC));
+  GPT_HIPCHK(M.alloc(&S.g_new, nC));
+  GPT_HIPCHK(M.alloc(&S.kin0, nb));
+  GPT_HIPCHK(M.alloc(&S.kin1, nb));
+  GPT_HIPCHK(M.alloc(&S.prior, nb));
+  GPT_HIPCHK(M.alloc(&S.sc, 4));
+  GPT_HIPCHK(M.alloc(&S.flag, 4));
+  GPT_HIPCHK(M.alloc(&S.ndiv, 2));
+  S.theta = h->theta;
+  S.status = h->status;
+  S.n = h->n;
+  S.C = h->C;
+  h->hmc_alloc = true;
+  return GPT_OK;
+}
+
+static bool cj_hmc_step_ok(double eps, int64_t L) {
+  if (!(eps > 0.0) || !std::isfinite(eps)) { set_error("cjoint: eps must be positive and finite"); return false; }
+  if (L < 1 || L > 1024) { set_error("cjoint: the number of leapfrog steps must be in 1..1024"); return false; }
+  return true;
+}
+
+// The kernel arguments at hyper, the status word cleared, and the cache of the resident theta:
+// when it does not stand for this theta at these hyper bits, one evaluation at theta forms U and
+// grad U, and a non-finite U (a non-finite theta makes it so) is GPT_ERR_NAN_THETA.
+static int cj_hmc_prepare(gpt_cjoint* h, const double* hyper, int64_t Lh, hipStream_t st, CjArgs* A) {
+  int rc = cj_hmc_buffers(h);
+  if (rc != GPT_OK) return rc;
+  double sigma = 0.0;
+  rc = cj_args(h, hyper, Lh, st, A, &sigma);
+  if (rc != GPT_OK) return rc;
+  GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
+  A->status = h->status;
+  const bool same = h->cache_ok && h->cache_hyper.size() == (size_t)Lh &&
+                    std::memcmp(h->cache_hyper.data(), hyper, 8 * (size_t)Lh) == 0;
+  if (same) return GPT_OK;
+  h->cache_ok = false;
+  const HmcDev& S = h->hmc;
+  GPT_HIPCHK(launch_cjoint_eval(*A, h->L, kCjTheta, st));
+  GPT_HIPCHK(launch_hmc_prime(S, h->part_theta, h->L.nblk, st));
+  GPT_HIPCHK(launch_hmc_decide(S, 0, h->part_sc, h->L.nblk, 0, 0, 0, nullptr, nullptr, nullptr, st));
+  double U = 0.0;
+  GPT_HIPCHK(hipMemcpy(&U, S.sc, 8, hipMemcpyDeviceToHost));
+  if (!std::isfinite(U)) {
+    set_error("cjoint: theta or its joint likelihood is not finite at the start of the run");
+    return GPT_ERR_NAN_THETA;
+  }
+  h->cache_hyper.assign(hyper, hyper + Lh);
+  h->cache_ok = true;
+  return GPT_OK;
+}
+
+// The L leapfrog steps from (theta, p): L evaluations at the work position q.
+static int cj_hmc_integrate(gpt_cjoint* h, CjArgs A, double eps, int64_t L, hipStream_t st) {
+  const HmcDev& S = h->hmc;
+  const double s = std::sqrt(eps);
+  A.theta = S.q;
+  GPT_HIPCHK(launch_hmc_leap(S, 0, h->part_theta, h->L.nblk, s, st));
+  for (int64_t l = 1; l <= L; ++l) {
+    GPT_HIPCHK(launch_cjoint_eval(A, h->L, kCjTheta, st));
+    GPT_HIPCHK(launch_hmc_leap(S, l < L ? 1 : 2, h->part_theta, h->L.nblk, s, st));
+  }
+  return GPT_OK;
+}
+
+extern "C" int gpt_chmc_run(gpt_cjoint* h, const double* hyper, int64_t Lh, double eps, int64_t L,
+                              int64_t burnin, int64_t nsamples, int64_t thin, uint64_t seed,
+                              int64_t t0, double* theta_store, int32_t* accept_out, double* dH_out,
+                              double* value_out, int64_t* ndivergent_out) {
+  if (!h) { set_error("cjoint: null handle"); return GPT_ERR_BAD_DIMS; }
+  if (!cj_hyper_ok(hyper, Lh, h->D) || !cj_hmc_step_ok(eps, L)) return GPT_ERR_BAD_DIMS;
+  if (thin < 1 || burnin < 0 || nsamples < 0 || burnin > (1 << 24) || nsamples > (1 << 24)) {
+    set_error("cjoint: thin must be at least 1, burnin and nsamples in 0..2^24");
+    return GPT_ERR_BAD_DIMS;
+  }
+  const int64_t ntrans = burnin + nsamples, first = t0 >= 0 ? t0 : h->step;
+  if (first + ntrans > (1LL << 32)) {
+    set_error("cjoint: the step counter must stay below 2^32"); return GPT_ERR_BAD_DIMS;
+  }
+  hipStream_t st = nullptr;
+  CjArgs A;
+  int rc = cj_hmc_prepare(h, hyper, Lh, st, &A);
+  if (rc != GPT_OK) return rc;
+  const HmcDev& S = h->hmc;
+  const size_t nC = (size_t)h->n * h->C, ncols = (size_t)(nsamples / thin);
+  const size_t nrec = ntrans > 0 ? (size_t)ntrans : 1;
+  DevMem dstore, dacc, ddh, dval;
+  if (theta_store) GPT_HIPCHK(dstore.alloc<double>(nC * ncols));
+  GPT_HIPCHK(dacc.alloc<int32_t>(nrec));
+  GPT_HIPCHK(ddh.alloc<double>(nrec));
+  GPT_HIPCHK(dval.alloc<double>(nrec));
+  GPT_HIPCHK(hipMemsetAsync(S.ndiv, 0, 16, st));
+  h->cache_ok = false;                                  // until the run has gone through
+  for (int64_t i = 0; i < ntrans; ++i) {
+    const uint32_t t = (uint32_t)(first + i);
+    GPT_HIPCHK(launch_hmc_begin(S, true, seed, t, st));
+    rc = cj_hmc_integrate(h, A, eps, L, st);
+    if (rc != GPT_OK) return rc;
+    GPT_HIPCHK(launch_hmc_decide(S, 1, h->part_sc, h->L.nblk, seed, t, i, dacc.as<int32_t>(),
+                                 ddh.as<double>(), dval.as<double>(), st));
+    const int64_t k = i - burnin + 1;                   // 1-based count of transitions past burn-in
+    double* col = nullptr;
+    if (theta_store && k >= 1 && k % thin == 0 && (size_t)(k / thin) <= ncols)
+      col = dstore.as<double>() + nC * (size_t)(k / thin - 1);
+    GPT_HIPCHK(launch_hmc_commit(S, col, st));
+  }
+  h->step = first + ntrans;
+  long long ndiv = 0;
+  GPT_HIPCHK(hipMemcpy(&ndiv, S.ndiv, 8, hipMemcpyDeviceToHost));      // the one synchronisation
+  if (ndivergent_out) *ndivergent_out = ndiv;
+  if (theta_store && ncols) GPT_HIPCHK(dstore.download(theta_store, nC * ncols));
+  if (ntrans > 0) {
+    if (accept_out) GPT_HIPCHK(dacc.download(accept_out, (size_t)ntrans));
+    if (dH_out) GPT_HIPCHK(ddh.download(dH_out, (size_t)ntrans));
+    if (value_out) GPT_HIPCHK(dval.download(value_out, (size_t)ntrans));
+  }
+  h->cache_ok = true;                                   // U and grad U of the kept state stand
+  return GPT_OK;
+}
+
+extern "C" int gpt_chmc_leapfrog(gpt_cjoint* h, const double* hyper, int64_t Lh, double eps,
+                                   int64_t L, double* p_inout, double* q_out, double* H_out) {
+  if (!h || !p_inout) { set_error("cjoint: null handle or momentum"); return GPT_ERR_BAD_DIMS; }
+  if (!cj_hyper_ok(hyper, Lh, h->D) || !cj_hmc_step_ok(eps, L)) return GPT_ERR_BAD_DIMS;
+  hipStream_t st = nullptr;
+  CjArgs A;
+  int rc = cj_hmc_prepare(h, hyper, Lh, st, &A);
+  if (rc != GPT_OK) return rc;
+  const HmcDev& S = h->hmc;
+  const size_t nC = (size_t)h->n * h->C;
+  GPT_HIPCHK(hipMemcpy(S.p, p_inout, 8 * nC, hipMemcpyHostToDevice));
+  GPT_HIPCHK(launch_hmc_begin(S, false, 0, 0, st));
+  rc = cj_hmc_integrate(h, A, eps, L, st);
+  if (rc != GPT_OK) return rc;
+  GPT_HIPCHK(launch_hmc_decide(S, 2, h->part_sc, h->L.nblk, 0, 0, 0, nullptr, nullptr, nullptr, st));
+  GPT_HIPCHK(hipMemcpy(p_inout, S.p, 8 * nC, hipMemcpyDeviceToHost));
+  if (q_out) GPT_HIPCHK(hipMemcpy(q_out, S.q, 8 * nC, hipMemcpyDeviceToHost));
+  if (H_out) GPT_HIPCHK(hipMemcpy(H_out, S.sc + 2, 16, hipMemcpyDeviceToHost));
   return GPT_OK;
 }
 
@@ -320,6 +476,28 @@ extern "C" int gpt_gpnt_joint_langevin(const double* X, int64_t N, int64_t D, co
   if (rc != GPT_OK) return rc;
   rc = gpt_cjoint_set_theta(h, theta);
   if (rc == GPT_OK) rc = gpt_cjoint_langevin(h, hyper, Lh, eps, nsteps, seed, t0);
+  if (rc == GPT_OK) rc = gpt_cjoint_get_theta(h, theta);
+  gpt_cjoint_destroy(h);
+  return rc;
+}
+
+extern "C" int gpt_gpnt_joint_hmc(const double* X, int64_t N, int64_t D, const double* y, int64_t C,
+                                  const double* Z, const double* b, int64_t n, double* theta,
+                                  const double* hyper, int64_t Lh, double eps, int64_t L,
+                                  int64_t burnin, int64_t nsamples, int64_t thin, uint64_t seed,
+                                  int64_t t0, double* theta_store, int32_t* accept_out,
+                                  double* dH_out, double* value_out, int32_t* ndivergent_out) {
+  if (!cj_dims_ok(X, N, D, C, Z, b, n) || !cj_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
+  if (!theta || t0 < 0) { set_error("cjoint: null theta or negative t0"); return GPT_ERR_BAD_DIMS; }
+  gpt_cjoint* h = nullptr;
+  int rc = gpt_cjoint_create(X, N, D, y, C, Z, b, n, &h);
+  if (rc != GPT_OK) return rc;
+  rc = gpt_cjoint_set_theta(h, theta);
+  int64_t ndiv = 0;
+  if (rc == GPT_OK)
+    rc = gpt_chmc_run(h, hyper, Lh, eps, L, burnin, nsamples, thin, seed, t0, theta_store,
+                        accept_out, dH_out, value_out, &ndiv);
+  if (rc == GPT_OK && ndivergent_out) *ndivergent_out = (int32_t)ndiv;   // at most 2^25 transitions
   if (rc == GPT_OK) rc = gpt_cjoint_get_theta(h, theta);
   gpt_cjoint_destroy(h);
   return rc;

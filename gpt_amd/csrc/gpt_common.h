@@ -22,7 +22,12 @@ enum Stream : uint32_t {
   // gpdraw.hip: element (i, s) of a call's normals Z (M × S) is normal_at(seed, e = i, c1 = s,
   // c2 = kGpDraw, c3 = kind), kind 0 = GP prior, 1 = GP posterior, 2 = RFF θ; on the host
   // oracle.philox.normals(M, seed, s, 25, kind)[i].  Column s does not depend on S.
-  kGpDraw = 25
+  kGpDraw = 25,
+  // chmc.hip: the momentum of 0-based transition t is p[j, c] = normal_at(seed, e = j, c1 = t,
+  // c2 = kHmcMom, c3 = c), on the host oracle.philox.normals(n, seed, t, 26, c)[j]; the uniform of
+  // its Metropolis test is u53 of the first two words of block 0 of (seed, t, kHmcAccept, 0), on
+  // the host oracle.philox.uniform(seed, t, 27, 0), as GMC's accept draws from kGmcU.
+  kHmcMom = 26, kHmcAccept = 27
 };
 
 struct U4 { uint32_t x, y, z, w; };

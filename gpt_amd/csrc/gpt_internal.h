@@ -455,6 +455,39 @@ hipError_t launch_cjoint_finish(const CjArgs& A, const CjLayout& L, double sigma
 hipError_t launch_cjoint_update(const CjArgs& A, const CjLayout& L, double* theta, double eps,
                                 uint64_t seed, uint32_t t, int32_t* status, hipStream_t st);
 
+// Hamiltonian Monte Carlo on the resident theta of the joint likelihood (chmc.hip).
+// Entry e = c*n + j of an n*C array belongs to thread e of a grid of hmc_blocks(n, C) workgroups.
+constexpr int kHmcMaxBlocks = (1024 * 32 + kNT - 1) / kNT;
+int hmc_blocks(int n, int C);
+struct HmcDev {
+  double* theta;           // n*C   the chain's state (the evaluator's resident theta)
+  double *q, *p;           // n*C   work position and momentum
+  double *g_cur, *g_new;   // n*C   grad U at theta (the cache) and at the last evaluation's q
+  double *kin0, *kin1;     // hmc_blocks  per-workgroup sums of p^2 at the start and the end
+  double* prior;           // hmc_blocks  per-workgroup sums of q^2 at the last evaluation's q
+  double* sc;              // 4     [0] U(theta) (the cache), [2] H0 and [3] H1 of the integrator alone
+  int32_t* flag;           // 1     the last decision: 1 accepted
+  long long* ndiv;         // 1     divergent transitions of the call
+  const int32_t* status;   // non-zero: every launch does nothing
+  int n, C;
+};
+// p of transition t (draw: element j of the normal stream (seed, t, kHmcMom, c); otherwise the p
+// in place), q <- theta, kin0
+hipError_t launch_hmc_begin(const HmcDev& S, bool draw, uint64_t seed, uint32_t t, hipStream_t st);
+// kind 0: p -= s/2 g_cur, q += s p; 1: g = sum of the partials + q, p -= s g, q += s p;
+// 2: p -= s/2 g, g_new = g, kin1 and prior.  s = sqrt(eps).
+hipError_t launch_hmc_leap(const HmcDev& S, int kind, const double* part_theta, int nblk, double s,
+                           hipStream_t st);
+// after an evaluation at theta: g_cur and prior
+hipError_t launch_hmc_prime(const HmcDev& S, const double* part_theta, int nblk, hipStream_t st);
+// mode 0: sc[0] = U(theta); 1: the Metropolis decision of transition t, record i of the call;
+// 2: sc[2], sc[3] = H0, H1
+hipError_t launch_hmc_decide(const HmcDev& S, int mode, const double* part_sc, int nblk,
+                             uint64_t seed, uint32_t t, long long i, int32_t* acc_rec,
+                             double* dh_rec, double* val_rec, hipStream_t st);
+// theta <- q, g_cur <- g_new where accepted; store_col (n*C or null) <- the kept theta
+hipError_t launch_hmc_commit(const HmcDev& S, double* store_col, hipStream_t st);
+
 // Host-side Philox consumers (init / permutations / samplenz)
 void host_init_state(int n, int r, int D, int Q, uint64_t seed, bool stiefel, double sigma_w,
                      double* w, double* U, int cls = 0, bool cls_init = false);

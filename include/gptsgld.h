@@ -641,6 +641,33 @@ int gpt_cjoint_get_theta(gpt_cjoint* h, double* theta_out);
 int gpt_cjoint_langevin(gpt_cjoint* h, const double* hyper, int64_t Lh, double eps, int64_t nsteps,
                         uint64_t seed, int64_t t0);
 int gpt_cjoint_steps(gpt_cjoint* h, int64_t* step_out);
+/* Hamiltonian Monte Carlo on the resident theta at hyper, burnin + nsamples transitions with no
+ * host round trip.  U(theta) is the value above (the prior |theta|^2/2 included), H = U + |p|^2/2
+ * and eps is the squared step, s = sqrt(eps); L = 1 is the MALA loop of
+ * BloodTransfusionExperiment.jl:255-278.  0-based transition t (the counter of
+ * gpt_cjoint_langevin: t0 >= 0 sets it first, t0 < 0 continues):
+ *   p[j, c] = element j of the normal stream (seed, t, HMC_MOM = 26, c);
+ *   p -= s/2 grad U(theta), q = theta + s p; L - 1 times p -= s grad U(q), q += s p;
+ *   p -= s/2 grad U(q);  u = the uniform of (seed, t, HMC_ACCEPT = 27, 0);
+ *   theta <- q iff u < exp(H0 - H1); otherwise theta keeps its bits.
+ * A non-finite H1 rejects and is counted in *ndivergent_out; it is no error.  theta_store
+ * (n, C, nsamples/thin) takes theta after every thin-th transition past burn-in; accept_out, dH_out
+ * (H0 - H1) and value_out (U of the kept state) take one entry per transition, burn-in included.
+ * Every output may be NULL.  U and grad U of the kept state are cached across transitions and
+ * calls, so a transition costs L evaluations; set_theta, eval with a theta, langevin or other
+ * hyper bits drop the cache, and the result is bit for bit that of recomputing.
+ * GPT_ERR_BAD_DIMS before any kernel: eps not positive and finite, L outside 1..1024, thin < 1,
+ * burnin or nsamples outside 0..2^24, a counter that would pass 2^32, bad hyper.
+ * GPT_ERR_NAN_THETA before any transition: the starting theta or U(theta) is not finite. */
+int gpt_chmc_run(gpt_cjoint* h, const double* hyper, int64_t Lh, double eps, int64_t L,
+                   int64_t burnin, int64_t nsamples, int64_t thin, uint64_t seed, int64_t t0,
+                   double* theta_store, int32_t* accept_out, double* dH_out, double* value_out,
+                   int64_t* ndivergent_out);
+/* The integrator alone: L leapfrog steps from the resident theta (unchanged) on the momentum
+ * p_inout (n, C), which takes the final momentum; q_out (n, C) the final position, H_out = [H0, H1].
+ * q_out and H_out may be NULL. */
+int gpt_chmc_leapfrog(gpt_cjoint* h, const double* hyper, int64_t Lh, double eps, int64_t L,
+                        double* p_inout, double* q_out, double* H_out);
 /* scores (Ntest, C) = featureNotensor(Xtest)'theta at hyper for the resident theta: the block
  * gpt_class_eval reads as one sample.  The _dev form takes device pointers and a hipStream_t and
  * does not synchronise. */
@@ -673,6 +700,14 @@ int gpt_gpnt_joint_langevin(const double* X, int64_t N, int64_t D, const double*
                             const double* Z, const double* b, int64_t n, double* theta,
                             const double* hyper, int64_t Lh, double eps, int64_t nsteps,
                             uint64_t seed, int64_t t0);
+/* gpt_chmc_run from host arrays: theta (n, C) is the start and takes the final state, t0 >= 0;
+ * the divergent count (at most 2^25 transitions) is a 32-bit integer here. */
+int gpt_gpnt_joint_hmc(const double* X, int64_t N, int64_t D, const double* y, int64_t C,
+                       const double* Z, const double* b, int64_t n, double* theta,
+                       const double* hyper, int64_t Lh, double eps, int64_t L, int64_t burnin,
+                       int64_t nsamples, int64_t thin, uint64_t seed, int64_t t0,
+                       double* theta_store, int32_t* accept_out, double* dH_out, double* value_out,
+                       int32_t* ndivergent_out);
 int gpt_gpnt_joint_scores(const double* Xtest, int64_t Ntest, int64_t D, int64_t C, const double* Z,
                           const double* b, int64_t n, const double* theta, const double* hyper,
                           int64_t Lh, double* scores_out);

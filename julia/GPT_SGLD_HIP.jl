@@ -14,7 +14,7 @@ export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTreg
        GPNT_SGLD, GPNT_SGLD_chains, GPNT_SGLD_chains_x, GPNT_pred, GPNT_pred_x, GPT_SGLDERM_RMSprop, GPT_SGLDERMw, GPTclassification, GPT_GMC, pred_mean_x,
        init_state, GPNT_nlogmarginal, GPNT_gradnlogmarginal, GP_nlogmarginal, GP_gradnlogmarginal, GP_predict, GPNT_predict, RFF_kernel_error,
        GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class,
-       neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores,
+       neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores, joint_hmc, joint_mala,
        predictive, pred_predictive, pred_predictive_x, GPNT_predictive, GPNT_predictive_x,
        GPrand, GPpost_rand, GPNT_draw_theta, fhatdraw, createmesh
 
@@ -959,6 +959,39 @@ function joint_langevin(X::Array{Float64,2}, y::Array, Z::Array{Float64,2}, b::A
                 epsilon, nsteps, UInt64(seed), t0))
     return theta
 end
+
+# burnin + nsamples Hamiltonian Monte Carlo transitions on theta at hyperparams from the 0-based
+# transition t0: L leapfrog steps of size sqrt(epsilon) and a Metropolis test (L = 1: the MALA loop
+# of BloodTransfusionExperiment.jl:255-278).  Returns (theta_vec after the run, theta_store
+# (n, C, nsamples ÷ thin), accept, dH, value, ndivergent); accept, dH = H0 - H1 and value = U of
+# the kept state have one entry per transition.  Error code 4: the starting theta is not finite.
+function joint_hmc(X::Array{Float64,2}, y::Array, Z::Array{Float64,2}, b::Array{Float64},
+                   theta_vec::Array{Float64}, hyperparams::Vector{Float64}, epsilon::Real,
+                   L::Integer, nsamples::Integer, seed::Integer; burnin::Integer=0,
+                   thin::Integer=1, t0::Integer=0, C=nothing)
+    ncls = joint_classes(y, C)
+    N, D, n = joint_dims(X, y, Z, b, theta_vec, hyperparams, ncls)
+    (nsamples >= 0 && burnin >= 0 && t0 >= 0) || error("nsamples, burnin and t0 must not be negative")
+    (thin >= 1 && L >= 1) || error("thin and L must be at least 1")
+    yf = collect(Float64, vec(y))
+    theta = collect(Float64, vec(theta_vec))
+    ntrans = burnin + nsamples
+    store = Array{Float64}(undef, n, ncls, div(nsamples, thin))
+    accept = Array{Int32}(undef, ntrans)
+    dH = Array{Float64}(undef, ntrans)
+    value = Array{Float64}(undef, ntrans)
+    ndiv = Array{Int32}(undef, 1)
+    check(ccall((:gpt_gpnt_joint_hmc, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64,
+                 Ptr{Float64}, Ptr{Float64}, Int64, Float64, Int64, Int64, Int64, Int64, UInt64,
+                 Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                X, N, D, yf, ncls, Z, vec(b), n, theta, hyperparams, length(hyperparams),
+                epsilon, L, burnin, nsamples, thin, UInt64(seed), t0, store, accept, dH, value,
+                ndiv))
+    return theta, store, accept, dH, value, Int(ndiv[1])
+end
+joint_mala(X, y, Z, b, theta_vec, hyperparams, epsilon, nsamples, seed; kw...) =
+    joint_hmc(X, y, Z, b, theta_vec, hyperparams, epsilon, 1, nsamples, seed; kw...)
 
 # scores (Ntest, C) = featureNotensor(Xtest)' * theta at hyperparams: class_eval's input
 # (reshape to (Ntest, C, 1)), the prop_missed / mean_nlp line of ImageExperiment.jl:258-268
