@@ -3,7 +3,8 @@
 // Workgroup = D waves; wave k owns U^(k) (n×r) in REGISTERS for the step (lane λ holds rows
 // j = λ + 64·jj, jj < J).  A step (GPT_SGLD.jl:377-445) streams its minibatch G rows at a time;
 // each row slice phi[:,k,row] is read from HBM ONCE — staged into this wave's LDS slice by
-// LDS-DMA (global_load_lds) one group ahead — and used twice from registers:
+// LDS-DMA (global_load_lds), two groups ahead into two buffers in the J = 8 wide build and one group
+// ahead elsewhere (chain_bufs) — and used twice from registers:
 //   (b) temp[k,:,row]  = phi[:,k,row]ᵀ U^(k)                    (phidotU, :193-205)
 //   (c) V, fhat and the core sums A[:,k,row] for the G rows, all waves together
 //       (computeV / computefhat / computeU_phi / computeA, :208-273)
@@ -22,17 +23,21 @@ namespace gpt {
 
 // Variants measured and dropped in rounds 1-3 (DESIGN.md keeps the numbers) are no longer
 // switchable here: LDS-scratch (b) reductions, padded butterflies, other row-staging points,
-// double-buffered staging, L2 touches of the next batch, wave priorities, the fused M + G Gram.
-constexpr int kChainBufs = 1;     // row-staging buffers
+// one-array double-buffered staging, L2 touches of the next batch, wave priorities, the fused
+// M + G Gram.
 constexpr int kChainDMax = 8;     // waves per workgroup (one per input dimension)
+// Row-staging buffers of chain_kernel<R, J, G, WV>.  2: the J = 8, WV = 8 build stages row group g
+// into buffer g & 1 (pbufA / pbufB), two groups in flight; wave k's post-batch scratch X lies over
+// wave k's slice of pbufB, which is idle once the batch loop ends (ChainLds::x_in_ring).  1: the
+// WV = 4 build (two chains per CU under 80 KB: no room) and the J <= 4 builds (a slice of
+// G·64·J doubles does not hold X) keep one buffer and the schedule they had.
+GPT_HD constexpr int chain_bufs(int J, int WV) { return (J == 8 && WV == kChainDMax) ? 2 : 1; }
 constexpr int kChainTPW8 = 1;     // V tasks per wave at J = 8, D > 4
 constexpr int kChainTasks = 2;    // V-phase tasks per wave (NCH·G <= tasks·D); J = 8: kChainTPW8
 constexpr int kChainG = 2;        // batch rows per group (G = 3 spills 60 VGPRs)
 constexpr int kChainQPL = 4;      // q chunks of 64 (Q <= 64·kChainQPL)
 constexpr int kChainQP = 64 * kChainQPL;
 constexpr int kChainRun = 64;     // members per run (core entries with one value of I[·,k])
-constexpr int kChainRunS = 72;    // reduction scratch stride (doubles): 8-lane readers of rows
-                                  // l, l+1.. hit disjoint LDS bank ranges (72·2 dwords ≡ 16 banks)
 constexpr int kChainQS = 264;     // w·V row stride; slot kChainQP of a row is a constant 0
 
 constexpr int kChainMMax = 256;   // largest minibatch the engine takes
@@ -51,7 +56,9 @@ GPT_HD constexpr int al16c(int x) { return (x + 15) & ~15; }
 // engine's maxima (kChainDMax dimensions, Q <= kChainQP, m <= kChainMMax), so every LDS address
 // is a constant and none of them occupies a scalar register (the kernel sits at the SGPR limit).
 // The batch's row indices are not in the carve: they are a static array beside the row staging.
-template <int R, int G, int WV = kChainDMax>
+// BUFS = chain_bufs(J, WV).  Flagship <5, 8, 2, 8>: 24 192 B here + 2 × 65 536 (pbufA, pbufB) + 2 048
+// (ibuf) static = 157 312 of 163 840 B; with one buffer (X in the carve) 81 088 + 67 584.
+template <int R, int G, int WV = kChainDMax, int BUFS = 1>
 struct ChainLds {
   static constexpr int DRG = kChainDMax * R * G;          // temp entries of a slot
   static constexpr int TS = 2 * (DRG + G);                // temp | ones(G) | 1/temp | ones(G)
@@ -65,18 +72,20 @@ struct ChainLds {
   static constexpr int o_misc = al16c(o_gwp + 8 * NTMAX * 64);
   static constexpr int o_touch = al16c(o_misc + 8 * 16);                // 256 B DMA sink
   static constexpr int o_un = al16c(o_touch + 256);
-  // union: w·V rows [row][q] (stride kChainQS) + per-wave reduction scratch (batch loop) |
-  // per-wave post-batch scratch
-  // (per-wave parts sized for the WV waves of the build: at WV = 4 the carve plus the row staging
-  // stays under 80 KB, two chains per CU)
-  static constexpr int L_dbl = G * kChainQS + WV * G * R * kChainRunS;
+  // union: w·V rows [row][q] (stride kChainQS, batch loop) | per-wave post-batch scratch
+  // (sized for the WV waves of the build: at WV = 4 the carve plus the row staging stays under
+  // 80 KB, two chains per CU).  With two staging buffers the post-batch scratch is not here: wave
+  // k's lies over wave k's slice of the second buffer.
+  static constexpr bool x_in_ring = BUFS == 2;
+  static constexpr int L_dbl = G * kChainQS;
   // expm(−tA) has scratch of its own in the wide build; the WV = 4 carve (two chains per CU, under
   // 80 KB with the row staging) has no room for it
   static constexpr bool own_x1 = WV == kChainDMax;
   static constexpr int x_dbl = chain_scratch_dbl(R, own_x1);
   // after the union: the U noise's (sin, cos)(2πi/256) table (WV = 8 builds; the WV = 4 carve
   // stays under 80 KB for two chains per CU and draws its angles by polynomial)
-  static constexpr int o_tab = al16c(o_un + 8 * (L_dbl > x_dbl * WV ? L_dbl : x_dbl * WV));
+  static constexpr int un_dbl = (x_in_ring || L_dbl > x_dbl * WV) ? L_dbl : x_dbl * WV;
+  static constexpr int o_tab = al16c(o_un + 8 * un_dbl);
   static constexpr bool tab = WV == kChainDMax;
   static constexpr int bytes = al16c(o_tab + (tab ? 8 * 64 : 0));
 };
@@ -191,6 +200,18 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// s_waitcnt vmcnt(N) alone: a counted wait that leaves the N youngest vector-memory operations (a
+// younger row group's LDS-DMA) in flight.  As the builtin it is an instruction the compiler's own
+// wait counting reads; the empty asm keeps memory accesses on their side of it.  gfx9 encoding:
+// vmcnt in bits 3:0 and 15:14, expcnt (6:4) and lgkmcnt (11:8) at their maxima.
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
+  asm volatile("" ::: "memory");
+}
+
 // WV: waves per workgroup the build is bounded for — kChainDMax, or 4 for D <= 4, where one wave
 // per SIMD leaves the register file to two V tasks per wave even at J = 8 (PowerPlant, D = 4,
 // minibatch 256: 8 tasks per row group).
@@ -200,7 +221,14 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
                                                                 const long long* __restrict__ tbase,
                                                                 int t_local, int nsteps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ __attribute__((aligned(16))) double pbuf[kChainBufs * WV * G * 64 * J];   // row staging
+  // Row staging.  With the ring (kRing) row group g of a batch lives in pbufA for even g and in
+  // pbufB for odd g, and group g + 2 is issued as soon as group g is in registers: a row has two
+  // group-times to arrive and up to two groups per wave (128 KB per CU) are in flight.
+  constexpr bool kRing = chain_bufs(J, WV) == 2;
+  constexpr int PW = G * 64 * J;                                // doubles of one wave's slice
+  constexpr int ND = G * (J >= 2 ? J / 2 : 2);                  // DMA instructions of a row group
+  __shared__ __attribute__((aligned(16))) double pbufA[WV * PW];
+  __shared__ __attribute__((aligned(16))) double pbufB[kRing ? WV * PW : 2];
   // Row indices of two batches: batch t's in slot t & 1 and batch t + 1's in the other; at the end
   // of step t batch t + 2's go by LDS-DMA into the slot batch t has left.  An array of its own, not
   // a piece of smem: the compiler orders the LDS reads of an array behind the pending DMA into that
@@ -211,7 +239,8 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   const ChainDesc* Cp = chains + blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, k = uni(tid >> 6);
   const int n = P.n, D = P.D, Q = P.Q, m = P.m, NTH = 64 * D;
-  using L = ChainLds<R, G, WV>;
+  using L = ChainLds<R, G, WV, chain_bufs(J, WV)>;
+  static_assert(!L::x_in_ring || L::x_dbl <= PW, "the post-batch scratch fits the wave's slice");
   const int NCH = (Q + 63) / 64, NT = NCH * G;                  // q chunks of 64, V tasks
   int* IT_l = (int*)(smem + L::o_IT);
   double* w_l = (double*)(smem + L::o_w);
@@ -223,10 +252,24 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
   double* misc = (double*)(smem + L::o_misc);
   int* flag = (int*)(misc + 8);
   double* wVr = (double*)(smem + L::o_un);                      // w_q·V_q per batch row
-  double* X = (double*)(smem + L::o_un) + k * L::x_dbl;         // this wave's scratch
+  double* pw0 = pbufA + k * PW;                                 // this wave's staged rows
+  [[maybe_unused]] double* pw1 = pbufB + (kRing ? k * PW : 0);  // (odd groups, with the ring)
+  // this wave's post-batch scratch: over its own slice of pbufB with the ring.  No other wave
+  // touches the slice, and this wave issues no DMA into it between its last row group and the top
+  // of the next step.
+  double* X = L::x_in_ring ? pw1 : (double*)(smem + L::o_un) + k * L::x_dbl;
+  // ... and as an LDS pointer the compiler cannot trace to pbufB: in front of an access it knows
+  // to be pbufB's it waits, with any LDS-DMA pending that is not into pbufB, for ALL of them —
+  // a vmcnt(0) behind the next batch's row and index DMA at every block of the Stiefel phase
+  // (the carve's tables, which it cannot place either, are read with no such wait).  The order
+  // against the DMA into the slice is kept by hand: wait_vm<0>() behind the batch loop, and the
+  // end-of-step barrier's lgkmcnt(0) in front of the next issue.
+  if constexpr (L::x_in_ring) {
+    auto* x3 = (__attribute__((address_space(3))) double*)X;
+    asm volatile("" : "+s"(x3));
+    X = (double*)x3;
+  }
   double* xi_l = X;                                             // noise slots (before expm)
-  double* pw0 = pbuf + k * (kChainBufs * G * 64 * J);           // this wave's staged rows
-  [[maybe_unused]] double* bscr = wVr + G * kChainQS + k * G * R * kChainRunS;   // per row
 
   // steps t0 .. tend-1 of this chain in one launch (a chunk of at most one epoch): U^(k) stays in
   // registers and w in LDS between steps; the next batch's rows and targets are fetched during
@@ -424,6 +467,21 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
 #pragma unroll
   for (int x = 0; x < TPW; ++x) { vsave[x] = 0.0; gw[x] = 0.0; }
 
+  // Ring: the batch's second row group goes out here, into pbufB.  X, which lies there, is this
+  // wave's alone and its last access is behind the end-of-step barrier's lgkmcnt(0); the loads
+  // above have been consumed (gq is pinned), so no compiler wait for them lands behind this DMA.
+  // Older than it in the VM queue: group 0's DMA, the row-index DMA of batch t + 2 and the U / w
+  // stores, all covered by group 0's counted wait.
+  if constexpr (kRing) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(gq[i]));
+    if (Bt > G) {
+      int ln = lane;                    // opaque: the piece offsets are not kept across the step
+      asm volatile("" : "+v"(ln));
+      stage(G, ln, pw1);
+    }
+  }
+
   int slot = 0;
   for (int g0 = 0; g0 < Bt; g0 += G, slot ^= 1) {
     // lane id the compiler cannot see through: per-lane addresses are recomputed inside the
@@ -431,10 +489,29 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
     int ln = lane;
     asm volatile("" : "+v"(ln));
     LSTAMP(0);
-    // (a) this wave's staged rows -> registers, then stage the next group behind them
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // (a) this wave's staged rows -> registers, then stage a later group behind them
+    if constexpr (kRing) {
+      // The next group's DMA (ND instructions, the other buffer), where there is one, was issued
+      // behind this group's: this group's has landed once at most ND are outstanding.  The last
+      // group of a batch waits for vmcnt(0), so nothing is in flight past the loop.
+      if (g0 + G < Bt) wait_vm<ND>();
+      else wait_vm<0>();
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     LSTAMP(1);
     double* pw = pw0;
+    if constexpr (kRing) {
+      // One copy of the loop body serves both buffers (unrolled by two, each half naming its
+      // array, the step took 9.5 k cycles more for the second copy alone).  The buffer of this
+      // group by its parity, as an LDS pointer the compiler cannot trace to either array: it then
+      // puts no wait of its own in front of the reads (one it could trace to "pbufA or pbufB" it
+      // would order behind the younger group's DMA with a vmcnt(0)); the counted wait above is
+      // the only order there is.
+      auto* q = (__attribute__((address_space(3))) double*)(slot ? pw1 : pw0);
+      asm volatile("" : "+s"(q));
+      pw = (double*)q;
+    }
     double p[G][J];
 #pragma unroll
     for (int gg = 0; gg < G; ++gg)
@@ -443,6 +520,11 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
         p[gg][jj] = pw[gg * 64 * J + ln + 64 * jj];   // j >= n: finite in-row values, u = 0 there
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     LSTAMP(2);
+    // Ring: p is in registers and the slice is free, so the group after the next goes out at once
+    // (in front of (b): 179.1 k cycles per step, behind it 183.6 k, the one-buffer kernel 182.8 k)
+    if constexpr (kRing) {
+      if (g0 + 2 * G < Bt) stage(g0 + 2 * G, ln, pw);
+    }
     // (b) temp[k,l,row] and 1/temp for the G rows: R partial dots per lane, reduced through this
     // wave's LDS scratch by 8-lane groups (lane 8l+s sums 8 partials of output l, DPP finishes)
     double* tsl = temp_l + slot * L::TS;
@@ -469,8 +551,11 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
         tsl[DRG + G + (k * R + l) * G + gg] = rcp_nr(v[0]);
       }
     }
-    // the next group's rows are staged here, behind (b) (measured best of five placements)
-    if (g0 + G < Bt) stage(g0 + G, ln, pw);
+    // one buffer: the next group's rows are staged here, behind (b) (measured best of five
+    // placements)
+    if constexpr (!kRing) {
+      if (g0 + G < Bt) stage(g0 + G, ln, pw);
+    }
     LSTAMP(3);
     lds_barrier();
     LSTAMP(4);
@@ -544,6 +629,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
     }
     LSTAMP(7);
   }
+  if constexpr (kRing) wait_vm<0>();    // nothing is pending (see above): X, over pbufB, is free
   CSTAMP(2);
 
   // loaded after the batch loop (see Cp), through a pointer the compiler cannot see through, so
@@ -873,6 +959,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void chain_kernel(StepPar
     }
     if (flag[0]) {                        // NaN in the geodesic: the chain stops (:422-424)
       if (tid == 0) __hip_atomic_store(C.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if constexpr (kRing) wait_vm<0>();  // the next batch's rows and indices: no DMA outlives the wave
       return;
     }
     // both targets are uniform and null on a step that neither ends the launch nor stores: held
@@ -913,16 +1000,17 @@ static_assert(contains(ChainWVs{}, kChainDMax), "the wide U phase has one wave p
 // Static LDS of chain_kernel<R, J, G>: the row staging buffer and the two row-index slots.
 static int chain_wv(int D) { return D <= 4 ? 4 : kChainDMax; }
 static size_t chain_static_lds(int J, int WV) {
-  return 8 * (size_t)kChainBufs * WV * kChainG * 64 * J + 2 * 4 * kChainMMax;   // pbuf + ibuf
+  return 8 * (size_t)chain_bufs(J, WV) * WV * kChainG * 64 * J + 2 * 4 * kChainMMax;   // pbufA/B + ibuf
 }
 
 static int chain_J(int n) { return n <= 64 ? 1 : (n <= 128 ? 2 : (n <= 256 ? 4 : (n <= 512 ? 8 : 0))); }
 
 size_t chain_lds_bytes(int n, int D, int r, int Q, int m) {
-  (void)n; (void)Q; (void)m;
+  (void)Q; (void)m;
   return with_value_or(ChainRanks{}, r, (size_t)1 << 30, [&](auto R) {
     return with_value_or(ChainWVs{}, chain_wv(D), (size_t)1 << 30, [&](auto WV) {
-      return (size_t)ChainLds<R, kChainG, WV>::bytes;
+      return chain_bufs(chain_J(n), WV) == 2 ? (size_t)ChainLds<R, kChainG, WV, 2>::bytes
+                                             : (size_t)ChainLds<R, kChainG, WV, 1>::bytes;
     });
   });
 }
