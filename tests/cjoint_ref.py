@@ -5,7 +5,10 @@ tests/golden/cjoint_mp.npz and the error yardstick of the device parity tests.
     neglogjoint_literal / gradneglogjoint_literal   ImageExperiment.jl:135-204 (per-row loops and
                                                     the n x N x (Lh) gradfeatureNotensor array)
     value_and_grad_fused                            the one-pass form the device runs
-    mp_value_grad                                   the same quantities at 50 digits
+    mp_value_grad                                   the same quantities at 50 digits (mp_core
+                                                    keeps them as mpf, mp_features is its phi, S)
+    ld_value_grad                                   the fused form in long double
+    cjoint_layout                                   the device's tile layout restated
     langevin                                        the E step of GPNT_hyperparameters_ng
                                                     (GPT_SGLD.jl:1031-1033)
 
@@ -191,60 +194,150 @@ def langevin(X, y, Z, b, theta, h, eps, nsteps, seed, t0=0, gradtheta=gradtheta_
 
 
 # --------------------------------------------------------------------------- mpmath
+MP_DIGITS = 50
+
+
+def mp_features(X, Z, b, h, want_S=True):
+    """phi = c cos f and S = c sin f (n rows of N mpf) at 50 digits from the float64 inputs, with
+    Zt = Z / l formed in mp; a leapfrog evaluates many theta on one of these.  Call under
+    mp.workdps(MP_DIGITS)."""
+    import mpmath as mp
+    M = mp.mpf
+    N, D = X.shape
+    n = Z.shape[0]
+    Lh = len(h)
+    hh = [M(float(v)) for v in h]
+    ls = [hh[0]] * D if Lh == 2 else hh[:D]
+    sig = hh[-1]
+    Xm = [[M(float(X[i, k])) for k in range(D)] for i in range(N)]
+    Zt = [[M(float(Z[j, k])) / ls[k] for k in range(D)] for j in range(n)]
+    cc = mp.sqrt(M(2) / n) * sig
+    f = [[mp.fdot(Xm[i], Zt[j]) + M(float(b[j])) for i in range(N)] for j in range(n)]
+    phi = [[cc * mp.cos(v) for v in row] for row in f]                          # phi[j][i]
+    S = [[cc * mp.sin(v) for v in row] for row in f] if want_S else None
+    return dict(n=n, N=N, D=D, Lh=Lh, ls=ls, sig=sig, Xm=Xm, Zt=Zt, phi=phi, S=S,
+                phic=[[phi[j][i] for j in range(n)] for i in range(N)])
+
+
+def mp_theta(theta):
+    """theta (n, C) of doubles as th[j][c] of mpf (exact)."""
+    import mpmath as mp
+    return [[mp.mpf(float(v)) for v in row] for row in np.asarray(theta, dtype=np.float64)]
+
+
+def mp_core(F, y, th, want_h=True):
+    """value, gradtheta (gt[j][c]) and gradh (list, or None) as mpf at the mpf theta th[j][c] on
+    mp_features' F: nothing is rounded to double, so an integrator can chain evaluations.  Call
+    under mp.workdps(MP_DIGITS)."""
+    import mpmath as mp
+    M = mp.mpf
+    n, N, D, Lh = F["n"], F["N"], F["D"], F["Lh"]
+    C = len(th[0])
+    phi, phic = F["phi"], F["phic"]
+    yi = labels0(y, C)
+    thc = [[th[j][c] for j in range(n)] for c in range(C)]
+    val = M(0)
+    rs = M(0)
+    R = [[None] * N for _ in range(C)]                                          # R[c][i]
+    for i in range(N):
+        s = [mp.fdot(thc[c], phic[i]) for c in range(C)]
+        a = max(s)
+        lse = a + mp.log(mp.fsum(mp.exp(v - a) for v in s))
+        val += lse - s[yi[i]]
+        for c in range(C):
+            r = mp.exp(s[c] - lse) - (1 if c == yi[i] else 0)
+            R[c][i] = r
+            rs += r * s[c]
+    val += mp.fsum(v * v for row in th for v in row) / 2
+    gt = [[mp.fdot(phi[j], R[c]) + th[j][c] for c in range(C)] for j in range(n)]
+    if not want_h:
+        return val, gt, None
+    S, Zt, ls = F["S"], F["Zt"], F["ls"]
+    Xc = [[F["Xm"][i][k] for i in range(N)] for k in range(D)]
+    Rcol = [[R[c][i] for c in range(C)] for i in range(N)]
+    gl = [M(0)] * D
+    for j in range(n):
+        T = [S[j][i] * mp.fdot(th[j], Rcol[i]) for i in range(N)]
+        for k in range(D):
+            gl[k] += Zt[j][k] * mp.fdot(T, Xc[k])
+    gl = [gl[k] / ls[k] for k in range(D)]
+    gh = [mp.fsum(gl)] if Lh == 2 else list(gl)
+    gh.append(rs / F["sig"])
+    return val, gt, gh
+
+
 def mp_value_grad(X, y, Z, b, theta, h):
     """value (float), gradtheta (n, C) and gradh (Lh) from a 50-digit evaluation.  Zt = Z / l is
     formed in mp from the float64 inputs, so this is the true value at those inputs."""
     import mpmath as mp
-    old = mp.mp.dps
-    mp.mp.dps = 50
-    try:
-        M = mp.mpf
-        n, C = theta.shape
-        N, D = X.shape
-        Lh = len(h)
-        hh = [M(float(v)) for v in h]
-        ls = [hh[0]] * D if Lh == 2 else hh[:D]
-        sig = hh[-1]
-        yi = labels0(y, C)
-        Xm = [[M(float(X[i, k])) for k in range(D)] for i in range(N)]
-        Xc = [[Xm[i][k] for i in range(N)] for k in range(D)]
-        Zt = [[M(float(Z[j, k])) / ls[k] for k in range(D)] for j in range(n)]
-        th = [[M(float(theta[j, c])) for c in range(C)] for j in range(n)]      # th[j][c]
-        thc = [[th[j][c] for j in range(n)] for c in range(C)]
-        cc = mp.sqrt(M(2) / n) * sig
-        f = [[mp.fdot(Xm[i], Zt[j]) + M(float(b[j])) for i in range(N)] for j in range(n)]
-        phi = [[cc * mp.cos(v) for v in row] for row in f]                      # phi[j][i]
-        S = [[cc * mp.sin(v) for v in row] for row in f]
-        phic = [[phi[j][i] for j in range(n)] for i in range(N)]
-        val = M(0)
-        rs = M(0)
-        R = [[None] * N for _ in range(C)]                                      # R[c][i]
-        for i in range(N):
-            s = [mp.fdot(thc[c], phic[i]) for c in range(C)]
-            a = max(s)
-            lse = a + mp.log(mp.fsum(mp.exp(v - a) for v in s))
-            val += lse - s[yi[i]]
-            for c in range(C):
-                r = mp.exp(s[c] - lse) - (1 if c == yi[i] else 0)
-                R[c][i] = r
-                rs += r * s[c]
-        val += mp.fsum(v * v for row in th for v in row) / 2
-        gtheta = np.empty((n, C))
-        for j in range(n):
-            for c in range(C):
-                gtheta[j, c] = float(mp.fdot(phi[j], R[c]) + th[j][c])
-        Rcol = [[R[c][i] for c in range(C)] for i in range(N)]
-        gl = [M(0)] * D
-        for j in range(n):
-            T = [S[j][i] * mp.fdot(th[j], Rcol[i]) for i in range(N)]
-            for k in range(D):
-                gl[k] += Zt[j][k] * mp.fdot(T, Xc[k])
-        gl = [gl[k] / ls[k] for k in range(D)]
-        gh = [mp.fsum(gl)] if Lh == 2 else list(gl)
-        gh.append(rs / sig)
+    with mp.workdps(MP_DIGITS):
+        val, gt, gh = mp_core(mp_features(X, Z, b, h), y, mp_theta(theta))
+        gtheta = np.array([[float(v) for v in row] for row in gt])
         return float(val), gtheta, np.array([float(v) for v in gh])
-    finally:
-        mp.mp.dps = old
+
+
+def ld_value_grad(X, y, Z, b, theta, h):
+    """value, gradtheta (n, C), gradh (Lh) in np.longdouble (x87 80-bit where numpy has it): the
+    fused form on the float64 inputs, the reference of the tile-walk cases whose mpmath evaluation
+    takes too long (tests/golden/make_exactgp_golden.py's way above N = 259)."""
+    L = np.longdouble
+    n, C = theta.shape
+    N, D = X.shape
+    h = np.asarray(h, dtype=np.float64)
+    ls, sigma = split(h, D)
+    yi = labels0(y, C)
+    Xl, th = X.astype(L), theta.astype(L)
+    lsl = ls.astype(L)
+    Zt = Z.astype(L) / lsl
+    f = Zt @ Xl.T + b.astype(L)[:, None]
+    c = np.sqrt(L(2) / L(n)) * L(sigma)
+    phi, S = c * np.cos(f), c * np.sin(f)
+    s = th.T @ phi
+    a = s.max(axis=0)
+    lse = a + np.log(np.exp(s - a).sum(axis=0))
+    R = np.exp(s - lse)
+    R[yi, np.arange(N)] -= L(1)
+    val = np.sum(lse - s[yi, np.arange(N)]) + np.sum(th * th) / L(2)
+    gtheta = phi @ R.T + th
+    T = S * (th @ R)
+    gl = (Zt * (T @ Xl)).sum(axis=0) / lsl
+    gh = np.empty(h.size, dtype=L)
+    if h.size == 2:
+        gh[0] = gl.sum()
+    else:
+        gh[:D] = gl
+    gh[-1] = np.sum(R * s) / L(sigma)
+    return val, gtheta, gh
+
+
+# --------------------------------------------------------------------------- device layout
+CJ_LDS, CJ_MAX_BLOCKS, NW = 160 * 1024, 256, 8
+
+
+def _al16(x):
+    return (x + 15) & ~15
+
+
+def cjoint_layout(n, N, C):
+    """gpt_amd/csrc/cjoint.hip's cjoint_layout restated (the C ABI has no query for it): dict(CC,
+    TI, ntiles, nblk, theta_lds, bytes).  Workgroup w of nblk walks the tiles w, w + nblk, ..."""
+    CC = 2 if C <= 2 else 4 if C <= 4 else 8 if C <= 8 else 16 if C <= 16 else 32
+    TI = 32
+    while True:
+        o = _al16(8 * CC * TI)
+        o = _al16(o + 8 * 16 * TI)
+        o = _al16(o + 8 * 16)
+        o = _al16(o + 8 * NW)
+        o = _al16(o + 8 * n * TI)
+        o = _al16(o + 8 * n * TI)
+        if o <= CJ_LDS or TI == 8:
+            break
+        TI //= 2
+    with_theta = _al16(o + 8 * n * CC)
+    theta_lds = with_theta <= CJ_LDS
+    ntiles = -(-N // TI)
+    return dict(CC=CC, TI=TI, ntiles=ntiles, nblk=min(ntiles, CJ_MAX_BLOCKS),
+                theta_lds=bool(theta_lds), bytes=with_theta if theta_lds else o)
 
 
 # --------------------------------------------------------------------------- golden and yardstick

@@ -105,11 +105,12 @@ def gpnt_sgld_class(phi, y, sigma_theta, m, eps_theta, decay_rate, burnin, maxep
 
 
 def gpnt_sgld_class_literal(phi, y, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch,
-                            param_seed):
-    """The same with the loops of :877-892 transcribed one to one."""
+                            param_seed, ncls=None):
+    """The same with the loops of :877-892 transcribed one to one (``ncls``: C where the labels do
+    not span it)."""
     phi = np.asarray(phi, dtype=np.float64)
     n, N = phi.shape
-    yi, C = check_labels(y)
+    yi, C = check_labels(y, ncls)
     numbatches = -(-N // m)
     theta = np.empty((n, C))
     for c in range(C):
