@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import cls_ref as CR
+import gpnt_ref as GR
 from oracle import gpt_sgld_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -189,9 +190,13 @@ def test_device_pointer_evaluation_equals_the_host_form():
 
 
 # ------------------------------------------------------------------------ full-theta evaluation
-@pytest.mark.parametrize("dims", [(70, 130, 3, 4), (150, 257, 7, 3), (16, 64, 2, 1), (33, 65, 16, 5)])
+@pytest.mark.parametrize("dims", [(70, 130, 3, 4), (150, 257, 7, 3), (16, 64, 2, 1), (33, 65, 16, 5),
+                                  (20, 70, 32, 3)])
 def test_full_theta_evaluation(dims):
-    """(n, Ntest, C, T): ragged K, row and column tiles of nt_scores_kernel."""
+    """(n, Ntest, C, T): ragged K, row and column tiles of nt_scores_kernel; the last has S = C·T = 96,
+    two column tiles with a ragged second.  Every score is one fma chain over j, so it is held to
+    (n + 2)·2^-53·sum_j |phitest[j, i]·theta[j, s]| of the 50-digit dot product (the bound of
+    tests/test_gpu_gpnt.py::test_scores_against_mpmath), beside the 1e-13·max|want| of the einsum."""
     n, Nt, C, T = dims
     rng = np.random.default_rng(n + Nt)
     theta = rng.standard_normal((n, C, T))
@@ -202,6 +207,12 @@ def test_full_theta_evaluation(dims):
     want = np.einsum("ji,jct->ict", phitest, theta)
     assert ev.scores.shape == (Nt, C, T)
     assert np.abs(ev.scores - want).max() <= 1e-13 * np.abs(want).max()
+    smp, mag = GR.scores_mp(phitest, theta.reshape((n, C * T), order="F"))
+    got = ev.scores.reshape((Nt, C * T), order="F")
+    worst = max(GR.abs_err_mp(got[i, s], smp[i][s]) / ((n + 2) * GR.U * mag[i, s])
+                for i in range(Nt) for s in range(C * T))
+    print("scores %s: worst error / bound = %.3f" % (dims, worst))
+    assert worst <= 1.0
     assert same_figures(ev, G().class_eval(ev.scores, y, window=window))
     cols = [T - 1, 0]
     sub = G().GPNT_pred_class(theta, phitest, y, cols=cols, scores=True)
