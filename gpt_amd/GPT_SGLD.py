@@ -588,25 +588,30 @@ def _per_chain(values, nchains, what):
     return v
 
 
+def _chain_seeds(seeds, store_every):
+    seeds = np.ascontiguousarray([int(s) & (2 ** 64 - 1) for s in np.atleast_1d(seeds)], dtype=np.uint64)
+    if seeds.size < 1:
+        raise ValueError("seeds must have one entry per chain")
+    if int(store_every) < 1:
+        raise ValueError("store_every must be >= 1")
+    return seeds
+
+
 def _chains_args(y, N, signal_vars, sigma_thetas, eps_thetas, seeds, store_every):
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
     if y.size != N:
         raise ValueError("the features and y disagree on N")
-    seeds = np.ascontiguousarray([int(s) & (2 ** 64 - 1) for s in np.atleast_1d(seeds)], dtype=np.uint64)
+    seeds = _chain_seeds(seeds, store_every)
     k = seeds.size
-    if k < 1:
-        raise ValueError("seeds must have one entry per chain")
-    if int(store_every) < 1:
-        raise ValueError("store_every must be >= 1")
     return (y, _per_chain(signal_vars, k, "signal_vars"), _per_chain(sigma_thetas, k, "sigma_thetas"),
             _per_chain(eps_thetas, k, "eps_thetas"), seeds)
 
 
-def _chains_out(n, N, m, burnin, maxepoch, store_every, nchains):
+def _chains_out(lead, N, m, burnin, maxepoch, store_every, nchains):
     if int(m) < 1:
         raise ValueError("m must be >= 1")
     kept = (int(maxepoch) + int(burnin)) * (-(-N // int(m))) // int(store_every)
-    return np.zeros((n, max(kept, 0), nchains), order="F"), np.zeros(nchains, dtype=np.int32)
+    return np.zeros((*lead, max(kept, 0), nchains), order="F"), np.zeros(nchains, dtype=np.int32)
 
 
 def GPNT_SGLD_chains(phi, y, signal_vars, sigma_thetas, m, eps_thetas, decay_rate, burnin, maxepoch,
@@ -621,7 +626,7 @@ def GPNT_SGLD_chains(phi, y, signal_vars, sigma_thetas, m, eps_thetas, decay_rat
     n, N = phi.shape
     y, sv, sth, eps, seeds = _chains_args(y, N, signal_vars, sigma_thetas, eps_thetas, seeds,
                                           store_every)
-    out, status = _chains_out(n, N, m, burnin, maxepoch, store_every, seeds.size)
+    out, status = _chains_out((n,), N, m, burnin, maxepoch, store_every, seeds.size)
     check(lib().gpt_gpnt_sgld_chains(_ptr(phi), _ptr(y), n, N, int(m), _ptr(sv), _ptr(sth),
                                      _ptr(eps), float(decay_rate), int(burnin), int(maxepoch),
                                      _ptr(seeds, P_U64), seeds.size, int(store_every), _ptr(out),
@@ -653,7 +658,7 @@ def GPNT_SGLD_chains_x(X, y, length_scale, sigma_RBF, Z, b, signal_vars, sigma_t
     N, D = X.shape
     y, sv, sth, eps, seeds = _chains_args(y, N, signal_vars, sigma_thetas, eps_thetas, seeds,
                                           store_every)
-    out, status = _chains_out(n, N, m, burnin, maxepoch, store_every, seeds.size)
+    out, status = _chains_out((n,), N, m, burnin, maxepoch, store_every, seeds.size)
     check(lib().gpt_gpnt_sgld_chains_x(_ptr(X), _ptr(y), N, D, _ptr(ls), ls.size, float(sigma_RBF),
                                        _ptr(Z), _ptr(b), n, int(m), _ptr(sv), _ptr(sth), _ptr(eps),
                                        float(decay_rate), int(burnin), int(maxepoch),
@@ -956,18 +961,10 @@ def GPNT_SGLDclass_chains(phi, y, sigma_theta, m, eps_thetas, decay_rate, burnin
         raise ValueError("phi and y disagree on N")
     if ncls is None:
         ncls = int(y.max() - y.min() + 1)
-    seeds = np.ascontiguousarray([int(s) & (2 ** 64 - 1) for s in np.atleast_1d(seeds)], dtype=np.uint64)
-    eps = _f64(np.atleast_1d(eps_thetas))
-    if eps.size == 1 and seeds.size > 1:
-        eps = _f64(np.full(seeds.size, eps[0]))
-    if eps.size != seeds.size:
-        raise ValueError("eps_thetas and seeds must have one entry per chain")
-    if int(store_every) < 1:
-        raise ValueError("store_every must be >= 1")
-    nb = -(-N // m)
-    kept = (maxepoch + burnin) * nb // int(store_every)
-    out = np.zeros((n, max(int(ncls), 1), kept, seeds.size), order="F")
-    status = np.zeros(seeds.size, dtype=np.int32)
+    seeds = _chain_seeds(seeds, store_every)
+    eps = _per_chain(eps_thetas, seeds.size, "eps_thetas")
+    out, status = _chains_out((n, max(int(ncls), 1)), N, m, burnin, maxepoch, store_every,
+                              seeds.size)
     check(lib().gpt_gpnt_sgld_class_chains(_ptr(phi), _ptr(y), n, N, int(ncls), float(sigma_theta),
                                            int(m), _ptr(eps), float(decay_rate), int(burnin),
                                            int(maxepoch), _ptr(seeds, P_U64), seeds.size,

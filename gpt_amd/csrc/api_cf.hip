@@ -100,7 +100,7 @@ static int cf_sgd_run(
          f.testpred_store && f.trainRMSE && f.testRMSE && f.N >= 1 && f.Ntest >= 1 &&
          f.ldr >= f.N && f.ldt >= f.Ntest && f.N == folds[0].N;
   if (!ok) { set_error(std::string("bad ") + name + " arguments"); return GPT_ERR_BAD_DIMS; }
-  if (!rank_supported((int)r) || cf_lds_bytes((int)r, (int)m, (int)(D1 + D2), D1 <= 64 && D2 <= 64) > 160 * 1024) {
+  if (!rank_supported((int)r) || cf_lds_bytes((int)r, (int)m, (int)(D1 + D2), D1 <= 64 && D2 <= 64) > kMaxLds) {
     set_error(std::string(name) + ": rank not instantiated (" + ranks_text() + ") or minibatch too large");
     return GPT_ERR_BAD_DIMS;
   }
@@ -263,7 +263,7 @@ static int cf_sgd_run(
   const double cdecay = 1.0 - P.epsU / (2.0 * P.sigma_u * P.sigma_u);
   const bool lazy = !stiefel && !langevin && P.umask != nullptr && cdecay > 0.0 && cdecay < 1.0 &&
                     cf_lazy_lds_bytes((int)r, (int)m, (int)(D1 + D2), rowsU + rowsV, nbatch) <=
-                        160 * 1024 &&
+                        kMaxLds &&
                     !(std::getenv("GPTSGLD_CF_LAZY") && std::strcmp(std::getenv("GPTSGLD_CF_LAZY"), "0") == 0);
   g_cf_mode = stiefel ? 1 : (lazy ? 2 : 0);
   for (int64_t epoch = 1; epoch <= burnin + maxepoch && nlive > 0; ++epoch) {

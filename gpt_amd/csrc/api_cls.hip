@@ -4,7 +4,6 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <unordered_map>
 #include <vector>
 
 #include "host_util.h"
@@ -115,10 +114,8 @@ extern "C" int gpt_gpnt_sgld_class_chains(const double* phi, const double* y, in
   if (!phi || !y || !eps_theta || !seeds || !theta_store || !status) {
     set_error("gpt_gpnt_sgld_class_chains: null argument"); return GPT_ERR_BAD_DIMS;
   }
-  if (n < 1 || N < 1 || m < 1 || burnin < 0 || maxepoch < 0 || nchains < 1 || store_every < 1 ||
-      n > (1 << 20) || N > (1LL << 31) - 1 || m > (1 << 20) || nchains > 65535 ||
-      store_every > (1 << 30) ||
-      burnin + maxepoch > (1 << 24)) {
+  // m <= 2^20, not 2^31 - 1: the C·m residual and the staged n·m features are sized by m, not min(m, N)
+  if (!theta_chain_dims_ok(n, N, m, burnin, maxepoch, nchains, store_every) || m > (1 << 20)) {
     set_error("bad GPNT_SGLDclass dimensions"); return GPT_ERR_BAD_DIMS;
   }
   if (ncls < 1 || ncls > 32) {
@@ -132,71 +129,27 @@ extern "C" int gpt_gpnt_sgld_class_chains(const double* phi, const double* y, in
   std::vector<int32_t> y0((size_t)N);
   for (int64_t i = 0; i < N; ++i) y0[i] = (int32_t)y[i] - 1;
   const NtcLayout L = ntc_layout((int)n, C, (int)m);
-  if (L.bytes > 160 * 1024) {
+  if (L.bytes > (size_t)kMaxLds) {
     set_error("GPNT_SGLDclass: theta (n x C) and the batch residual exceed 160 KiB of LDS");
     return GPT_ERR_BAD_DIMS;
   }
-  const long long nb = (N + m - 1) / m;
-  const int epochs = (int)(burnin + maxepoch);
-  const long long total = (long long)epochs * nb;
-  const long long kept = total / store_every;
-  const size_t nC = (size_t)n * C;
+  const ThetaRun R(N, m, burnin, maxepoch, store_every);
   for (int k = 0; k < nchains; ++k) status[k] = 0;
-  if (total == 0) return GPT_OK;
-  // epoch orders: one set per distinct seed
-  std::unordered_map<uint64_t, size_t> ord_of;
-  std::vector<size_t> ord_at(nchains);
-  for (int k = 0; k < nchains; ++k) {
-    auto it = ord_of.find(seeds[k]);
-    if (it == ord_of.end()) it = ord_of.emplace(seeds[k], ord_of.size()).first;
-    ord_at[k] = it->second;
-  }
-  const size_t per = (size_t)epochs * N;
-  std::vector<int32_t> ord(per * ord_of.size());
-  for (const auto& kv : ord_of) host_epoch_orders((int)N, kv.first, epochs, ord.data() + per * kv.second);
-  std::vector<double> th0(nC * nchains);
-  for (int k = 0; k < nchains; ++k)
-    for (int c = 0; c < C; ++c)
-      for (int64_t j = 0; j < n; ++j)
-        th0[nC * k + (size_t)n * c + j] =
-            sigma_theta * host_normal(seeds[k], (uint32_t)j, 0, kThetaInit, (uint32_t)c);
-  const size_t nkept = nC * (size_t)kept * nchains;
-  DevMem dphi, dy, dord, dth, dst, dstat, dch;
+  if (R.total == 0) return GPT_OK;
+  ThetaChainSet S;
+  const int rc = S.init(seeds, eps_theta, nchains, n, C, N, R, &sigma_theta, 0);
+  if (rc != GPT_OK) return rc;
+  std::vector<NtcChain> ch(nchains);
+  for (int k = 0; k < nchains; ++k) ch[k] = NtcChain{S.chain(k)};
+  DevMem dphi, dy, dch;
   GPT_HIPCHK(dphi.upload(phi, (size_t)n * N));
   GPT_HIPCHK(dy.upload(y0.data(), y0.size()));
-  GPT_HIPCHK(dord.upload(ord.data(), ord.size()));
-  GPT_HIPCHK(dth.upload(th0.data(), th0.size()));
-  GPT_HIPCHK(dst.alloc<double>(nkept));
-  GPT_HIPCHK(dstat.alloc<int32_t>(nchains));
-  std::vector<NtcChain> ch(nchains);
-  for (int k = 0; k < nchains; ++k) {
-    ch[k].order = dord.as<int32_t>() + per * ord_at[k];
-    ch[k].theta = dth.as<double>() + nC * k;
-    ch[k].store = dst.as<double>() + nC * (size_t)kept * k;
-    ch[k].status = dstat.as<int32_t>() + k;
-    ch[k].seed = seeds[k];
-    ch[k].eps_theta = eps_theta[k];
-  }
   GPT_HIPCHK(dch.upload(ch.data(), ch.size()));
-  GPT_HIPCHK(dstat.zero());
-  GPT_HIPCHK(dst.zero());
-  const int chunk = (int)std::min<long long>(nb, 4096);       // steps per launch, within an epoch
-  ClsTimer tm(0, nullptr);
-  for (int e = 0; e < epochs; ++e)
-    for (long long b0 = 0; b0 < nb; b0 += chunk) {
-      hipError_t er = launch_ntc_chain(dphi.as<double>(), dy.as<int32_t>(), dch.as<NtcChain>(),
-                                       nchains, (int)n, (int)N, C, (int)m, (int)nb, total,
-                                       decay_rate, (int)store_every,
-                                       (long long)e * nb + b0,
-                                       (int)std::min<long long>(chunk, nb - b0), nullptr);
-      if (er != hipSuccess) return hip_fail(er, "ntc_chain kernel");
-    }
-  tm.stop();
-  GPT_HIPCHK(dstat.download(status, nchains));
-  GPT_HIPCHK(dst.download(theta_store, nkept));
-  for (int k = 0; k < nchains; ++k)
-    if (status[k]) std::memset(theta_store + nC * (size_t)kept * k, 0, 8 * nC * (size_t)kept);
-  return GPT_OK;
+  return S.run(R, &g_cls_ms[0], "ntc_chain kernel", [&](long long t0, int nsteps) {
+    return launch_ntc_chain(dphi.as<double>(), dy.as<int32_t>(), dch.as<NtcChain>(), nchains,
+                            (int)n, (int)N, C, (int)m, (int)R.nb, R.total, decay_rate,
+                            (int)store_every, t0, nsteps, L, nullptr);
+  }, theta_store, status);
 }
 
 extern "C" int gpt_gpnt_sgld_class(const double* phi, const double* y, int64_t n, int64_t N,

@@ -160,7 +160,7 @@ bool valid_cfg(const gpt_sgld_config* c) {
                                         c->langevin != 0, c->stiefel != 0);
   const bool wave_ok = wave_supported((int)c->n, (int)c->D, (int)c->r, (int)c->Q, (int)c->m,
                                        c->langevin != 0, c->stiefel != 0);
-  if (L.bytes > 160 * 1024 && !chain_ok && !wave_ok) {
+  if (L.bytes > kMaxLds && !chain_ok && !wave_ok) {
     set_error("working set exceeds 160 KiB LDS (n*r, Q*D or m too large)"); return false;
   }
   return true;

@@ -4,8 +4,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
-#include <unordered_map>
 #include <vector>
 
 #include "host_util.h"
@@ -39,9 +37,7 @@ static int gpnt_rows_cap() {
   return (int)std::min<long>(v, 1 << 30);
 }
 
-struct GpntRun {
-  long long nb, total, kept;
-  int epochs;
+struct GpntRun : ThetaRun {
   GpntLayout L;
 };
 
@@ -53,9 +49,8 @@ static bool gpnt_run_info(const void* data, const double* y, int64_t n, int64_t 
   if (!data || !y || !signal_var || !sigma_theta || !eps_theta || !seeds || !theta_store || !status) {
     set_error("gpt_gpnt_sgld_chains: null argument"); return false;
   }
-  if (n < 1 || N < 1 || m < 1 || burnin < 0 || maxepoch < 0 || nchains < 1 || store_every < 1 ||
-      n > (1 << 20) || N > (1LL << 31) - 1 || m > (1LL << 31) - 1 || nchains > 65535 ||
-      store_every > (1 << 30) || burnin + maxepoch > (1 << 24)) {
+  if (!theta_chain_dims_ok(n, N, m, burnin, maxepoch, nchains, store_every) ||
+      m > (1LL << 31) - 1) {
     set_error("bad GPNT_SGLD_chains dimensions"); return false;
   }
   R->L = gpnt_layout((int)n, (int)N, (int)m, gpnt_rows_cap());
@@ -63,10 +58,7 @@ static bool gpnt_run_info(const void* data, const double* y, int64_t n, int64_t 
     set_error("GPNT_SGLD_chains: theta (n) and the batch's bookkeeping exceed 160 KiB of LDS");
     return false;
   }
-  R->nb = (N + m - 1) / m;
-  R->epochs = (int)(burnin + maxepoch);
-  R->total = (long long)R->epochs * R->nb;
-  R->kept = R->total / store_every;
+  static_cast<ThetaRun&>(*R) = ThetaRun(N, m, burnin, maxepoch, store_every);
   return true;
 }
 
@@ -76,65 +68,22 @@ static int gpnt_chains_core(const double* dphi, const double* y, int64_t n, int6
                             const double* eps_theta, double decay_rate, const uint64_t* seeds,
                             int32_t nchains, int64_t store_every, const GpntRun& R,
                             double* theta_store, int32_t* status) {
-  const int epochs = R.epochs;
-  const long long nb = R.nb, total = R.total, kept = R.kept;
-  // epoch orders: one set per distinct seed
-  std::unordered_map<uint64_t, size_t> ord_of;
-  std::vector<size_t> ord_at(nchains);
-  for (int k = 0; k < nchains; ++k) {
-    auto it = ord_of.find(seeds[k]);
-    if (it == ord_of.end()) it = ord_of.emplace(seeds[k], ord_of.size()).first;
-    ord_at[k] = it->second;
-  }
-  const size_t per = (size_t)epochs * N;
-  std::vector<int32_t> ord(per * ord_of.size());
-  for (const auto& kv : ord_of) host_epoch_orders((int)N, kv.first, epochs, ord.data() + per * kv.second);
-  std::vector<double> th0((size_t)n * nchains);
-  for (int k = 0; k < nchains; ++k)
-    for (int64_t j = 0; j < n; ++j)
-      th0[(size_t)n * k + j] = sigma_theta[k] * host_normal(seeds[k], (uint32_t)j, 0, kThetaInit, 0);
-  const size_t nkept = (size_t)n * (size_t)kept * nchains;
-  DevMem dy, dord, dth, dst, dstat, dch;
-  GPT_HIPCHK(dy.upload(y, (size_t)N));
-  GPT_HIPCHK(dord.upload(ord.data(), ord.size()));
-  GPT_HIPCHK(dth.upload(th0.data(), th0.size()));
-  GPT_HIPCHK(dst.alloc<double>(nkept));
-  GPT_HIPCHK(dstat.alloc<int32_t>(nchains));
+  ThetaChainSet S;
+  const int rc = S.init(seeds, eps_theta, nchains, n, 1, N, R, sigma_theta, 1);
+  if (rc != GPT_OK) return rc;
   std::vector<GpntChain> ch(nchains);
-  for (int k = 0; k < nchains; ++k) {
-    ch[k].order = dord.as<int32_t>() + per * ord_at[k];
-    ch[k].theta = dth.as<double>() + (size_t)n * k;
-    ch[k].store = dst.as<double>() + (size_t)n * (size_t)kept * k;
-    ch[k].status = dstat.as<int32_t>() + k;
-    ch[k].seed = seeds[k];
-    ch[k].eps_theta = eps_theta[k];
-    ch[k].signal_var = signal_var[k];
-    ch[k].sigma_theta = sigma_theta[k];
-  }
+  for (int k = 0; k < nchains; ++k) ch[k] = GpntChain{S.chain(k), signal_var[k], sigma_theta[k]};
+  DevMem dy, dch;
+  GPT_HIPCHK(dy.upload(y, (size_t)N));
   GPT_HIPCHK(dch.upload(ch.data(), ch.size()));
-  GPT_HIPCHK(dstat.zero());
-  GPT_HIPCHK(dst.zero());
   g_gpnt_route[0] = R.L.rows;
   g_gpnt_route[1] = R.L.groups;
   g_gpnt_route[2] = (int32_t)R.L.bytes;
-  const int chunk = (int)std::min<long long>(nb, 4096);       // steps per launch, within an epoch
-  {
-    EventTimer tm(&g_gpnt_ms[0], nullptr);
-    for (int e = 0; e < epochs; ++e)
-      for (long long b0 = 0; b0 < nb; b0 += chunk) {
-        hipError_t er = launch_gpnt_chain(dphi, dy.as<double>(), dch.as<GpntChain>(), nchains,
-                                          (int)n, (int)N, (int)m, (int)nb, total, decay_rate,
-                                          (int)store_every, (long long)e * nb + b0,
-                                          (int)std::min<long long>(chunk, nb - b0), R.L, nullptr);
-        if (er != hipSuccess) return hip_fail(er, "gpnt_chain kernel");
-      }
-    tm.stop();
-    GPT_HIPCHK(dstat.download(status, nchains));
-  }
-  GPT_HIPCHK(dst.download(theta_store, nkept));
-  for (int k = 0; k < nchains; ++k)                            // GPT_SGLD.jl:840-843
-    if (status[k]) std::memset(theta_store + (size_t)n * (size_t)kept * k, 0, 8 * (size_t)n * (size_t)kept);
-  return GPT_OK;
+  return S.run(R, &g_gpnt_ms[0], "gpnt_chain kernel", [&](long long t0, int nsteps) {
+    return launch_gpnt_chain(dphi, dy.as<double>(), dch.as<GpntChain>(), nchains, (int)n, (int)N,
+                             (int)m, (int)R.nb, R.total, decay_rate, (int)store_every, t0, nsteps,
+                             R.L, nullptr);
+  }, theta_store, status);
 }
 
 extern "C" int gpt_gpnt_sgld_chains(const double* phi, const double* y, int64_t n, int64_t N,

@@ -72,7 +72,7 @@ bool gpt::valid_pred(int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q) 
   if (n < 1 || D < 1 || Ntest < 0 || r < 1 || Q < 1) { set_error("bad pred dims"); return false; }
   if (D > kDMax) { set_error("D > 16 unsupported"); return false; }
   if (!rank_supported((int)r)) { set_error("rank not instantiated"); return false; }
-  if (pred_lds_bytes((int)n, (int)D, (int)r, (int)Q) > 160 * 1024) { set_error("pred LDS too large"); return false; }
+  if (pred_lds_bytes((int)n, (int)D, (int)r, (int)Q) > kMaxLds) { set_error("pred LDS too large"); return false; }
   return true;
 }
 
@@ -180,7 +180,7 @@ int gpt::pred_store_fhat_x(const double* w_store, const double* U_store, const i
     set_error("dimensions of X and length_scale do not match"); return GPT_ERR_BAD_DIMS;
   }
   if (!valid_pred(n, D, Ntest, r, Q)) return GPT_ERR_BAD_DIMS;
-  if (pred_x_lds_bytes((int)n, (int)D, (int)r, (int)Q) > 160 * 1024) {
+  if (pred_x_lds_bytes((int)n, (int)D, (int)r, (int)Q) > kMaxLds) {
     set_error("pred LDS too large"); return GPT_ERR_BAD_DIMS;
   }
   std::vector<int32_t> I0;

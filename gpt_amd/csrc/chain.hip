@@ -1023,7 +1023,7 @@ bool chain_supported(int n, int D, int r, int Q, int m, bool langevin, bool stie
   if (Q > kChainQP || m > kChainMMax) return false;   // the fixed LDS carve's maxima
   const int NT = (Q + 63) / 64 * kChainG;
   if (NT > ((chain_J(n) >= 8 && D > 4) ? kChainTPW8 : kChainTasks) * D) return false;
-  return chain_lds_bytes(n, D, r, Q, m) + chain_static_lds(chain_J(n), chain_wv(D)) <= 160 * 1024;
+  return chain_lds_bytes(n, D, r, Q, m) + chain_static_lds(chain_J(n), chain_wv(D)) <= kMaxLds;
 }
 
 hipError_t launch_chain(const StepParams& P, const ChainDesc* chains, int nchains,

@@ -16,7 +16,7 @@
 
 namespace gpt {
 
-constexpr size_t kCjLds = 160 * 1024;
+constexpr size_t kCjLds = kMaxLds;
 
 // LDS of cjoint_eval_kernel.  Fixed part: the scores / residual of the tile sr[ii][CC], the tile's
 // rows of X padded to 16 (X[ii][16]), 1/ℓ (16) and the workgroup sum's scratch.  Then the tile:

@@ -4,7 +4,7 @@
 // per sample and on the scores averaged over a window of samples (ImageExperiment.jl:50-72,
 // ImageNoTensorExperiment.jl:50-75).  Everything is fp64; exp and log are the device library's.
 #include "gpt_internal.h"
-#include "device_util.h"
+#include "theta_chain.h"
 
 namespace gpt {
 
@@ -23,7 +23,7 @@ NtcLayout ntc_layout(int n, int C, int m) {
   L.o_phi = o;
   L.base = o;
   const size_t staged = al16(o + 8 * (size_t)n * m);
-  L.stage = staged <= 160 * 1024 ? 1 : 0;
+  L.stage = staged <= (size_t)kMaxLds ? 1 : 0;
   L.bytes = L.stage ? staged : o;
   return L;
 }
@@ -42,8 +42,7 @@ __global__ __launch_bounds__(kNT) void ntc_chain_kernel(
     double decay_rate, int store_every, long long t0, int nsteps, NtcLayout L) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const NtcChain ch = chains[blockIdx.x];
-  if (t0 >= total) return;
-  if (__hip_atomic_load(ch.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+  if (theta_chain_done(t0, total, ch.status)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = uni(tid >> 6);
   double* theta_l = (double*)(smem + L.o_theta);
   int* idx_l = (int*)(smem + L.o_idx);
@@ -56,16 +55,10 @@ __global__ __launch_bounds__(kNT) void ntc_chain_kernel(
   const int NP = ((n + 63) / 64) * 64;
   const long long tend = min(total, t0 + (long long)nsteps);
   for (long long t = t0; t < tend; ++t) {
-    const int ep = (int)(t / nb), b = (int)(t - (long long)ep * nb);
-    const int start = b * m;
-    const int Bt = min(m, N - start);
-    const int32_t* ord = ch.order + (size_t)ep * N + start;
+    const int32_t* ord;
+    const int Bt = theta_batch(ch.order, t, nb, m, N, &ord);
     __syncthreads();                          // theta_l loaded / the step before is finished
-    for (int i = tid; i < Bt; i += kNT) {
-      const int row = min(max(ord[i], 0), N - 1);
-      idx_l[i] = row;
-      yb_l[i] = y0[row];
-    }
+    gather_batch(ord, Bt, N, y0, idx_l, yb_l);
     __syncthreads();
     for (int i = wv; i < Bt; i += kNW) {
       const double* col = phi + (long long)uni(idx_l[i]) * n;
@@ -95,11 +88,9 @@ __global__ __launch_bounds__(kNT) void ntc_chain_kernel(
         if (c < C && lane == c) P_l[c * m + i] = exp(acc[c] - lse) - (c == yi ? 1.0 : 0.0);
     }
     __syncthreads();
-    const double eps = ch.eps_theta * pow((double)(t + 1), -decay_rate);
-    const double sq = sqrt(eps);
-    const double cN = (double)N / (double)Bt;
-    const bool keep = ((t + 1) % store_every) == 0;
-    double* out = keep ? ch.store + (size_t)((t + 1) / store_every - 1) * n * C : nullptr;
+    const ThetaStepSize S = theta_step_size(ch.eps_theta, t, decay_rate, N, Bt);
+    const double eps = S.eps, sq = S.sq, cN = S.cN;
+    double* out = theta_store_slot(ch.store, t, store_every, (size_t)n * C);
     bool bad = false;
     for (int e = tid; e < NP * C; e += kNT) {
       const int c = e / NP, j = e - c * NP;   // c is uniform over a wave: P_l is read by broadcast
@@ -119,19 +110,7 @@ __global__ __launch_bounds__(kNT) void ntc_chain_kernel(
       if (out) out[c * n + j] = nt;
       bad |= (nt != nt);
     }
-    // the whole workgroup leaves together: a flag per wave in dynamic LDS (no static LDS, so the
-    // kernel's dynamic limit can be the full 160 KB)
-    const int wbad = __ballot(bad) != 0 ? 1 : 0;
-    if (lane == 0) flag_l[wv] = wbad;
-    __syncthreads();
-    int any = 0;
-#pragma unroll
-    for (int w2 = 0; w2 < kNW; ++w2) any |= flag_l[w2];
-    if (any) {
-      if (tid == 0)
-        __hip_atomic_store(ch.status, GPT_ERR_NAN_THETA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
+    if (theta_chain_nan(bad, flag_l, ch.status)) return;
   }
   __syncthreads();
   for (int e = tid; e < n * C; e += kNT) ch.theta[e] = theta_l[e];
@@ -140,9 +119,8 @@ __global__ __launch_bounds__(kNT) void ntc_chain_kernel(
 hipError_t launch_ntc_chain(const double* phi, const int32_t* y0, const NtcChain* chains,
                             int nchains, int n, int N, int C, int m, int nb, long long total,
                             double decay_rate, int store_every, long long t0, int nsteps,
-                            hipStream_t st) {
-  const NtcLayout L = ntc_layout(n, C, m);
-  if (C < 1 || C > 32 || L.bytes > 160 * 1024 || nchains < 1 || store_every < 1)
+                            const NtcLayout& L, hipStream_t st) {
+  if (C < 1 || C > 32 || L.bytes > (size_t)kMaxLds || nchains < 1 || store_every < 1)
     return hipErrorInvalidValue;
   const int cc = contains(IntList<2, 4, 8, 16>{}, L.CC) ? L.CC : 32;    // C rounded up
   return with_value(IntList<2, 4, 8, 16, 32>{}, cc, [&](auto CC) {

@@ -115,7 +115,7 @@ GPT_HD StepLayout step_layout(int n, int D, int r, int Q, int m) {
   const size_t un_v = 8 * (size_t)D * r * L.MP;
   const size_t un_g = 2 * nrp + red;
   size_t un = un_v > un_g ? un_v : un_g;
-  const size_t cap = 160 * 1024;
+  const size_t cap = kMaxLds;
   // Preferred: expm scratch after red with U_l kept (old U stays in LDS for tmpU), both expm
   // concurrent.  Fallbacks alias the scratch over U_l/red, then run the two expm in turn.
   if (al16(o + (un > 2 * nrp + red + x0 + x1 ? un : 2 * nrp + red + x0 + x1)) <= cap) {
@@ -351,15 +351,18 @@ hipError_t launch_gpnt(const double* phi, const double* y, const int32_t* order,
                        double* theta_store, int32_t* status, const long long* tbase, int t_local,
                        hipStream_t st);
 
-// Sibling GPNT_SGLD chains (gpnt.hip): one workgroup per chain, theta in LDS for a launch of up
-// to one epoch's steps.
-struct GpntChain {
+// One chain of the full-theta samplers (gpnt.hip, cls.hip; their frame is theta_chain.h): one
+// workgroup per chain, theta (len = n doubles, n*C for the classifier) in LDS for a launch.
+struct ThetaChain {
   const int32_t* order;  // epochs*N cumulative epoch orders of the chain's seed (0-based rows)
-  double* theta;         // n       current theta
-  double* store;         // n*kept
+  double* theta;         // len       current theta
+  double* store;         // len*kept
   int32_t* status;       // 0 ok, GPT_ERR_NAN_THETA
   uint64_t seed;
-  double eps_theta, signal_var, sigma_theta;
+  double eps_theta;
+};
+struct GpntChain : ThetaChain {   // sibling GPNT_SGLD chains (gpnt.hip)
+  double signal_var, sigma_theta;
 };
 struct GpntLayout {
   int rows, groups;      // rows: feature rows staged per group (0: none); groups per full batch
@@ -372,16 +375,8 @@ hipError_t launch_gpnt_chain(const double* phi, const double* y, const GpntChain
                              double decay_rate, int store_every, long long t0, int nsteps,
                              const GpntLayout& L, hipStream_t st);
 
-// Classification (cls.hip).  GPNT_SGLDclass: one workgroup per chain, theta (n x C) in LDS for a
-// launch of up to one epoch's steps.
-struct NtcChain {
-  const int32_t* order;  // epochs*N cumulative epoch orders of the chain's seed (0-based rows)
-  double* theta;         // n*C     current theta
-  double* store;         // n*C*kept
-  int32_t* status;       // 0 ok, GPT_ERR_NAN_THETA
-  uint64_t seed;
-  double eps_theta;
-};
+// Classification (cls.hip).  GPNT_SGLDclass: a ThetaChain with theta (n x C).
+struct NtcChain : ThetaChain {};
 struct NtcLayout {
   int CC, stage;         // CC: C rounded up to 2, 4, 8, 16, 32; stage: the batch's phi is in LDS
   size_t o_theta, o_idx, o_yb, o_P, o_flag, o_phi, base, bytes;   // base: bytes without the staged phi
@@ -391,7 +386,7 @@ NtcLayout ntc_layout(int n, int C, int m);
 hipError_t launch_ntc_chain(const double* phi, const int32_t* y0, const NtcChain* chains,
                             int nchains, int n, int N, int C, int m, int nb, long long total,
                             double decay_rate, int store_every, long long t0, int nsteps,
-                            hipStream_t st);
+                            const NtcLayout& L, hipStream_t st);
 // scores (Ntest, S) = phitestᵀ (n, Ntest) · theta (n, S)
 hipError_t launch_nt_scores(const double* phitest, const double* theta, int n, long long Ntest,
                             long long S, double* scores, hipStream_t st);

@@ -1,6 +1,8 @@
 // Host-only helpers of the libgptsgld translation units: the HIP error check, the owners of device
 // allocations and the argument idioms the C entries share.  No device code.
 #pragma once
+#include <algorithm>
+#include <cstring>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -120,6 +122,84 @@ struct EventTimer {
       *ms = t;
     if (a) (void)hipEventDestroy(a);
     if (b) (void)hipEventDestroy(b);
+  }
+};
+
+// ---- sibling full-theta chains (gpt_gpnt_sgld_chains*, gpt_gpnt_sgld_class_chains) -------------
+// The bounds the two entries share; each adds its own bound on m and its own message.
+inline bool theta_chain_dims_ok(int64_t n, int64_t N, int64_t m, int64_t burnin, int64_t maxepoch,
+                                int32_t nchains, int64_t store_every) {
+  return n >= 1 && N >= 1 && m >= 1 && burnin >= 0 && maxepoch >= 0 && nchains >= 1 &&
+         store_every >= 1 && n <= (1 << 20) && N <= (1LL << 31) - 1 && nchains <= 65535 &&
+         store_every <= (1 << 30) && burnin + maxepoch <= (1 << 24);
+}
+// A run's step counts: nb batches per epoch, total steps, of which kept are stored.
+struct ThetaRun {
+  int epochs = 0;
+  long long nb = 0, total = 0, kept = 0;
+  ThetaRun() = default;
+  ThetaRun(int64_t N, int64_t m, int64_t burnin, int64_t maxepoch, int64_t store_every)
+      : epochs((int)(burnin + maxepoch)), nb((N + m - 1) / m), total(epochs * nb),
+        kept(total / store_every) {}
+};
+// The device state of nchains sibling chains whose theta has len = n·C doubles, and the launch
+// loop over it.  An entry builds its descriptors on chain(k) and gives run() its kernel launch.
+struct ThetaChainSet {
+  DevMem ord, theta, store, status;
+  std::vector<size_t> ord_at;     // chain k's epoch orders start at ord + ord_at[k]
+  const uint64_t* seeds;
+  const double* eps_theta;
+  size_t nchains, len, kept;
+  // Epoch orders, one set per distinct seed; theta0[:, c] of chain k =
+  // sigma_theta[k·sigma_stride]·normals(n, seeds[k], 0, THETA_INIT, c); a zeroed store and status.
+  int init(const uint64_t* seeds_, const double* eps_theta_, int nchains_, int64_t n, int C,
+           int64_t N, const ThetaRun& R, const double* sigma_theta, int sigma_stride) {
+    seeds = seeds_; eps_theta = eps_theta_; nchains = nchains_; len = (size_t)n * C; kept = R.kept;
+    std::unordered_map<uint64_t, size_t> ord_of;
+    const size_t per = (size_t)R.epochs * N;
+    for (size_t k = 0; k < nchains; ++k)
+      ord_at.push_back(per * ord_of.emplace(seeds[k], ord_of.size()).first->second);
+    std::vector<int32_t> o(per * ord_of.size());
+    for (const auto& kv : ord_of) host_epoch_orders((int)N, kv.first, R.epochs, o.data() + per * kv.second);
+    std::vector<double> th0(len * nchains);
+    for (size_t k = 0; k < nchains; ++k)
+      for (int c = 0; c < C; ++c)
+        for (int64_t j = 0; j < n; ++j)
+          th0[len * k + (size_t)n * c + j] = sigma_theta[k * sigma_stride] *
+              host_normal(seeds[k], (uint32_t)j, 0, kThetaInit, (uint32_t)c);
+    GPT_HIPCHK(ord.upload(o.data(), o.size()));
+    GPT_HIPCHK(theta.upload(th0.data(), th0.size()));
+    GPT_HIPCHK(store.alloc<double>(len * kept * nchains));
+    GPT_HIPCHK(status.alloc<int32_t>(nchains));
+    GPT_HIPCHK(status.zero());
+    GPT_HIPCHK(store.zero());
+    return GPT_OK;
+  }
+  ThetaChain chain(int k) const {
+    return {ord.as<int32_t>() + ord_at[k], theta.as<double>() + len * k,
+            store.as<double>() + len * kept * k, status.as<int32_t>() + k, seeds[k], eps_theta[k]};
+  }
+  // launch(t0, nsteps) for every epoch in chunks of at most 4096 steps, timed into *ms by device
+  // events around the launches; then the status and the store come back, the store of a chain
+  // that met a NaN zero-filled (GPT_SGLD.jl:840-843 / :894-897).
+  template <class Launch>
+  int run(const ThetaRun& R, double* ms, const char* what, Launch&& launch, double* theta_store,
+          int32_t* status_out) const {
+    const int chunk = (int)std::min<long long>(R.nb, 4096);    // steps per launch, within an epoch
+    {
+      EventTimer tm(ms, nullptr);
+      for (int e = 0; e < R.epochs; ++e)
+        for (long long b0 = 0; b0 < R.nb; b0 += chunk) {
+          const hipError_t er = launch(e * R.nb + b0, (int)std::min<long long>(chunk, R.nb - b0));
+          if (er != hipSuccess) return hip_fail(er, what);
+        }
+      tm.stop();
+      GPT_HIPCHK(status.download(status_out, nchains));
+    }
+    GPT_HIPCHK(store.download(theta_store, len * kept * nchains));
+    for (size_t k = 0; k < nchains; ++k)
+      if (status_out[k]) std::memset(theta_store + len * kept * k, 0, 8 * len * kept);
+    return GPT_OK;
   }
 };
 

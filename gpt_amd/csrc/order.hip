@@ -24,7 +24,7 @@
 namespace gpt {
 
 constexpr int kOrdNT = 1024;
-constexpr int kOrdLdsMax = 160 * 1024 - 256;       // dynamic LDS beside the kernel's static words
+constexpr int kOrdLdsMax = kMaxLds - 256;       // dynamic LDS beside the kernel's static words
 constexpr int kOrdLdsRows = kOrdLdsMax / 12;
 
 template <bool LDS>

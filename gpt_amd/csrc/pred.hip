@@ -619,7 +619,7 @@ static hipError_t launch_rows_pf(const double* w, const double* T, const int32_t
   if (e != hipSuccess) return e;
   const size_t lds = 8 * (size_t)D * r * 64 + 8 * (size_t)NW * 64 + 4 * (((size_t)Q * D + 3) & ~3) +
                      8 * (size_t)Q;
-  const long long per_cu = std::max<long long>(1, (long long)(160 * 1024) / (long long)lds);
+  const long long per_cu = std::max<long long>(1, (long long)kMaxLds / (long long)lds);
   const long long ntiles = (Ntest + 63) / 64 * (long long)Sc;
   const unsigned grid = (unsigned)std::min<long long>(ntiles, per_cu * cus);
   g_pred_route.tdim = DD;
@@ -636,7 +636,7 @@ static hipError_t launch_vphase_rows(const double* w, const double* T, const int
   // the sample's w — a large core (Q·D) can push it past one CU's 160 KB)
   const size_t pf_lds = 8 * (size_t)D * r * 64 + 8 * (size_t)kRowsPfWaves * 64 +
                         4 * (((size_t)Q * D + 3) & ~(size_t)3) + 8 * (size_t)Q;
-  if (D * r <= kRowsPfWaves * 16 && pf_lds <= 160 * 1024) {
+  if (D * r <= kRowsPfWaves * 16 && pf_lds <= kMaxLds) {
     // rows per wave: 10 (D·r ≤ 160: kin40kExperiment.jl's D = 8, r = 20) or 16
     // (DD = D where the kernel is instantiated for that D, else its run-time-D form DD = 0)
     if (D * r <= kRowsPfWaves * 10) {

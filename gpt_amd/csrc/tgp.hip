@@ -853,7 +853,7 @@ static size_t gmc_geod_lds(int n, int r) {
 }
 
 bool gmc_supported(int n, int r) {
-  return gmc_geod_lds(n, r) <= 160 * 1024 && gmc_kick_lds(n, r) <= 160 * 1024;
+  return gmc_geod_lds(n, r) <= kMaxLds && gmc_kick_lds(n, r) <= kMaxLds;
 }
 
 static hipError_t launch_gmc_kick(const double* U, double* mom, const double* gU, double c, int n,

@@ -1102,7 +1102,7 @@ bool wave_supported(int n, int D, int r, int Q, int m, bool langevin, bool stief
   if (!contains(WaveRanks{}, r) || wv_J(n) == 0 || m > kWvMaxM || D < 1 || D > kDMax) return false;
   if (3 * r * r > n * r) return false;            // expm(−tA)'s scratch below the Grams
   if ((long long)D * r * m >= 65536 || Q >= 65536) return false;   // 16-bit V-phase tables
-  return wv_vphase_lds_bytes(D, r, Q, m) <= 160 * 1024 && wv_dim_lds_bytes(n, r, m) <= 160 * 1024;
+  return wv_vphase_lds_bytes(D, r, Q, m) <= kMaxLds && wv_dim_lds_bytes(n, r, m) <= kMaxLds;
 }
 
 // D·Q members of every run (core entries q with I[q,k] = l, in q order, runs in l order), then
@@ -1200,7 +1200,7 @@ static hipError_t expm_check_launch(int count, const double* A, double* E, int32
   // wave_expm's scratch is seven NN² blocks, wv_expm's the three slots geod gives it
   const size_t lds = 8 * (size_t)(MODE == 1 || MODE == 3 || MODE == 5 ? 7 : 3) * NN * NN;
   hipError_t e = hipFuncSetAttribute((const void*)wv_expm_check_kernel<NN, MODE>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((wv_expm_check_kernel<NN, MODE>), dim3(count), dim3(64), lds, st, A, E, bad,
                      stamps);

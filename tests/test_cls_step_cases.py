@@ -67,8 +67,9 @@ def test_fixture_equals_mpmath():
 
 
 def test_layout_restatement_is_the_kernels():
-    """The formula is cls.hip's, term for term; kNW and the 160 KiB and 4096-step limits are the
-    sources'; and it agrees with the restatement tests/ctheta_cases.py already holds."""
+    """The formula is cls.hip's, term for term; kNW and the 160 KiB (kMaxLds) and 4096-step limits
+    (the launch loop the full-theta chains share, host_util.h) are the sources'; and it agrees with
+    the restatement tests/ctheta_cases.py already holds."""
     src = source("cls.hip")
     for line in ("L.CC = C <= 2 ? 2 : (C <= 4 ? 4 : (C <= 8 ? 8 : (C <= 16 ? 16 : 32)));",
                  "L.o_theta = o; o = al16(o + 8 * (size_t)n * L.CC);",
@@ -77,14 +78,16 @@ def test_layout_restatement_is_the_kernels():
                  "L.o_P = o;     o = al16(o + 8 * (size_t)C * m);",
                  "L.o_flag = o;  o = al16(o + 4 * (size_t)kNW);",
                  "const size_t staged = al16(o + 8 * (size_t)n * m);",
-                 "L.stage = staged <= 160 * 1024 ? 1 : 0;",
+                 "L.stage = staged <= (size_t)kMaxLds ? 1 : 0;",
                  "L.bytes = L.stage ? staged : o;"):
         assert line in src, line
     hdr = source("gpt_internal.h")
     nt = int(re.search(r"#define GPT_NT (\d+)", hdr).group(1))
     assert nt // WAVE == T.NW
-    assert "std::min<long long>(nb, %d)" % T.LAUNCH_STEPS in source("api_cls.hip")
-    assert "L.bytes > 160 * 1024" in source("api_cls.hip") and T.LDS == 160 * 1024
+    assert "std::min<long long>(R.nb, %d)" % T.LAUNCH_STEPS in source("host_util.h")
+    assert "S.run(R, " in source("api_cls.hip")
+    assert "constexpr int kMaxLds = 160 * 1024;" in source("launch_util.h")
+    assert "L.bytes > (size_t)kMaxLds" in source("api_cls.hip") and T.LDS == 160 * 1024
     for c in T.CASES:
         L = layout(c)
         assert {k: L[k] for k in ("CC", "stage", "bytes")} == ctheta_cases.ntc_layout(c.n, c.C, c.m)

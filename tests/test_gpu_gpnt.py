@@ -130,6 +130,29 @@ def test_chains_are_independent_and_store_every_thins():
     assert np.array_equal(some, store[:, 3::4, :][:, :total // 4, :])
 
 
+def test_an_epoch_of_two_launches():
+    """nb = 4100 batches of one row: the epoch takes launches of 4096 and 4 steps, so theta goes to
+    HBM and comes back and the second launch starts mid-epoch.  With m = 1 the step is contractive
+    while eps·N/(2·signal_var) is well below 1 (0.041 here); the oracle's max|theta| is 2.63 and a
+    relative 1e-15 perturbation of phi moves its result by 1.0e-15, so the 1e-9 bar of
+    test_chains_match_the_oracle holds over the 4100 steps too."""
+    n, N, m, decay, sv, sth, eps = 64, 4100, 1, 0.1, 0.05, 1.0, 1e-6
+    seeds = [5, 2 ** 40 + 9]
+    phi, y = GR.inputs("D", N=N)
+    chains = lambda s, **kw: G().GPNT_SGLD_chains(phi, y, sv, sth, m, eps, decay, 0, 1, s, **kw)
+    store, status = chains(seeds)
+    assert not status.any() and store.shape == (n, N, 2)
+    for k, seed in enumerate(seeds):
+        r = GR.rel(store[:, :, k], R.GPNT_SGLD(phi, y, sv, sth, m, eps, decay, 0, 1, seed))
+        print("4100 steps, chain %d: rel = %.3g" % (k, r))
+        assert r < 1e-9, (k, r)
+        one, st = chains([seed])
+        assert not st.any() and np.array_equal(one[:, :, 0], store[:, :, k]), k
+    last, status = chains(seeds, store_every=N)
+    assert not status.any() and last.shape == (n, 1, 2)
+    assert np.array_equal(last[:, 0, :], store[:, -1, :])
+
+
 def test_nan_chain_is_zero_filled_and_leaves_its_siblings():
     from gpt_amd import _lib
     eps = [GR.EPS[0], 1e300, GR.EPS[2]]
