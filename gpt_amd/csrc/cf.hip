@@ -1399,7 +1399,7 @@ size_t cf_lazy_lds_bytes(int r, int m, int nfeat, int rows, int nb) {
 }
 
 hipError_t launch_cf_epoch(const CfParams& P, const CfChain* chains, int nchains, long long step0,
-                           int bt0, int nb, int domove, hipStream_t st,
+                           int bt0, int nb, CfMode domove, hipStream_t st,
                            const long long* step_base) {
   size_t lds = cf_lds_bytes(P.r, P.m, P.D1 + P.D2, P.D1 <= 64 && P.D2 <= 64);
   if (domove == 2)

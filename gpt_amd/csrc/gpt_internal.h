@@ -299,10 +299,16 @@ struct CfChain {
   int32_t* status;
 };
 
+// How an SGD / SGLD epoch is launched (cf_epoch_kernel's domove; gpt_cf_last_mode reports it):
+//   kCfStepPairs     per minibatch a batch-phase launch and a row-parallel cf_move_kernel launch
+//   kCfStiefelEpoch  one launch per epoch, the Stiefel move of every row inside it
+//   kCfLazyEpoch     one launch per epoch, the lazy SGD move (rows outside a batch only decay)
+enum CfMode { kCfStepPairs = 0, kCfStiefelEpoch = 1, kCfLazyEpoch = 2 };
+
 size_t cf_lds_bytes(int r, int m, int nfeat, bool masks);
 size_t cf_lazy_lds_bytes(int r, int m, int nfeat, int rows, int nb);
 hipError_t launch_cf_epoch(const CfParams& P, const CfChain* chains, int nchains, long long step0,
-                           int bt0, int nb, int domove, hipStream_t st,
+                           int bt0, int nb, CfMode domove, hipStream_t st,
                            const long long* step_base = nullptr);
 hipError_t launch_cf_gather(const CfChain* chains, int nchains, int N, hipStream_t st);
 hipError_t launch_cf_move(const CfParams& P, const CfChain* chains, int nchains, long long step,

@@ -1,32 +1,17 @@
 """MovieLens-100k tensor collaborative filtering (100k_movielensExperiment.jl, §8(f) item 1 /
 BASELINE config 5) on libgptsgld.so.
 
-    GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w,
-                       w_init, m, epsw, epsU, a, b, c, burnin, maxepoch, param_seed,
-                       ytrainMean, ytrainStd; langevin=False, stiefel=False, avg=False)
-                                                             100k_movielensExperiment.jl:409-551
-                       (the four SGD entries also take U_init=, V_init=: the initial U and V in
-                       place of the Philox draw, for the tests' injected state)
-    GPT_fullw_gibbs(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w,
-                    w_init, burnin, maxepoch, n_samples, param_seed, ytrainMean, ytrainStd;
-                    avg=False, rotated_w=False)              100k_movielensExperiment.jl:1032-1129
-    GPT_fullw_sideinfo_folds(Ratings, UserData, MovieData, Ratingtests, ..., ytrainMeans,
-                             ytrainStds; ...)   the folds loop of :733-736 as one device launch
-                                                per epoch (a list of per-fold result tuples)
-    GPT_fixw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m, epsU,
-                      a, b, c, burnin, maxepoch, param_seed, ytrainMean, ytrainStd;
-                      langevin, stiefel, avg)                  :282-404
-    GPT_fullw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w, w_init, m,
-              epsw, epsU, burnin, maxepoch, param_seed, ytrainMean, ytrainStd;
-              langevin, stiefel, avg)                          :160-279
-    GPT_fixw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m, epsU, burnin,
-             maxepoch, param_seed, ytrainMean, ytrainStd; langevin, stiefel, avg)     :56-156
-    GPT_fixw_gibbs(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, burnin,
-                   maxepoch, n_samples, param_seed, ytrainMean, ytrainStd; avg, rotated_w)
-                                                             :945-1028
+    GPT_fullw_sideinfo        :409-551   SGD / SGLD, side information (the four SGD entries also
+    GPT_fixw_sideinfo         :282-404   take U_init=, V_init=: the initial U and V in place of the
+    GPT_fullw                 :160-279   Philox draw, for the tests' injected state)
+    GPT_fixw                  :56-156
+    GPT_fullw_gibbs           :1032-1129
+    GPT_fixw_gibbs            :945-1028
+    GPT_fullw_sideinfo_folds  :733-736   the folds loop as one device launch per epoch (a list of
+                                         per-fold result tuples)
     fold(data, i)     the standardised u{i}.base / u{i}.test split of :566-576
 
-Same argument meaning and return tuple as the reference: (w_store, U_store, V_store,
+Same arguments (the signatures below) and return tuple as the reference: (w_store, U_store, V_store,
 testpred_store, trainRMSEvec, testRMSEvec), without w_store for the fixed-w variants.  ``data`` is the mapping written by
 scripts/make_ml100k_fixture.py (ratings per fold, the processed UserData / MovieData of
 :578-584).  Randomness follows the framework's Philox contract (oracle/movielens_ref.py).
@@ -75,74 +60,11 @@ def fold(data, i):
             np.asarray(data["movie_data"], dtype=np.float64), mu, sd)
 
 
-def GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w,
-                       w_init, m, epsw, epsU, a, b, c, burnin, maxepoch, param_seed, ytrainMean,
-                       ytrainStd, langevin=False, stiefel=False, avg=False, U_init=None, V_init=None):
-    """U_init / V_init (tests): the initial U and V in place of the Philox draw."""
-    Rt = _f64(Rating)
-    Rs = _f64(Ratingtest)
-    Ud = _f64(UserData)
-    Md = _f64(MovieData)
-    w0 = _f64(w_init)
-    N, Ntest = Rt.shape[0], Rs.shape[0]
-    n1, D1 = Ud.shape
-    n2, D2 = Md.shape
-    r = w0.shape[0]
-    if Rt.shape[1] < 3 or Rs.shape[1] < 3 or w0.shape != (r, r):
-        raise ValueError("Rating / Ratingtest need (user, movie, rating) columns; w_init is r x r")
-    w_store = np.zeros((r, r, maxepoch), order="F")
-    U_store = np.zeros((n1 + D1, r, maxepoch), order="F")
-    V_store = np.zeros((n2 + D2, r, maxepoch), order="F")
-    tps = np.zeros((Ntest, maxepoch), order="F")
-    trm = np.zeros(maxepoch)
-    tsm = np.zeros(maxepoch)
-    _inject(U_init, V_init)
-    code = lib().gpt_cf_fullw_sideinfo(
-        _ptr(Rt), N, N, _ptr(Ud), n1, D1, _ptr(Md), n2, D2, _ptr(Rs), Ntest, Ntest,
-        float(signal_var), float(sigma_u), float(sigma_w), _ptr(w0), r, int(m), float(epsw),
-        float(epsU), float(a), float(b), float(c), int(burnin), int(maxepoch),
-        int(param_seed) & (2 ** 64 - 1), float(ytrainMean), float(ytrainStd), int(bool(langevin)),
-        int(bool(stiefel)), int(bool(avg)), _ptr(w_store), _ptr(U_store), _ptr(V_store),
-        _ptr(tps), _ptr(trm), _ptr(tsm))
-    if code == _lib.GPT_ERR_NAN_GEODESIC:
-        print("Get NaN when moving along Geodesic. Try smaller epsU")
-    else:
-        check(code)
-    return w_store, U_store, V_store, tps, trm, tsm
-
-
-def GPT_fullw_gibbs(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w, w_init,
-                    burnin, maxepoch, n_samples, param_seed, ytrainMean, ytrainStd, avg=False,
-                    rotated_w=False):
-    Rt = _f64(Rating)
-    Rs = _f64(Ratingtest)
-    w0 = _f64(w_init)
-    N, Ntest = Rt.shape[0], Rs.shape[0]
-    n1, n2 = np.shape(UserData)[0], np.shape(MovieData)[0]
-    r = w0.shape[0]
-    w_store = np.zeros((r, r, maxepoch), order="F")
-    U_store = np.zeros((n1, r, maxepoch), order="F")
-    V_store = np.zeros((n2, r, maxepoch), order="F")
-    tps = np.zeros((Ntest, maxepoch), order="F")
-    trm = np.zeros(maxepoch)
-    tsm = np.zeros(maxepoch)
-    check(lib().gpt_cf_fullw_gibbs(
-        _ptr(Rt), N, N, n1, n2, _ptr(Rs), Ntest, Ntest, float(signal_var), float(sigma_u),
-        float(sigma_w), _ptr(w0), r, int(burnin), int(maxepoch), int(n_samples),
-        int(param_seed) & (2 ** 64 - 1), float(ytrainMean), float(ytrainStd), int(bool(avg)),
-        int(bool(rotated_w)), _ptr(w_store), _ptr(U_store), _ptr(V_store), _ptr(tps), _ptr(trm),
-        _ptr(tsm)))
-    return w_store, U_store, V_store, tps, trm, tsm
-
-
-def _sgd_common(Rating, Ratingtest, w, maxepoch):
-    Rt, Rs, w0 = _f64(Rating), _f64(Ratingtest), _f64(w)
-    r = w0.shape[0]
-    if Rt.shape[1] < 3 or Rs.shape[1] < 3 or w0.shape != (r, r):
-        raise ValueError("Rating / Ratingtest need (user, movie, rating) columns; w is r x r")
-    Ntest = Rs.shape[0]
-    return (Rt, Rs, w0, r, np.zeros((Ntest, maxepoch), order="F"), np.zeros(maxepoch),
-            np.zeros(maxepoch))
+def _stores(r, rowsU, rowsV, Ntest, maxepoch, fixw=False):
+    """The zeroed outputs of one fold (no w_store for the fixed-w variants)."""
+    outs = [] if fixw else [np.zeros((r, r, maxepoch), order="F")]
+    return outs + [np.zeros((rowsU, r, maxepoch), order="F"), np.zeros((rowsV, r, maxepoch), order="F"),
+                   np.zeros((Ntest, maxepoch), order="F"), np.zeros(maxepoch), np.zeros(maxepoch)]
 
 
 def _nan_or_check(code):
@@ -152,26 +74,63 @@ def _nan_or_check(code):
         check(code)
 
 
+def _run(entry, Rating, UserData, MovieData, Ratingtest, w, hyper, steps, epochs, param_seed,
+         ytrainMean, ytrainStd, flags, side=False, fixw=False, init=None):
+    """One call of a single-fold C entry: conversions, shape check, output stores, seed mask and
+    the arguments in the entries' common order -- ratings, side information (side: the arrays with
+    their sizes, else n1 and n2), test ratings, hyper (floats), w and r, steps (m, then the
+    floats), epochs (ints, maxepoch second), seed, ytrainMean, ytrainStd, flags (bools), outputs.
+    init = (U_init, V_init): an SGD entry (the injected state; the geodesic NaN printed); None: Gibbs."""
+    Rt, Rs, w0 = _f64(Rating), _f64(Ratingtest), _f64(w)
+    r, N, Ntest = w0.shape[0], Rt.shape[0], Rs.shape[0]
+    if Rt.shape[1] < 3 or Rs.shape[1] < 3 or w0.shape != (r, r):
+        raise ValueError("Rating / Ratingtest need (user, movie, rating) columns; %s is r x r"
+                         % ("w" if fixw else "w_init"))
+    if side:
+        Ud, Md = _f64(UserData), _f64(MovieData)
+        (n1, D1), (n2, D2) = Ud.shape, Md.shape
+        middle = (_ptr(Ud), n1, D1, _ptr(Md), n2, D2)
+    else:
+        n1, n2, D1, D2 = np.shape(UserData)[0], np.shape(MovieData)[0], 0, 0
+        middle = (n1, n2)
+    outs = _stores(r, n1 + D1, n2 + D2, Ntest, int(epochs[1]), fixw)
+    if init is not None:
+        _inject(*init)
+    code = getattr(lib(), entry)(
+        _ptr(Rt), N, N, *middle, _ptr(Rs), Ntest, Ntest, *map(float, hyper), _ptr(w0), r,
+        *map(int, steps[:1]), *map(float, steps[1:]), *map(int, epochs),
+        int(param_seed) & (2 ** 64 - 1), float(ytrainMean), float(ytrainStd),
+        *(int(bool(f)) for f in flags), *map(_ptr, outs))
+    (check if init is None else _nan_or_check)(code)
+    return tuple(outs)
+
+
+def GPT_fullw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w,
+                       w_init, m, epsw, epsU, a, b, c, burnin, maxepoch, param_seed, ytrainMean,
+                       ytrainStd, langevin=False, stiefel=False, avg=False, U_init=None, V_init=None):
+    """U_init / V_init (tests): the initial U and V in place of the Philox draw."""
+    return _run("gpt_cf_fullw_sideinfo", Rating, UserData, MovieData, Ratingtest, w_init,
+                (signal_var, sigma_u, sigma_w), (m, epsw, epsU, a, b, c), (burnin, maxepoch),
+                param_seed, ytrainMean, ytrainStd, (langevin, stiefel, avg), side=True,
+                init=(U_init, V_init))
+
+
+def GPT_fullw_gibbs(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w, w_init,
+                    burnin, maxepoch, n_samples, param_seed, ytrainMean, ytrainStd, avg=False,
+                    rotated_w=False):
+    return _run("gpt_cf_fullw_gibbs", Rating, UserData, MovieData, Ratingtest, w_init,
+                (signal_var, sigma_u, sigma_w), (), (burnin, maxepoch, n_samples), param_seed,
+                ytrainMean, ytrainStd, (avg, rotated_w))
+
+
 def GPT_fixw_sideinfo(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m, epsU,
                       a, b, c, burnin, maxepoch, param_seed, ytrainMean, ytrainStd,
                       langevin=False, stiefel=False, avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:282-404 -> (U_store, V_store, testpred_store, trainRMSEvec,
     testRMSEvec)."""
-    Rt, Rs, w0, r, tps, trm, tsm = _sgd_common(Rating, Ratingtest, w, maxepoch)
-    Ud, Md = _f64(UserData), _f64(MovieData)
-    n1, D1 = Ud.shape
-    n2, D2 = Md.shape
-    U_store = np.zeros((n1 + D1, r, maxepoch), order="F")
-    V_store = np.zeros((n2 + D2, r, maxepoch), order="F")
-    _inject(U_init, V_init)
-    _nan_or_check(lib().gpt_cf_fixw_sideinfo(
-        _ptr(Rt), Rt.shape[0], Rt.shape[0], _ptr(Ud), n1, D1, _ptr(Md), n2, D2, _ptr(Rs),
-        Rs.shape[0], Rs.shape[0], float(signal_var), float(sigma_u), _ptr(w0), r, int(m),
-        float(epsU), float(a), float(b), float(c), int(burnin), int(maxepoch),
-        int(param_seed) & (2 ** 64 - 1), float(ytrainMean), float(ytrainStd), int(bool(langevin)),
-        int(bool(stiefel)), int(bool(avg)), _ptr(U_store), _ptr(V_store), _ptr(tps), _ptr(trm),
-        _ptr(tsm)))
-    return U_store, V_store, tps, trm, tsm
+    return _run("gpt_cf_fixw_sideinfo", Rating, UserData, MovieData, Ratingtest, w,
+                (signal_var, sigma_u), (m, epsU, a, b, c), (burnin, maxepoch), param_seed, ytrainMean,
+                ytrainStd, (langevin, stiefel, avg), side=True, fixw=True, init=(U_init, V_init))
 
 
 def GPT_fullw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigma_w, w_init, m,
@@ -179,20 +138,9 @@ def GPT_fullw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, sigm
               stiefel=False, avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:160-279 (no side information) -> (w_store, U_store, V_store,
     testpred_store, trainRMSEvec, testRMSEvec)."""
-    Rt, Rs, w0, r, tps, trm, tsm = _sgd_common(Rating, Ratingtest, w_init, maxepoch)
-    n1, n2 = np.shape(UserData)[0], np.shape(MovieData)[0]
-    w_store = np.zeros((r, r, maxepoch), order="F")
-    U_store = np.zeros((n1, r, maxepoch), order="F")
-    V_store = np.zeros((n2, r, maxepoch), order="F")
-    _inject(U_init, V_init)
-    _nan_or_check(lib().gpt_cf_fullw(
-        _ptr(Rt), Rt.shape[0], Rt.shape[0], n1, n2, _ptr(Rs), Rs.shape[0], Rs.shape[0],
-        float(signal_var), float(sigma_u), float(sigma_w), _ptr(w0), r, int(m), float(epsw),
-        float(epsU), int(burnin), int(maxepoch), int(param_seed) & (2 ** 64 - 1),
-        float(ytrainMean), float(ytrainStd), int(bool(langevin)), int(bool(stiefel)),
-        int(bool(avg)), _ptr(w_store), _ptr(U_store), _ptr(V_store), _ptr(tps), _ptr(trm),
-        _ptr(tsm)))
-    return w_store, U_store, V_store, tps, trm, tsm
+    return _run("gpt_cf_fullw", Rating, UserData, MovieData, Ratingtest, w_init,
+                (signal_var, sigma_u, sigma_w), (m, epsw, epsU), (burnin, maxepoch), param_seed,
+                ytrainMean, ytrainStd, (langevin, stiefel, avg), init=(U_init, V_init))
 
 
 def GPT_fixw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m, epsU, burnin,
@@ -200,18 +148,9 @@ def GPT_fixw(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, m,
              avg=False, U_init=None, V_init=None):
     """100k_movielensExperiment.jl:56-156 (no side information, w fixed) -> (U_store, V_store,
     testpred_store, trainRMSEvec, testRMSEvec)."""
-    Rt, Rs, w0, r, tps, trm, tsm = _sgd_common(Rating, Ratingtest, w, maxepoch)
-    n1, n2 = np.shape(UserData)[0], np.shape(MovieData)[0]
-    U_store = np.zeros((n1, r, maxepoch), order="F")
-    V_store = np.zeros((n2, r, maxepoch), order="F")
-    _inject(U_init, V_init)
-    _nan_or_check(lib().gpt_cf_fixw(
-        _ptr(Rt), Rt.shape[0], Rt.shape[0], n1, n2, _ptr(Rs), Rs.shape[0], Rs.shape[0],
-        float(signal_var), float(sigma_u), _ptr(w0), r, int(m), float(epsU), int(burnin),
-        int(maxepoch), int(param_seed) & (2 ** 64 - 1), float(ytrainMean), float(ytrainStd),
-        int(bool(langevin)), int(bool(stiefel)), int(bool(avg)), _ptr(U_store), _ptr(V_store),
-        _ptr(tps), _ptr(trm), _ptr(tsm)))
-    return U_store, V_store, tps, trm, tsm
+    return _run("gpt_cf_fixw", Rating, UserData, MovieData, Ratingtest, w, (signal_var, sigma_u),
+                (m, epsU), (burnin, maxepoch), param_seed, ytrainMean, ytrainStd,
+                (langevin, stiefel, avg), fixw=True, init=(U_init, V_init))
 
 
 def GPT_fixw_gibbs(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u, w, burnin,
@@ -219,24 +158,16 @@ def GPT_fixw_gibbs(Rating, UserData, MovieData, Ratingtest, signal_var, sigma_u,
                    rotated_w=False):
     """100k_movielensExperiment.jl:945-1028 -> (U_store, V_store, testpred_store, trainRMSEvec,
     testRMSEvec)."""
-    Rt, Rs, w0, r, tps, trm, tsm = _sgd_common(Rating, Ratingtest, w, maxepoch)
-    n1, n2 = np.shape(UserData)[0], np.shape(MovieData)[0]
-    U_store = np.zeros((n1, r, maxepoch), order="F")
-    V_store = np.zeros((n2, r, maxepoch), order="F")
-    check(lib().gpt_cf_fixw_gibbs(
-        _ptr(Rt), Rt.shape[0], Rt.shape[0], n1, n2, _ptr(Rs), Rs.shape[0], Rs.shape[0],
-        float(signal_var), float(sigma_u), _ptr(w0), r, int(burnin), int(maxepoch),
-        int(n_samples), int(param_seed) & (2 ** 64 - 1), float(ytrainMean), float(ytrainStd),
-        int(bool(avg)), int(bool(rotated_w)), _ptr(U_store), _ptr(V_store), _ptr(tps), _ptr(trm),
-        _ptr(tsm)))
-    return U_store, V_store, tps, trm, tsm
+    return _run("gpt_cf_fixw_gibbs", Rating, UserData, MovieData, Ratingtest, w,
+                (signal_var, sigma_u), (), (burnin, maxepoch, n_samples), param_seed, ytrainMean,
+                ytrainStd, (avg, rotated_w), fixw=True)
 
 
 def last_timing():
     """Device time of the last CF SGD / SGLD call on this thread (gpt_cf_last_timing): dict with
     epoch_ms (cf_epoch_kernel launches), eval_ms (cf_eval_kernel), epochs, fold_steps and mode
-    (gpt_cf_last_mode: 0 batch-phase + move launches per step, 1 Stiefel epoch launch, 2 lazy SGD
-    epoch launch)."""
+    (gpt_cf_last_mode, the library's CfMode: 0 kCfStepPairs, batch-phase + move launches per step;
+    1 kCfStiefelEpoch, one Stiefel epoch launch; 2 kCfLazyEpoch, one lazy SGD epoch launch)."""
     em, vm = C.c_double(), C.c_double()
     ne, fs = C.c_int64(), C.c_int64()
     check(lib().gpt_cf_last_timing(C.byref(em), C.byref(vm), C.byref(ne), C.byref(fs)))
@@ -248,43 +179,32 @@ def last_timing():
 
 def GPT_fullw_sideinfo_folds(Ratings, UserData, MovieData, Ratingtests, signal_var, sigma_u,
                              sigma_w, w_init, m, epsw, epsU, a, b, c, burnin, maxepoch, param_seed,
-                             ytrainMeans, ytrainStds, langevin=False, stiefel=False, avg=False):
+                             ytrainMeans, ytrainStds, langevin=False, stiefel=False, avg=False, *,
+                             return_status=False):
     """The per-fold loop of 100k_movielensExperiment.jl:733-736 (GPT_fullw_sideinfo on fold i
     with its own ratings and ytrainMean[i] / ytrainStd[i], one param_seed) with the folds as
     sibling chains of one device launch per epoch.  Returns one (w_store, U_store, V_store,
     testpred_store, trainRMSEvec, testRMSEvec) tuple per fold — the same values as separate
-    GPT_fullw_sideinfo calls; a fold that hit the geodesic NaN keeps zero parameter stores."""
+    GPT_fullw_sideinfo calls; a fold that hit the geodesic NaN keeps zero parameter stores.
+    return_status=True: (that list, the int32 status of each fold — 0 or GPT_ERR_NAN_GEODESIC)."""
     F = len(Ratings)
     if len(Ratingtests) != F or len(ytrainMeans) != F or len(ytrainStds) != F:
         raise ValueError("one test set, ytrainMean and ytrainStd per fold")
-    Rts = [_f64(R) for R in Ratings]
-    Rss = [_f64(R) for R in Ratingtests]
+    Rts, Rss = [_f64(R) for R in Ratings], [_f64(R) for R in Ratingtests]
     Ud, Md, w0 = _f64(UserData), _f64(MovieData), _f64(w_init)
-    n1, D1 = Ud.shape
-    n2, D2 = Md.shape
+    (n1, D1), (n2, D2) = Ud.shape, Md.shape
     r = w0.shape[0]
-    outs = []
-    for Rs in Rss:
-        outs.append((np.zeros((r, r, maxepoch), order="F"),
-                     np.zeros((n1 + D1, r, maxepoch), order="F"),
-                     np.zeros((n2 + D2, r, maxepoch), order="F"),
-                     np.zeros((Rs.shape[0], maxepoch), order="F"), np.zeros(maxepoch),
-                     np.zeros(maxepoch)))
+    outs = [tuple(_stores(r, n1 + D1, n2 + D2, Rs.shape[0], maxepoch)) for Rs in Rss]
     PP = C.c_void_p * F
     ptrs = lambda arrs: PP(*[a.ctypes.data for a in arrs])
-    Ns = np.array([R.shape[0] for R in Rts], dtype=np.int64)
-    Nts = np.array([R.shape[0] for R in Rss], dtype=np.int64)
-    ym = _f64(np.asarray(ytrainMeans, dtype=np.float64))
-    ys = _f64(np.asarray(ytrainStds, dtype=np.float64))
+    Ns, Nts = (np.array([R.shape[0] for R in Rx], dtype=np.int64) for Rx in (Rts, Rss))
+    ym, ys = (_f64(np.asarray(y, dtype=np.float64)) for y in (ytrainMeans, ytrainStds))
     st = np.zeros(F, dtype=np.int32)
-    code = lib().gpt_cf_fullw_sideinfo_folds(
+    _nan_or_check(lib().gpt_cf_fullw_sideinfo_folds(
         F, ptrs(Rts), Ns.ctypes.data, ptrs(Rss), Nts.ctypes.data, _ptr(Ud), n1, D1, _ptr(Md), n2,
         D2, float(signal_var), float(sigma_u), float(sigma_w), _ptr(w0), r, int(m), float(epsw),
         float(epsU), float(a), float(b), float(c), int(burnin), int(maxepoch),
         int(param_seed) & (2 ** 64 - 1), _ptr(ym), _ptr(ys), int(bool(langevin)),
-        int(bool(stiefel)), int(bool(avg)), ptrs([o[0] for o in outs]),
-        ptrs([o[1] for o in outs]), ptrs([o[2] for o in outs]), ptrs([o[3] for o in outs]),
-        ptrs([o[4] for o in outs]), ptrs([o[5] for o in outs]),
-        st.ctypes.data_as(_lib.P_I32))
-    _nan_or_check(code)
-    return outs
+        int(bool(stiefel)), int(bool(avg)), *(ptrs([o[k] for o in outs]) for k in range(6)),
+        st.ctypes.data_as(_lib.P_I32)))
+    return (outs, st) if return_status else outs

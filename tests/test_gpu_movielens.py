@@ -8,6 +8,7 @@ sums in the reference's rating order but forms (e·sumV)·wᵀ as e·(sumV·wᵀ
   test predictions       max |Δ| <= 1e-8 (rating scale)
   train / test RMSE      relative <= 1e-9
 """
+import functools
 import os
 
 import numpy as np
@@ -302,3 +303,134 @@ def test_gaussian_draw_flags_non_spd():
                                                   out.ctypes.data_as(_lib.P_D),
                                                   st.ctypes.data_as(_lib.P_I32)))
     assert st[0] == 1
+
+
+# ---- the host loop's own decisions: the per-fold early stop and the geodesic NaN bail-out --------
+# Folds 1, 2, 3, the first 600 training / 200 test rows of each, r = 3, m = 100 (6 batches an
+# epoch).  At εw = εU = 3e-3 the oracle's test RMSE turns upwards within two epochs, so the five
+# rises in a row of :541-547 come after 7, 6 and 8 kept epochs.
+STOP_NB = 6
+BAIL_MSG = "Get NaN when moving along Geodesic. Try smaller epsU"
+
+
+@functools.lru_cache(maxsize=None)
+def _stop_folds():
+    from gpt_amd import movielens
+    d = np.load(GOLD)
+    folds = [movielens.fold(d, i) for i in (1, 2, 3)]
+    return ([f[0][:600] for f in folds], [f[1][:200] for f in folds], folds[0][2], folds[0][3],
+            [f[4] for f in folds], [f[5] for f in folds])
+
+
+def _stop_common(maxepoch, epsU=3e-3):
+    w0 = np.random.default_rng(5).standard_normal((3, 3))
+    return (0.8, 0.1, 1.0, w0, 100, 3e-3, epsU, 0.5, 0.25, 0.5, 0, maxepoch, 17)
+
+
+@functools.lru_cache(maxsize=None)
+def _stop_oracle(maxepoch, epsU=3e-3, geodesic=False):
+    """The oracle's tuple of every fold (shared by the cases below, never written to)."""
+    trs, tes, ud, md, mus, sds = _stop_folds()
+    return [M.GPT_fullw_sideinfo(trs[f], ud, md, tes[f], *_stop_common(maxepoch, epsU), mus[f], sds[f],
+                                 langevin=geodesic, stiefel=geodesic) for f in range(3)]
+
+
+def _assert_matches(got, want):
+    for g, w_ in zip(got[:3], want[:3]):
+        assert g.shape == w_.shape
+        assert rel(g, w_) < 1e-8, rel(g, w_)
+    assert np.abs(got[3] - want[3]).max() < 1e-8
+    assert np.all(np.abs(got[4] - want[4]) <= 1e-9 * want[4])
+    assert np.all(np.abs(got[5] - want[5]) <= 1e-9 * want[5])
+
+
+@pytest.mark.parametrize("lazy,mode", [(None, 2), ("0", 0)], ids=["lazy_epoch", "graph_replay"])
+@pytest.mark.parametrize("maxepoch,kept", [(7, (7, 6, 7)), (10, (7, 6, 8))])
+def test_sideinfo_folds_early_stop_matches_oracle(monkeypatch, maxepoch, kept, lazy, mode):
+    """Five rises of the test RMSE in a row stop a fold (:541-547); the other folds go on, the
+    stopped one is skipped by the later launches (in mode 0 inside the replayed graph).  maxepoch
+    = 7: fold 2 stops after 6 epochs (its last testRMSE entry stays at :441's 10.0), fold 1 on the
+    last epoch, fold 3 never; maxepoch = 10: after 7, 6 and 8.  Every comparison the oracle's stop
+    rule makes has a relative gap of 1e-8 or more (8.7e-8 the smallest), ten times the 1e-9 the
+    device's RMSE may differ by, so the device decides as the oracle does."""
+    from gpt_amd import movielens
+    trs, tes, ud, md, mus, sds = _stop_folds()
+    want = _stop_oracle(maxepoch)
+    for f in range(3):
+        k = int((want[f][4] > 0).sum())
+        assert k == kept[f]
+        ts = want[f][5][:k]
+        gaps = np.abs(np.diff(ts)) / ts[:-1]
+        print("fold", f + 1, "kept", k, "smallest relative gap %.3g" % gaps.min())
+        assert gaps.min() >= 1e-8                       # the test's own precondition
+    if lazy is not None:
+        monkeypatch.setenv("GPTSGLD_CF_LAZY", lazy)
+    got = movielens.GPT_fullw_sideinfo_folds(trs, ud, md, tes, *_stop_common(maxepoch), mus, sds)
+    tm = movielens.last_timing()
+    assert tm["mode"] == mode
+    # every launch counts the folds live at its start: fold f is live in epochs 1..kept[f]
+    live = [sum(k >= e for k in kept) for e in range(1, maxepoch + 1)]
+    assert tm["fold_steps"] == STOP_NB * sum(live)
+    assert tm["epochs"] == max(kept)
+    for f in range(3):
+        print("fold", f + 1, [rel(g, w_) for g, w_ in zip(got[f][:3], want[f][:3])],
+              np.abs(got[f][3] - want[f][3]).max(), np.abs(got[f][5] / want[f][5] - 1).max())
+        _assert_matches(got[f], want[f])
+        k = kept[f]
+        for g, w_ in zip(got[f], want[f]):              # past the stop: zeros, 10.0 in testRMSE
+            assert np.array_equal(g[..., k:], w_[..., k:])
+        assert all(not got[f][z][..., k:].any() for z in range(5))
+        assert np.all(got[f][5][k:] == 10.0) and np.all(got[f][5][:k] < 10.0)
+
+
+def test_fullw_sideinfo_geodesic_nan_bails_out(capsys):
+    """εU = 1e4 on the Stiefel path: the first epoch's geodesic gives NaN (:490-492), the run
+    returns zero parameter stores, the curves as they are (nothing kept yet: zeros, 10.0) and
+    prints the reference's message; εU = 1e-2 runs through."""
+    from gpt_amd import movielens
+    trs, tes, ud, md, mus, sds = _stop_folds()
+    want = _stop_oracle(3, 1e4, True)[0]
+    assert not any(x.any() for x in want[:5]) and np.all(want[5] == 10.0)
+    got = movielens.GPT_fullw_sideinfo(trs[0], ud, md, tes[0], *_stop_common(3, 1e4), mus[0], sds[0],
+                                       langevin=True, stiefel=True)
+    assert movielens.last_timing()["mode"] == 1
+    assert capsys.readouterr().out == BAIL_MSG + "\n"
+    for g, w_ in zip(got, want):
+        assert g.shape == w_.shape and np.array_equal(g, w_)
+    want = _stop_oracle(3, 1e-2, True)[0]
+    got = movielens.GPT_fullw_sideinfo(trs[0], ud, md, tes[0], *_stop_common(3, 1e-2), mus[0], sds[0],
+                                       langevin=True, stiefel=True)
+    assert capsys.readouterr().out == ""
+    assert all(x[..., -1].any() for x in got)
+    print([rel(g, w_) for g, w_ in zip(got[:3], want[:3])], np.abs(got[3] - want[3]).max(),
+          np.abs(got[5] / want[5] - 1).max())
+    _assert_matches(got, want)
+
+
+def test_sideinfo_folds_geodesic_nan_sets_the_status_of_each_fold(capsys):
+    """The folds entry reports the bail-out per fold (status[f] = GPT_ERR_NAN_GEODESIC) and
+    returns that code, which the wrapper prints as the reference does; every fold's tuple is that
+    of its own GPT_fullw_sideinfo call, bit for bit.  (At εU = 1e4 the geodesic's argument has a
+    norm in the hundreds: the step at which its exponential first overflows is rounding noise
+    times e^norm, so only fold 1's bail-out in the first epoch is held to the oracle, above; the
+    oracle's folds 2 and 3 bail out too, one of them an epoch later.)"""
+    from gpt_amd import _lib, movielens
+    trs, tes, ud, md, mus, sds = _stop_folds()
+    kw = dict(langevin=True, stiefel=True)
+    for epsU, code in ((1e4, _lib.GPT_ERR_NAN_GEODESIC), (1e-2, _lib.GPT_OK)):
+        want = _stop_oracle(3, epsU, True)
+        assert [not any(x.any() for x in w_[:3]) for w_ in want] == [code != _lib.GPT_OK] * 3
+        common = _stop_common(3, epsU)
+        got, status = movielens.GPT_fullw_sideinfo_folds(trs, ud, md, tes, *common, mus, sds, **kw,
+                                                         return_status=True)
+        assert capsys.readouterr().out == (BAIL_MSG + "\n" if code else "")
+        assert status.dtype == np.int32 and status.tolist() == [code] * 3
+        for f in range(3):
+            one = movielens.GPT_fullw_sideinfo(trs[f], ud, md, tes[f], *common, mus[f], sds[f], **kw)
+            for g, o in zip(got[f], one):
+                assert g.shape == o.shape and np.array_equal(g, o)
+            if code:
+                assert not any(x.any() for x in got[f][:3])             # zero parameter stores
+            else:
+                _assert_matches(got[f], want[f])
+        assert capsys.readouterr().out == (BAIL_MSG + "\n") * (3 if code else 0)   # the single calls
