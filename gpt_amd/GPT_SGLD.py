@@ -216,12 +216,16 @@ def _engine_env(engine):
             os.environ["GPTSGLD_ENGINE"] = old
 
 
-def GPTregression(phi, y, signal_var, I, r, Q, m, epsw, epsU, burnin, maxepoch, param_seed=0,
-                  langevin=True, stiefel=True, sigma_w=1.0, store_every=1, max_steps=0,
-                  w_init=None, U_init=None, diag=False, engine=None):
-    """Tensor-GP regression sampler (GPT_SGLD.jl:345-448).  Returns (w_store, U_store)
-    [, diag]; ``diag`` = per-step [‖gradw‖, ‖gradU_1‖, …] ((1+D) × steps).
-    ``engine`` ("grid" | "chain" | "wave" | None = library default) selects the step kernel."""
+def _run_counts(N, m, burnin, maxepoch, store_every=1, max_steps=0):
+    """(batches per epoch, steps run, samples stored) of a sampler run, as the library counts
+    them (session_counts, api_session.hip)."""
+    nb = -(-N // m)
+    total = (burnin + maxepoch) * nb
+    return nb, total if max_steps <= 0 else min(total, max_steps), (maxepoch * nb) // store_every
+
+
+def _sampler_inputs(phi, y, I, Q):
+    """phi (n, D, N), y (N) and I (Q, D) as the library reads them, and (n, D, N)."""
     phi = _f64(phi)
     n, D, N = phi.shape
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
@@ -230,28 +234,71 @@ def GPTregression(phi, y, signal_var, I, r, Q, m, epsw, epsU, burnin, maxepoch, 
     I = np.asfortranarray(np.asarray(I, dtype=np.int32))
     if I.shape != (Q, D):
         raise ValueError("I must be (Q, D)")
-    cfg = make_config(n, D, N, r, Q, m, epsw, epsU, signal_var, sigma_w, burnin, maxepoch,
-                      param_seed, langevin, stiefel, store_every, max_steps)
-    nb = -(-N // m)
-    T = (maxepoch * nb) // store_every
-    w_store = np.zeros((Q, T), order="F")
-    U_store = np.zeros((n, r, D, T), order="F")
-    total = (burnin + maxepoch) * nb if max_steps <= 0 else min((burnin + maxepoch) * nb, max_steps)
-    dg = np.zeros((1 + D, total), order="F") if diag else None
-    wi = _f64(w_init) if w_init is not None else None
-    Ui = _f64(U_init) if U_init is not None else None
-    with _engine_env(engine):
-        code = lib().gpt_sgld_regression(C.byref(cfg), _ptr(phi), _ptr(y), _ptr(I, P_I32),
-                                         _ptr(wi) if wi is not None else None,
-                                         _ptr(Ui) if Ui is not None else None,
-                                         _ptr(w_store), _ptr(U_store), _ptr(dg) if diag else None)
+    return phi, y, I, (n, D, N)
+
+
+def _opt_ptr(a):
+    """The pointer of an optional array argument (it keeps its array alive), or None."""
+    return None if a is None else _ptr(_f64(a))
+
+
+def _geodesic_epilogue(code, *stores):
+    """The reference's message and all-zero stores on the geodesic NaN bail-out
+    (GPT_SGLD.jl:422-424); any other code through check."""
     if code == _lib.GPT_ERR_NAN_GEODESIC:
         print("Get NaN when moving along Geodesic. Try smaller epsU")
-        w_store[:] = 0.0
-        U_store[:] = 0.0
+        for s in stores:
+            s[:] = 0.0
     else:
         check(code)
+
+
+def GPTregression(phi, y, signal_var, I, r, Q, m, epsw, epsU, burnin, maxepoch, param_seed=0,
+                  langevin=True, stiefel=True, sigma_w=1.0, store_every=1, max_steps=0,
+                  w_init=None, U_init=None, diag=False, engine=None):
+    """Tensor-GP regression sampler (GPT_SGLD.jl:345-448).  Returns (w_store, U_store)
+    [, diag]; ``diag`` = per-step [‖gradw‖, ‖gradU_1‖, …] ((1+D) × steps).
+    ``engine`` ("grid" | "chain" | "wave" | None = library default) selects the step kernel."""
+    phi, y, I, (n, D, N) = _sampler_inputs(phi, y, I, Q)
+    cfg = make_config(n, D, N, r, Q, m, epsw, epsU, signal_var, sigma_w, burnin, maxepoch,
+                      param_seed, langevin, stiefel, store_every, max_steps)
+    _, total, T = _run_counts(N, m, burnin, maxepoch, store_every, max_steps)
+    w_store = np.zeros((Q, T), order="F")
+    U_store = np.zeros((n, r, D, T), order="F")
+    dg = np.zeros((1 + D, total), order="F") if diag else None
+    with _engine_env(engine):
+        code = lib().gpt_sgld_regression(C.byref(cfg), _ptr(phi), _ptr(y), _ptr(I, P_I32),
+                                         _opt_ptr(w_init), _opt_ptr(U_init), _ptr(w_store),
+                                         _ptr(U_store), _opt_ptr(dg))
+    _geodesic_epilogue(code, w_store, U_store)
     return (w_store, U_store, dg) if diag else (w_store, U_store)
+
+
+def _ptr_array(xs):
+    return (P_D * len(xs))(*[_ptr(x) for x in xs])
+
+
+def _regression_chains(call, seeds, y, I, dims, r, Q, m, epsw, epsU, signal_var, sigma_w, burnin,
+                       maxepoch, store_every, max_steps, engine):
+    """What the two _chains forms share: the per-chain scalars, the seeds, the zeroed stores and
+    the returned list.  ``call(cfg, nchains, seeds, ys, I, epsw, epsU, signal_var, w_stores,
+    U_stores, status)`` is the library entry with the caller's own inputs bound."""
+    n, D, N = dims
+    nch = len(seeds)
+    ew, eu, sv = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (nch,)))
+                  for v in (epsw, epsU, signal_var))
+    cfg = make_config(n, D, N, r, Q, m, ew[0], eu[0], sv[0], sigma_w, burnin, maxepoch, 0, True,
+                      True, store_every, max_steps)
+    T = _run_counts(N, m, burnin, maxepoch, store_every)[2]
+    ws = [np.zeros((Q, T), order="F") for _ in range(nch)]
+    Us = [np.zeros((n, r, D, T), order="F") for _ in range(nch)]
+    st = np.zeros(nch, dtype=np.int32)
+    sd = np.array(seeds, dtype=np.uint64)
+    with _engine_env(engine):
+        check(call(C.byref(cfg), nch, sd.ctypes.data_as(P_U64), _ptr_array([y] * nch),
+                   _ptr(I, P_I32), _ptr(ew), _ptr(eu), _ptr(sv), _ptr_array(ws), _ptr_array(Us),
+                   _ptr(st, P_I32)))
+    return [(ws[c], Us[c], int(st[c])) for c in range(nch)]
 
 
 def GPTregression_chains(phis, y, signal_var, I, r, Q, m, epsw, epsU, burnin, maxepoch, seeds,
@@ -273,35 +320,14 @@ def GPTregression_chains(phis, y, signal_var, I, r, Q, m, epsw, epsU, burnin, ma
         if id(p) not in uniq:
             uniq[id(p)] = _f64(p)
     ph = [uniq[id(p)] for p in phis]
-    n, D, N = ph[0].shape
-    if any(p.shape != (n, D, N) for p in ph):
+    if any(p.shape != ph[0].shape for p in ph):
         raise ValueError("every phi must have the same (n, D, N)")
-    y = _f64(np.asarray(y, dtype=np.float64).ravel())
-    if y.size != N:
-        raise ValueError("phi and y disagree on N")
-    I = np.asfortranarray(np.asarray(I, dtype=np.int32))
-    if I.shape != (Q, D):
-        raise ValueError("I must be (Q, D)")
-
-    def per_chain(v):
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (nch,)))
-        return a, _ptr(a)
-    ew, ew_p = per_chain(epsw)
-    eu, eu_p = per_chain(epsU)
-    sv, sv_p = per_chain(signal_var)
-    cfg = make_config(n, D, N, r, Q, m, ew[0], eu[0], sv[0], sigma_w, burnin, maxepoch, 0, True,
-                      True, store_every, max_steps)
-    T = (maxepoch * (-(-N // m))) // store_every
-    ws = [np.zeros((Q, T), order="F") for _ in range(nch)]
-    Us = [np.zeros((n, r, D, T), order="F") for _ in range(nch)]
-    st = np.zeros(nch, dtype=np.int32)
-    arr = lambda xs: (P_D * nch)(*[_ptr(x) for x in xs])
-    sd = np.array(seeds, dtype=np.uint64)
-    with _engine_env(engine):
-        check(lib().gpt_sgld_regression_chains(C.byref(cfg), nch, sd.ctypes.data_as(P_U64),
-                                               arr(ph), arr([y] * nch), _ptr(I, P_I32), ew_p,
-                                               eu_p, sv_p, arr(ws), arr(Us), _ptr(st, P_I32)))
-    return [(ws[c], Us[c], int(st[c])) for c in range(nch)]
+    _, y, I, dims = _sampler_inputs(ph[0], y, I, Q)
+    return _regression_chains(
+        lambda cfg, k, sd, ys, *rest: lib().gpt_sgld_regression_chains(cfg, k, sd, _ptr_array(ph),
+                                                                       ys, *rest),
+        seeds, y, I, dims, r, Q, m, epsw, epsU, signal_var, sigma_w, burnin, maxepoch, store_every,
+        max_steps, engine)
 
 
 def GPTregression_chains_x(X, y, length_scales, sigma_RBFs, phi_scale, Z, b, signal_var, I, r, Q,
@@ -337,60 +363,29 @@ def GPTregression_chains_x(X, y, length_scales, sigma_RBFs, phi_scale, Z, b, sig
     I = np.asfortranarray(np.asarray(I, dtype=np.int32))
     if I.shape != (Q, D):
         raise ValueError("I must be (Q, D)")
-
-    def per_chain(v):
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (nch,)))
-        return a, _ptr(a)
-    ew, ew_p = per_chain(epsw)
-    eu, eu_p = per_chain(epsU)
-    sv, sv_p = per_chain(signal_var)
-    cfg = make_config(n, D, N, r, Q, m, ew[0], eu[0], sv[0], sigma_w, burnin, maxepoch, 0, True,
-                      True, store_every, max_steps)
-    T = (maxepoch * (-(-N // m))) // store_every
-    ws = [np.zeros((Q, T), order="F") for _ in range(nch)]
-    Us = [np.zeros((n, r, D, T), order="F") for _ in range(nch)]
-    st = np.zeros(nch, dtype=np.int32)
-    arr = lambda xs: (P_D * nch)(*[_ptr(x) for x in xs])
-    sd = np.array(seeds, dtype=np.uint64)
-    with _engine_env(engine):
-        check(lib().gpt_sgld_regression_chains_x(
-            C.byref(cfg), nch, sd.ctypes.data_as(P_U64), _ptr(X), arr([y] * nch), _ptr(ls),
-            ls.shape[1], _ptr(sg), float(phi_scale), _ptr(Z), _ptr(b), _ptr(I, P_I32), ew_p, eu_p,
-            sv_p, arr(ws), arr(Us), _ptr(st, P_I32)))
-    return [(ws[c], Us[c], int(st[c])) for c in range(nch)]
+    return _regression_chains(
+        lambda cfg, k, sd, ys, Ip, *rest: lib().gpt_sgld_regression_chains_x(
+            cfg, k, sd, _ptr(X), ys, _ptr(ls), ls.shape[1], _ptr(sg), float(phi_scale), _ptr(Z),
+            _ptr(b), Ip, *rest),
+        seeds, y, I, (n, D, N), r, Q, m, epsw, epsU, signal_var, sigma_w, burnin, maxepoch,
+        store_every, max_steps, engine)
 
 
 def GPT_SGLDERM_RMSprop(phi, y, signal_var, I, r, Q, m, epsilon, alpha, burnin, maxepoch,
                         param_seed=0, w_init=None, U_init=None, diag=False):
     """SGLD with RMSprop step sizes (GPT_SGLD.jl:1121-1237).  Returns (w_store, U_store)
     [, diag]; on the geodesic NaN bail-out prints the reference's message and returns zeros."""
-    phi = _f64(phi)
-    n, D, N = phi.shape
-    y = _f64(np.asarray(y, dtype=np.float64).ravel())
-    if y.size != N:
-        raise ValueError("phi and y disagree on N")
-    I = np.asfortranarray(np.asarray(I, dtype=np.int32))
-    if I.shape != (Q, D):
-        raise ValueError("I must be (Q, D)")
+    phi, y, I, (n, D, N) = _sampler_inputs(phi, y, I, Q)
     cfg = make_config(n, D, N, r, Q, m, epsilon, epsilon, signal_var, 1.0, burnin, maxepoch,
                       param_seed, True, True, 1, 0)
-    nb = -(-N // m)
-    T = maxepoch * nb
+    _, total, T = _run_counts(N, m, burnin, maxepoch)
     w_store = np.zeros((Q, T), order="F")
     U_store = np.zeros((n, r, D, T), order="F")
-    dg = np.zeros((1 + D, (burnin + maxepoch) * nb), order="F") if diag else None
-    wi = _f64(w_init) if w_init is not None else None
-    Ui = _f64(U_init) if U_init is not None else None
+    dg = np.zeros((1 + D, total), order="F") if diag else None
     code = lib().gpt_sgld_rmsprop(C.byref(cfg), float(epsilon), float(alpha), _ptr(phi), _ptr(y),
-                                  _ptr(I, P_I32), _ptr(wi) if wi is not None else None,
-                                  _ptr(Ui) if Ui is not None else None, _ptr(w_store),
-                                  _ptr(U_store), _ptr(dg) if diag else None)
-    if code == _lib.GPT_ERR_NAN_GEODESIC:
-        print("Get NaN when moving along Geodesic. Try smaller epsU")
-        w_store[:] = 0.0
-        U_store[:] = 0.0
-    else:
-        check(code)
+                                  _ptr(I, P_I32), _opt_ptr(w_init), _opt_ptr(U_init),
+                                  _ptr(w_store), _ptr(U_store), _opt_ptr(dg))
+    _geodesic_epilogue(code, w_store, U_store)
     return (w_store, U_store, dg) if diag else (w_store, U_store)
 
 
@@ -398,26 +393,15 @@ def GPT_SGLDERMw(phi, y, signal_var, I, r, Q, m, epsw, burnin, maxepoch, param_s
                  w_init=None, U_init=None, diag=False):
     """SGLD on w with U fixed at its uniform Stiefel draw (GPT_SGLD.jl:1065-1118).  Returns
     (w_store, U) [, gradw norms per step]."""
-    phi = _f64(phi)
-    n, D, N = phi.shape
-    y = _f64(np.asarray(y, dtype=np.float64).ravel())
-    if y.size != N:
-        raise ValueError("phi and y disagree on N")
-    I = np.asfortranarray(np.asarray(I, dtype=np.int32))
-    if I.shape != (Q, D):
-        raise ValueError("I must be (Q, D)")
+    phi, y, I, (n, D, N) = _sampler_inputs(phi, y, I, Q)
     cfg = make_config(n, D, N, r, Q, m, epsw, 0.0, signal_var, 1.0, burnin, maxepoch,
                       param_seed, True, True, 1, 0)
-    nb = -(-N // m)
-    w_store = np.zeros((Q, maxepoch * nb), order="F")
+    _, total, T = _run_counts(N, m, burnin, maxepoch)
+    w_store = np.zeros((Q, T), order="F")
     U = np.zeros((n, r, D), order="F")
-    dg = np.zeros((1 + D, (burnin + maxepoch) * nb), order="F") if diag else None
-    wi = _f64(w_init) if w_init is not None else None
-    Ui = _f64(U_init) if U_init is not None else None
-    check(lib().gpt_sgld_wonly(C.byref(cfg), _ptr(phi), _ptr(y), _ptr(I, P_I32),
-                               _ptr(wi) if wi is not None else None,
-                               _ptr(Ui) if Ui is not None else None, _ptr(w_store), _ptr(U),
-                               _ptr(dg) if diag else None))
+    dg = np.zeros((1 + D, total), order="F") if diag else None
+    check(lib().gpt_sgld_wonly(C.byref(cfg), _ptr(phi), _ptr(y), _ptr(I, P_I32), _opt_ptr(w_init),
+                               _opt_ptr(U_init), _ptr(w_store), _ptr(U), _opt_ptr(dg)))
     return (w_store, U, dg[0].copy()) if diag else (w_store, U)
 
 
@@ -426,32 +410,18 @@ def GPTclassification(phi, y, I, r, Q, m, epsw, epsU, burnin, maxepoch, param_se
     """Softmax tensor-GP classifier (GPT_SGLD.jl:452-680), labels y in 1..C.  Returns
     (w_store (Q, C, T), U_store (n, r, D, C, T)) [, diag (1+D, steps, C)]; on the geodesic NaN
     bail-out prints the reference's message and returns zeros."""
-    phi = _f64(phi)
-    n, D, N = phi.shape
-    y = _f64(np.asarray(y, dtype=np.float64).ravel())
-    if y.size != N:
-        raise ValueError("phi and y disagree on N")
+    phi, y, I, (n, D, N) = _sampler_inputs(phi, y, I, Q)
     ncls = int(y.max() - y.min() + 1)
-    I = np.asfortranarray(np.asarray(I, dtype=np.int32))
-    if I.shape != (Q, D):
-        raise ValueError("I must be (Q, D)")
     cfg = make_config(n, D, N, r, Q, m, epsw, epsU, 1.0, 1.0, burnin, maxepoch, param_seed,
                       langevin, stiefel, 1, 0)
-    nb = -(-N // m)
-    T = maxepoch * nb
+    _, total, T = _run_counts(N, m, burnin, maxepoch)
     w_store = np.zeros((Q, ncls, T), order="F")
     U_store = np.zeros((n, r, D, ncls, T), order="F")
-    dg = np.zeros((1 + D, (burnin + maxepoch) * nb, ncls), order="F") if diag else None
-    wi = _f64(w_init) if w_init is not None else None
-    Ui = _f64(U_init) if U_init is not None else None
+    dg = np.zeros((1 + D, total, ncls), order="F") if diag else None
     code = lib().gpt_sgld_classification(C.byref(cfg), _ptr(phi), _ptr(y), _ptr(I, P_I32),
-                                         _ptr(wi) if wi is not None else None,
-                                         _ptr(Ui) if Ui is not None else None, _ptr(w_store),
-                                         _ptr(U_store), _ptr(dg) if diag else None)
-    if code == _lib.GPT_ERR_NAN_GEODESIC:
-        print("Get NaN when moving along Geodesic. Try smaller epsU")
-    else:
-        check(code)
+                                         _opt_ptr(w_init), _opt_ptr(U_init), _ptr(w_store),
+                                         _ptr(U_store), _opt_ptr(dg))
+    _geodesic_epilogue(code, w_store, U_store)
     return (w_store, U_store, dg) if diag else (w_store, U_store)
 
 
@@ -460,28 +430,15 @@ def GPT_GMC(phi, y, signal_var, I, r, Q, epsw, epsU, burnin, maxepoch, L, param_
     """Geodesic Monte Carlo (GPT_SGLD.jl:684-805).  Returns (w_store (Q, maxepoch),
     U_store (n, r, D, maxepoch), accept_prob (burnin+maxepoch)); on the geodesic NaN bail-out
     prints the reference's message and returns zeros and NaN probabilities."""
-    phi = _f64(phi)
-    n, D, N = phi.shape
-    y = _f64(np.asarray(y, dtype=np.float64).ravel())
-    if y.size != N:
-        raise ValueError("phi and y disagree on N")
-    I = np.asfortranarray(np.asarray(I, dtype=np.int32))
-    if I.shape != (Q, D):
-        raise ValueError("I must be (Q, D)")
+    phi, y, I, (n, D, N) = _sampler_inputs(phi, y, I, Q)
     w_store = np.zeros((Q, maxepoch), order="F")
     U_store = np.zeros((n, r, D, maxepoch), order="F")
     acc = np.zeros(burnin + maxepoch)
-    wi = _f64(w_init) if w_init is not None else None
-    Ui = _f64(U_init) if U_init is not None else None
     code = lib().gpt_gmc(_ptr(phi), _ptr(y), n, D, N, r, Q, _ptr(I, P_I32), float(signal_var),
                          float(epsw), float(epsU), int(burnin), int(maxepoch), int(L),
-                         int(param_seed) & (2 ** 64 - 1), _ptr(wi) if wi is not None else None,
-                         _ptr(Ui) if Ui is not None else None, _ptr(w_store), _ptr(U_store),
-                         _ptr(acc))
-    if code == _lib.GPT_ERR_NAN_GEODESIC:
-        print("Get NaN when moving along Geodesic. Try smaller epsU")
-    else:
-        check(code)
+                         int(param_seed) & (2 ** 64 - 1), _opt_ptr(w_init), _opt_ptr(U_init),
+                         _ptr(w_store), _ptr(U_store), _ptr(acc))
+    _geodesic_epilogue(code, w_store, U_store)
     return w_store, U_store, acc
 
 

@@ -11,7 +11,6 @@
 #include "host_util.h"
 
 using namespace gpt;
-#define CF_TRY(call) do { const int rc_ = (call); if (rc_ != GPT_OK) return rc_; } while (0)
 
 // U, V initialisation of the SGD / SGLD CF samplers (the reference's variants differ):
 //   kCfInitSide  GPT_fullw_sideinfo :424-428  stiefel ? polar(randn(r,rows)) : σ_u·randn(rows,r)
@@ -118,22 +117,6 @@ static bool cf_model_ok(const CfModel& M, const CfSchedule& S) {
   return M.w_init && M.n1 >= 1 && M.n2 >= 1 && S.burnin >= 0 && S.maxepoch >= 0 &&
          M.signal_var > 0 && M.sigma_u > 0 && M.sigma_w > 0;
 }
-
-// Carves typed arrays out of one device allocation.  Every array starts on a 256-byte boundary,
-// the alignment of a hipMalloc of its own, so a kernel may assume of a carved pointer whatever it
-// may of an allocated one.  The same take() calls run twice: without a base they count the bytes,
-// with one they hand the arrays out and copy `host` in (the first failed copy is kept in err).
-struct Carve {
-  char* base = nullptr;
-  size_t off = 0;
-  hipError_t err = hipSuccess;
-  template <class T> T* take(size_t count, const T* host = nullptr) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += (sizeof(T) * count + 255) / 256 * 256;
-    if (p && host && err == hipSuccess) err = hipMemcpy(p, host, sizeof(T) * count, hipMemcpyHostToDevice);
-    return p;
-  }
-};
 
 // One fold's state on the device, of either sampler: ids, ratings, w, U, V, running predictions,
 // SSE partials and status in one zeroed allocation, and the CfChain that points into it.  `sgd`
@@ -412,14 +395,14 @@ static int cf_sgd_run(const char* name, const CfModel& M, const CfSchedule& S, s
   GPT_HIPCHK(d_perm.alloc<int32_t>(N));
   std::vector<CfChain> ch(F);
   for (int f = 0; f < F; ++f) {
-    CF_TRY(R.dev[f].init(folds[f], split[f], R.z, true, M.w_init, U0.data(), V0.data(), d_perm.as<int32_t>()));
+    GPT_TRY(R.dev[f].init(folds[f], split[f], R.z, true, M.w_init, U0.data(), V0.data(), d_perm.as<int32_t>()));
     ch[f] = R.dev[f].C;
     zero_outputs(folds[f], R.z, true, 10.0);
     folds[f].status = GPT_OK;
   }
   GPT_HIPCHK(d_ch.upload(ch.data(), ch.size()));
   CfSideDev side; CfParams P;
-  CF_TRY(fill_params(M, S, M.masks(), side, P));
+  GPT_TRY(fill_params(M, S, M.masks(), side, P));
   g_cf_stamps.clear();
   if (std::getenv("GPTSGLD_CF_STAMPS")) {
     GPT_HIPCHK(d_stamps.alloc<long long>((size_t)kCfStampSteps * kCfStampSlots));
@@ -434,14 +417,14 @@ static int cf_sgd_run(const char* name, const CfModel& M, const CfSchedule& S, s
   ScopedEvents evs;
   GPT_HIPCHK(evs.create(4));
   CfEpochLauncher L{cf_pick_mode(S, P, nbatch), P, d_ch.as<CfChain>(), F, N, nbatch};
-  CF_TRY(L.init());
+  GPT_TRY(L.init());
   g_cf_timing = CfTiming{};
   g_cf_mode = L.mode;
   for (int64_t epoch = 1; epoch <= S.burnin + S.maxepoch && R.nlive > 0; ++epoch) {
     host_randperm(N, M.seed, (int)(epoch - 1), perm.data());
     GPT_HIPCHK(hipMemcpy(d_perm.p, perm.data(), d_perm.bytes, hipMemcpyHostToDevice));
-    CF_TRY(L.launch(epoch, evs.e[0]));
-    CF_TRY(cf_stop_timer(evs.e[0], evs.e[1], L.s, &g_cf_timing.epoch_ms));
+    GPT_TRY(L.launch(epoch, evs.e[0]));
+    GPT_TRY(cf_stop_timer(evs.e[0], evs.e[1], L.s, &g_cf_timing.epoch_ms));
     if (P.stamps) {                // the first epoch only
       g_cf_stamps.resize((size_t)kCfStampSteps * kCfStampSlots);
       GPT_HIPCHK(d_stamps.download(g_cf_stamps.data(), g_cf_stamps.size()));
@@ -449,15 +432,15 @@ static int cf_sgd_run(const char* name, const CfModel& M, const CfSchedule& S, s
     }
     g_cf_timing.epochs += 1;
     g_cf_timing.fold_steps += (int64_t)R.nlive * nbatch;
-    CF_TRY(R.poll_bails());
+    GPT_TRY(R.poll_bails());
     if (epoch <= S.burnin || R.nlive == 0) continue;
     if (!S.avg) counter = 0;
     GPT_HIPCHK(hipEventRecord(evs.e[2], L.s));
     const hipError_t e = launch_cf_eval(P, d_ch.as<CfChain>(), F, R.z.nmax, counter, L.s);
     if (e != hipSuccess) return hip_fail(e, "cf eval kernel");
-    CF_TRY(cf_stop_timer(evs.e[2], evs.e[3], L.s, &g_cf_timing.eval_ms));
+    GPT_TRY(cf_stop_timer(evs.e[2], evs.e[3], L.s, &g_cf_timing.eval_ms));
     g_cf_timing.evals += 1;
-    CF_TRY(R.keep(epoch, epoch - S.burnin - 1));
+    GPT_TRY(R.keep(epoch, epoch - S.burnin - 1));
     counter += 1;
   }
   for (const CfFold& fd : folds)
@@ -810,17 +793,17 @@ static int cf_gibbs_run(const char* name, const CfModel& M, const CfSchedule& S,
   std::vector<double> w0, U0, V0;
   cfg_init(M, S.rotated_w != 0, w0, U0, V0);
   CfFoldDev D; CfGibbsDev G;
-  CF_TRY(D.init(fd, R, z, false, w0.data(), U0.data(), V0.data(), nullptr));
-  CF_TRY(G.init(M, R));
+  GPT_TRY(D.init(fd, R, z, false, w0.data(), U0.data(), V0.data(), nullptr));
+  GPT_TRY(G.init(M, R));
   const CfChain& C = D.C;
   CfSideDev side; CfParams P;
-  CF_TRY(fill_params(M, S, false, side, P));
+  GPT_TRY(fill_params(M, S, false, side, P));
   DevMem d_ch;
   GPT_HIPCHK(d_ch.upload(&C, 1));
   zero_outputs(fd, z, true, 0.0);
   CfKeep K; StatusRing sr;
-  CF_TRY(K.init(z, fd.Ntest));
-  CF_TRY(sr.init());
+  GPT_TRY(K.init(z, fd.Ntest));
+  GPT_TRY(sr.init());
   int counter = 0; uint32_t sweep = 0;
   for (int64_t epoch = 1; epoch <= S.burnin + S.maxepoch; ++epoch) {
     for (int64_t g = 0; g < S.n_samples; ++g, ++sweep) {
@@ -839,7 +822,7 @@ static int cf_gibbs_run(const char* name, const CfModel& M, const CfSchedule& S,
                             K.tp + (size_t)fd.Ntest * slot, nullptr);
       if (e != hipSuccess) return hip_fail(e, "cf eval kernel");
       counter += 1;
-      if (slot + 1 == K.chunkE) CF_TRY(K.flush(fd, z, C.status, s2 + 1));
+      if (slot + 1 == K.chunkE) GPT_TRY(K.flush(fd, z, C.status, s2 + 1));
     }
     const int ring = (int)(epoch & 1);
     GPT_HIPCHK(hipMemcpyAsync(sr.h + ring, C.status, 4, hipMemcpyDeviceToHost, nullptr));

@@ -42,37 +42,31 @@ extern "C" int gpt_sgld_classification(const gpt_sgld_config* cfg, const double*
   std::vector<uint64_t> seeds(ncls, cfg->seed);
   std::vector<const double*> pp(ncls, dphi.as<double>()), yy(ncls, dy.as<double>());
   gpt_sgld_session* s = nullptr;
-  const int flags = ((w_store || U_store) ? 1 : 0) | (diag ? 2 : 0) | 32;
-  int rc = gpt_sgld_session_create(cfg, ncls, seeds.data(), pp.data(), yy.data(), I, flags, nullptr, &s);
-  if (rc != GPT_OK) return rc;
+  const int flags = ((w_store || U_store) ? kFlagStore : 0) | (diag ? kFlagDiag : 0) | kFlagCls;
+  GPT_TRY(gpt_sgld_session_create(cfg, ncls, seeds.data(), pp.data(), yy.data(), I, flags, nullptr, &s));
   std::unique_ptr<gpt_sgld_session, void (*)(gpt_sgld_session*)> guard(s, gpt_sgld_session_destroy);
-  rc = session_alloc_aux(s);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(session_alloc_aux(s));
   std::vector<double> w0((size_t)Q), U0((size_t)nur);
   for (int c = 0; c < ncls; ++c) {
-    rc = gpt_sgld_session_set_hyper(s, c, cfg->epsw, cfg->epsU, 1.0, 1.0);   // no noise variance
-    if (rc != GPT_OK) return rc;
+    GPT_TRY(gpt_sgld_session_set_hyper(s, c, cfg->epsw, cfg->epsU, 1.0, 1.0));   // no noise variance
     if (w_init && U_init) {
-      rc = session_set_state(s, c, w_init + (size_t)Q * c, U_init + (size_t)nur * c);
+      GPT_TRY(session_set_state(s, c, w_init + (size_t)Q * c, U_init + (size_t)nur * c));
     } else {
       host_init_state((int)cfg->n, (int)cfg->r, (int)cfg->D, (int)Q, cfg->seed, cfg->stiefel != 0,
                       1.0, w0.data(), U0.data(), c, true);
-      rc = session_set_state(s, c, w0.data(), U0.data());
+      GPT_TRY(session_set_state(s, c, w0.data(), U0.data()));
     }
-    if (rc != GPT_OK) return rc;
   }
   const SessionRun run = session_run_info(s);
-  rc = gpt_sgld_session_run(s, run.total_steps);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(gpt_sgld_session_run(s, run.total_steps));
   const int64_t T = run.nstore, steps = run.total_steps;
   std::vector<double> wb(w_store ? (size_t)Q * T : 0), Ub(U_store ? (size_t)nur * T : 0),
       db(diag ? (size_t)(1 + cfg->D) * steps : 0);
   bool bad = false;
   for (int c = 0; c < ncls; ++c) {
     int32_t st = 0;
-    rc = gpt_sgld_session_fetch(s, c, w_store ? wb.data() : nullptr, U_store ? Ub.data() : nullptr,
-                                diag ? db.data() : nullptr, &st);
-    if (rc != GPT_OK) return rc;
+    GPT_TRY(gpt_sgld_session_fetch(s, c, w_store ? wb.data() : nullptr, U_store ? Ub.data() : nullptr,
+                                   diag ? db.data() : nullptr, &st));
     bad |= st != 0;
     for (int64_t z = 0; z < T; ++z) {      // (Q, C, T) and (n, r, D, C, T) column-major
       if (w_store) std::memcpy(w_store + ((size_t)z * ncls + c) * Q, wb.data() + (size_t)z * Q, 8 * Q);
@@ -137,8 +131,7 @@ extern "C" int gpt_gpnt_sgld_class_chains(const double* phi, const double* y, in
   for (int k = 0; k < nchains; ++k) status[k] = 0;
   if (R.total == 0) return GPT_OK;
   ThetaChainSet S;
-  const int rc = S.init(seeds, eps_theta, nchains, n, C, N, R, &sigma_theta, 0);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(S.init(seeds, eps_theta, nchains, n, C, N, R, &sigma_theta, 0));
   std::vector<NtcChain> ch(nchains);
   for (int k = 0; k < nchains; ++k) ch[k] = NtcChain{S.chain(k)};
   DevMem dphi, dy, dch;
@@ -166,10 +159,8 @@ extern "C" int gpt_gpnt_sgld_class(const double* phi, const double* y, int64_t n
     set_error("GPNT_SGLDclass: C = max(y) - min(y) + 1 must be in 1..32"); return GPT_ERR_BAD_DIMS;
   }
   int32_t st = 0;
-  const int rc = gpt_gpnt_sgld_class_chains(phi, y, n, N, (int64_t)Cd, sigma_theta, m, &eps_theta,
-                                            decay_rate, burnin, maxepoch, &seed, 1, 1, theta_store,
-                                            &st);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(gpt_gpnt_sgld_class_chains(phi, y, n, N, (int64_t)Cd, sigma_theta, m, &eps_theta,
+                                     decay_rate, burnin, maxepoch, &seed, 1, 1, theta_store, &st));
   if (st) { set_error("Get NaN in theta. Try smaller epsilon"); return GPT_ERR_NAN_THETA; }
   return GPT_OK;
 }
@@ -252,10 +243,9 @@ static int class_eval_to_host(const double* dscores, const int32_t* ytest, int64
   GPT_HIPCHK(dms.alloc<double>((size_t)Ntest * C));
   GPT_HIPCHK(dpr.alloc<int32_t>((size_t)Ntest));
   GPT_HIPCHK(dnp.alloc<double>((size_t)Ntest));
-  const int rc = class_eval_core(dscores, dy.as<int32_t>(), Ntest, C, T, avg_first, avg_last,
-                                 dpm.as<double>(), dnl.as<double>(), davg.as<double>(),
-                                 dms.as<double>(), dpr.as<int32_t>(), dnp.as<double>(), nullptr);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(class_eval_core(dscores, dy.as<int32_t>(), Ntest, C, T, avg_first, avg_last,
+                          dpm.as<double>(), dnl.as<double>(), davg.as<double>(), dms.as<double>(),
+                          dpr.as<int32_t>(), dnp.as<double>(), nullptr));
   GPT_HIPCHK(dpm.download(prop_missed, (size_t)T));
   GPT_HIPCHK(dnl.download(mean_nlp, (size_t)T));
   GPT_HIPCHK(davg.download(avg, 2));
@@ -305,10 +295,9 @@ extern "C" int gpt_gpnt_pred_class(const double* theta, const double* phitest, c
     if (e != hipSuccess) return hip_fail(e, "nt_scores kernel");
     tm.stop();
   }
-  const int rc = class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
-                                    prop_missed_out, mean_nlp_out, avg_out, mean_scores_out,
-                                    prediction_out, nlp_out);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
+                             prop_missed_out, mean_nlp_out, avg_out, mean_scores_out,
+                             prediction_out, nlp_out));
   if (scores_out) GPT_HIPCHK(ds.download(scores_out, nscores));
   return GPT_OK;
 }
@@ -338,17 +327,15 @@ extern "C" int gpt_pred_class(const double* w, const double* U, const int32_t* I
   GPT_HIPCHK(dI.upload(I0.data(), I0.size()));
   GPT_HIPCHK(dphi.upload(phitest, (size_t)n * D * Ntest));
   GPT_HIPCHK(ds.alloc<double>(nscores));
-  int rc;
   {
     ClsTimer tm(1, nullptr);
-    rc = gpt_pred_dev(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(), n, D,
-                      Ntest, r, Q, S, ds.as<double>(), nullptr);
-    if (rc != GPT_OK) return rc;
+    GPT_TRY(gpt_pred_dev(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(), n, D,
+                         Ntest, r, Q, S, ds.as<double>(), nullptr));
     tm.stop();
   }
-  rc = class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last, prop_missed_out,
-                          mean_nlp_out, avg_out, mean_scores_out, prediction_out, nlp_out);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
+                             prop_missed_out, mean_nlp_out, avg_out, mean_scores_out,
+                             prediction_out, nlp_out));
   if (scores_out) GPT_HIPCHK(ds.download(scores_out, nscores));
   return GPT_OK;
 }

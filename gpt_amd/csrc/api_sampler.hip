@@ -24,23 +24,14 @@ static int host_sampler(const gpt_sgld_config* cfg, const double* phi, const dou
   const double* pp = dphi.as<double>();
   const double* yy = dy.as<double>();
   gpt_sgld_session* s = nullptr;
-  const int flags = ((w_store || U_store) ? 1 : 0) | (diag ? 2 : 0) | extra_flags;
-  int rc = gpt_sgld_session_create(cfg, 1, &cfg->seed, &pp, &yy, I, flags, nullptr, &s);
-  if (rc != GPT_OK) return rc;
+  const int flags = ((w_store || U_store) ? kFlagStore : 0) | (diag ? kFlagDiag : 0) | extra_flags;
+  GPT_TRY(gpt_sgld_session_create(cfg, 1, &cfg->seed, &pp, &yy, I, flags, nullptr, &s));
   SessionGuard guard(s, gpt_sgld_session_destroy);
-  if (rms_eps > 0) {
-    rc = gpt_sgld_session_set_rmsprop(s, rms_eps, rms_alpha);
-    if (rc != GPT_OK) return rc;
-  }
-  if (w_init || U_init) {
-    rc = session_set_state(s, 0, w_init, U_init);
-    if (rc != GPT_OK) return rc;
-  }
-  rc = gpt_sgld_session_run(s, session_run_info(s).total_steps);
-  if (rc != GPT_OK) return rc;
+  if (rms_eps > 0) GPT_TRY(gpt_sgld_session_set_rmsprop(s, rms_eps, rms_alpha));
+  if (w_init || U_init) GPT_TRY(session_set_state(s, 0, w_init, U_init));
+  GPT_TRY(gpt_sgld_session_run(s, session_run_info(s).total_steps));
   int32_t st = 0;
-  rc = gpt_sgld_session_fetch(s, 0, w_store, U_store, diag, &st);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(gpt_sgld_session_fetch(s, 0, w_store, U_store, diag, &st));
   if (st) {
     set_error("Get NaN when moving along Geodesic. Try smaller epsU");
     return GPT_ERR_NAN_GEODESIC;
@@ -63,20 +54,14 @@ static int run_and_fetch_chains(gpt_sgld_session* s, const gpt_sgld_config* cfg,
                                 const double* epsw, const double* epsU, const double* signal_var,
                                 double* const* w_store, double* const* U_store, int32_t* status) {
   SessionGuard guard(s, gpt_sgld_session_destroy);
-  int rc = GPT_OK;
   if (epsw || epsU || signal_var)
-    for (int c = 0; c < nchains; ++c) {
-      rc = gpt_sgld_session_set_hyper(s, c, epsw ? epsw[c] : cfg->epsw, epsU ? epsU[c] : cfg->epsU,
-                                      signal_var ? signal_var[c] : cfg->signal_var, cfg->sigma_w);
-      if (rc != GPT_OK) return rc;
-    }
-  rc = gpt_sgld_session_run(s, session_run_info(s).total_steps);
-  if (rc != GPT_OK) return rc;
-  for (int c = 0; c < nchains; ++c) {
-    rc = gpt_sgld_session_fetch(s, c, w_store ? w_store[c] : nullptr, U_store ? U_store[c] : nullptr,
-                                nullptr, &status[c]);
-    if (rc != GPT_OK) return rc;
-  }
+    for (int c = 0; c < nchains; ++c)
+      GPT_TRY(gpt_sgld_session_set_hyper(s, c, epsw ? epsw[c] : cfg->epsw, epsU ? epsU[c] : cfg->epsU,
+                                         signal_var ? signal_var[c] : cfg->signal_var, cfg->sigma_w));
+  GPT_TRY(gpt_sgld_session_run(s, session_run_info(s).total_steps));
+  for (int c = 0; c < nchains; ++c)
+    GPT_TRY(gpt_sgld_session_fetch(s, c, w_store ? w_store[c] : nullptr,
+                                   U_store ? U_store[c] : nullptr, nullptr, &status[c]));
   return GPT_OK;
 }
 
@@ -110,9 +95,8 @@ extern "C" int gpt_sgld_regression_chains(const gpt_sgld_config* cfg, int32_t nc
     GPT_HIPCHK(upload_once(uc, y[c], (size_t)cfg->N, &dy[c]));
   }
   gpt_sgld_session* s = nullptr;
-  const int rc = gpt_sgld_session_create(cfg, nchains, seeds, dphi.data(), dy.data(), I,
-                                         stores ? 1 : 0, nullptr, &s);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(gpt_sgld_session_create(cfg, nchains, seeds, dphi.data(), dy.data(), I,
+                                  stores ? kFlagStore : 0, nullptr, &s));
   return run_and_fetch_chains(s, cfg, nchains, epsw, epsU, signal_var, w_store, U_store, status);
 }
 
@@ -131,7 +115,7 @@ extern "C" int gpt_sgld_regression_chains_x(const gpt_sgld_config* cfg, int32_t 
   if (!status) { set_error("gpt_sgld_regression_chains_x: null status"); return GPT_ERR_BAD_DIMS; }
   const bool stores = w_store || U_store;
   if (!valid_x_args(cfg, nchains, seeds, X, y, length_scale, ls_len, sigma_rbf, Z, b, I,
-                    stores ? 1 : 0))
+                    stores ? kFlagStore : 0))
     return GPT_ERR_BAD_DIMS;
   for (int c = 0; c < nchains; ++c)
     if ((w_store && !w_store[c]) || (U_store && !U_store[c])) {
@@ -152,10 +136,8 @@ extern "C" int gpt_sgld_regression_chains_x(const gpt_sgld_config* cfg, int32_t 
   std::vector<const double*> dy(nchains);
   for (int c = 0; c < nchains; ++c) GPT_HIPCHK(upload_once(uc, y[c], N, &dy[c]));
   gpt_sgld_session* s = nullptr;
-  const int rc = gpt_sgld_session_create_x(cfg, nchains, seeds, dX, dy.data(), dls, ls_len,
-                                           sigma_rbf, phi_scale, dZ, db, I, stores ? 1 : 0, nullptr,
-                                           &s);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(gpt_sgld_session_create_x(cfg, nchains, seeds, dX, dy.data(), dls, ls_len, sigma_rbf,
+                                    phi_scale, dZ, db, I, stores ? kFlagStore : 0, nullptr, &s));
   return run_and_fetch_chains(s, cfg, nchains, epsw, epsU, signal_var, w_store, U_store, status);
 }
 
@@ -164,7 +146,8 @@ extern "C" int gpt_sgld_rmsprop(const gpt_sgld_config* cfg, double epsilon, doub
                                 const double* w_init, const double* U_init, double* w_store,
                                 double* U_store, double* diag) {
   if (!(epsilon > 0)) { set_error("RMSprop needs epsilon > 0"); return GPT_ERR_BAD_DIMS; }
-  return host_sampler(cfg, phi, y, I, w_init, U_init, w_store, U_store, diag, 4, epsilon, alpha);
+  return host_sampler(cfg, phi, y, I, w_init, U_init, w_store, U_store, diag, kFlagGrid, epsilon,
+                      alpha);
 }
 
 extern "C" int gpt_sgld_wonly(const gpt_sgld_config* cfg, const double* phi, const double* y,
@@ -174,7 +157,8 @@ extern "C" int gpt_sgld_wonly(const gpt_sgld_config* cfg, const double* phi, con
     set_error("GPT_SGLDERMw: U is a uniform Stiefel draw and w takes SGLD steps (stiefel = langevin = 1)");
     return GPT_ERR_BAD_DIMS;
   }
-  return host_sampler(cfg, phi, y, I, w_init, U_init, w_store, nullptr, diag, 16, 0.0, 0.0, U_out);
+  return host_sampler(cfg, phi, y, I, w_init, U_init, w_store, nullptr, diag, kFlagWonly, 0.0, 0.0,
+                      U_out);
 }
 
 extern "C" int gpt_gpnt_sgld(const double* phi, const double* y, int64_t n, int64_t N,

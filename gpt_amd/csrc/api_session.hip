@@ -53,6 +53,25 @@ struct gpt_sgld_session {
   DevMem view_d, xcoef;
   std::vector<ChainDesc> view_h;
   long long stage_bytes = 0;          // ring + view bytes per chain (gpt_sgld_session_staging)
+
+  // Destroy every captured graph (after the stream has drained: a launched graph may still run).
+  void drop_graphs() {
+    if (graphs.empty()) return;
+    (void)hipStreamSynchronize(stream);
+    for (auto& g : graphs) {
+      (void)hipGraphExecDestroy(g.x);
+      (void)hipGraphDestroy(g.g);
+    }
+    graphs.clear();
+  }
+  // Also the end of a creation that failed midway: the stream has drained before the members
+  // free the device memory.
+  ~gpt_sgld_session() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    drop_graphs();
+    for (auto e : inflight) if (e) (void)hipEventDestroy(e);
+    if (own_stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 // The ChainDesc array the step engines read.
@@ -60,14 +79,16 @@ static const ChainDesc* engine_chains(const gpt_sgld_session* s) {
   return s->xmode ? s->view_d.as<ChainDesc>() : s->chains_d.as<ChainDesc>();
 }
 
-// Engine choice: store_flags bit 2 (or bit 4 / 5, w-only steps / classification) forces the grid
-// engine (sgld.hip), bit 3 the chain engine (chain.hip), bit 7 the wave engine (wave.hip);
+// Engine choice: kFlagGrid (or kFlagWonly / kFlagCls, w-only steps / classification) forces the grid
+// engine (sgld.hip), kFlagChain the chain engine (chain.hip), kFlagWave the wave engine (wave.hip);
 // otherwise GPTSGLD_ENGINE=grid|chain|wave; otherwise the chain engine whenever it supports the
 // shape, else the wave engine (ranks past the chain engine), else the grid engine.  Few chains
 // of a chain-engine shape go to the grid engine (D+1 workgroups per chain: the shorter step) as
 // long as every chain's workgroups fit the GPU at once.  (Engine 2, the round-3 split engine —
 // the grid engine with the batch in slices and an in-kernel barrier — measured slower at every
-// slice count and was removed in round 4; bit 6 / "split" are rejected.)
+// slice count and was removed in round 4; kFlagSplit / "split" are rejected.)  Every error here is
+// one of the arguments and comes before the first HIP call; only the automatic choice asks the
+// device, for its CU count.
 static int device_cus() {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
@@ -89,13 +110,13 @@ static int pick_engine(const gpt_sgld_config* c, const int32_t* I_host, int32_t 
       step_layout((int)c->n, (int)c->D, (int)c->r, (int)c->Q, (int)c->m).bytes <= kMaxLds;
   const bool wave_ok = wave_supported((int)c->n, (int)c->D, (int)c->r, (int)c->Q, (int)c->m,
                                       c->langevin != 0, c->stiefel != 0);
-  if (flags & 64) { set_error("the split engine (store_flags bit 6) was removed"); return GPT_ERR_BAD_DIMS; }
-  // explicit store_flags win over the environment: bits 4/16/32 (RMSprop-capable sessions, w-only
-  // steps, classification) exist only on the grid engine
+  if (flags & kFlagSplit) { set_error("the split engine (store_flags bit 6) was removed"); return GPT_ERR_BAD_DIMS; }
+  // explicit store_flags win over the environment: RMSprop-capable sessions, w-only steps and
+  // classification exist only on the grid engine
   int want = -1;
-  if (flags & (4 | 16 | 32)) want = kEngineGrid;
-  else if (flags & 8) want = kEngineChain;
-  else if (flags & 128) want = kEngineWave;
+  if (flags & (kFlagGrid | kFlagWonly | kFlagCls)) want = kEngineGrid;
+  else if (flags & kFlagChain) want = kEngineChain;
+  else if (flags & kFlagWave) want = kEngineWave;
   else if (const char* ev = std::getenv("GPTSGLD_ENGINE")) {
     if (!std::strcmp(ev, "grid")) want = kEngineGrid;
     else if (!std::strcmp(ev, "chain")) want = kEngineChain;
@@ -144,7 +165,7 @@ static void chain_runq(const std::vector<int32_t>& I0, int Q, int D, int r,
 // Steps t_local .. t_local+nsteps-1 of the sequence being enqueued (nsteps > 1 only on the chain
 // engine, within one epoch: every other kernel is one step per launch).
 static hipError_t session_launch(gpt_sgld_session* s, const StepParams& P, int t_local,
-                                 int nsteps = 1) {
+                                 int nsteps) {
   if (P.ncls)
     return launch_step_cls(P, engine_chains(s), s->nchains, s->tbase.as<long long>(),
                            t_local, s->stream);
@@ -221,21 +242,34 @@ static hipError_t session_stage_ahead(gpt_sgld_session* s, int t_local, int span
   return session_stage(s, t_local + 1, span);
 }
 
-static int session_enqueue(gpt_sgld_session* s, int count) {
+// The launches of the next `count` steps, of at most max_span steps each, and the advance of the
+// device's step counter behind them.  Every launch goes through around(i, launch): i = its first
+// step, counted from the sequence's start, and launch(P) enqueues it with the caller's StepParams.
+// What around adds sits between the stager and the step kernel, and after it.
+template <class Around>
+static int session_launches(gpt_sgld_session* s, long long count, int max_span, Around&& around) {
   s->ran = true;
-  for (int i = 0; i < count;) {
-    hipError_t e = session_epoch_order(s, s->steps_done + i, i);
+  for (long long i = 0; i < count;) {
+    hipError_t e = session_epoch_order(s, s->steps_done + i, (int)i);
     if (e != hipSuccess) return hip_fail(e, "launch_epoch_order");
-    const int span = session_span(s, s->steps_done + i, count - i);
-    e = session_stage_ahead(s, i, span);
+    const int span = std::min(session_span(s, s->steps_done + i, count - i), max_span);
+    e = session_stage_ahead(s, (int)i, span);
     if (e != hipSuccess) return hip_fail(e, "launch_stage_batches");
-    e = session_launch(s, s->P, i, span);
-    if (e != hipSuccess) return hip_fail(e, "launch_step");
+    GPT_TRY(around(i, [&](const StepParams& P) {
+      const hipError_t el = session_launch(s, P, (int)i, span);
+      return el == hipSuccess ? GPT_OK : hip_fail(el, "launch_step");
+    }));
     i += span;
   }
-  hipError_t e = launch_advance(s->tbase.as<long long>(), count, s->stream);
-  if (e != hipSuccess) return hip_fail(e, "launch_advance");
-  return GPT_OK;
+  const hipError_t e = launch_advance(s->tbase.as<long long>(), count, s->stream);
+  return e == hipSuccess ? GPT_OK : hip_fail(e, "launch_advance");
+}
+constexpr int kAnySpan = 1 << 30;
+
+// The plain sequence (also what a graph captures): nothing around the launches.
+static int session_enqueue(gpt_sgld_session* s, int count) {
+  return session_launches(s, count, kAnySpan,
+                          [&](long long, auto&& launch) { return launch(s->P); });
 }
 
 // The inputs an X session keeps in place of per-chain phi (gpt_sgld_session_create_x).
@@ -249,6 +283,155 @@ struct XInputs {
   const double* b;                // (n, D) device, shared
 };
 
+// The step counts of a configuration: batches per epoch, epochs, steps run and samples stored.
+struct SessionCounts { long long nb, total, nstore; int epochs; };
+static SessionCounts session_counts(const gpt_sgld_config* c) {
+  SessionCounts k{};
+  k.nb = (c->N + c->m - 1) / c->m;
+  k.epochs = (int)(c->burnin + c->maxepoch);
+  k.total = (long long)k.epochs * k.nb;
+  if (c->max_steps > 0) k.total = std::min<long long>(k.total, c->max_steps);
+  k.nstore = (c->maxepoch * k.nb) / c->store_every;
+  return k;
+}
+
+// StepParams of the session's configuration (s->P starts zeroed: no RMSprop, no diagnostics
+// buffers) and the tables of its engine on the device.
+static int session_step_params(gpt_sgld_session* s, const std::vector<int32_t>& I0, int32_t flags) {
+  const gpt_sgld_config& c = s->cfg;
+  const int n = (int)c.n, D = (int)c.D, r = (int)c.r, Q = (int)c.Q, m = (int)c.m;
+  StepParams& P = s->P;
+  P.n = n; P.D = D; P.N = (int)c.N; P.r = r; P.Q = Q; P.m = m; P.nb = (int)s->numbatches;
+  P.burnin_steps = (int)(c.burnin * s->numbatches);
+  P.total_steps = s->total_steps;
+  P.store_every = (int)c.store_every;
+  P.langevin = c.langevin; P.stiefel = c.stiefel;
+  P.wonly = (flags & kFlagWonly) ? 1 : 0;
+  P.ncls = (flags & kFlagCls) ? s->nchains : 0;
+  GPT_HIPCHK(s->I0.upload(I0.data(), I0.size()));
+  P.I0 = s->I0.as<int32_t>();
+  if (s->engine == kEngineChain) {
+    std::vector<int32_t> rq;
+    chain_runq(I0, Q, D, r, rq);
+    GPT_HIPCHK(s->runq.upload(rq.data(), rq.size()));
+    P.runq = s->runq.as<int32_t>();
+  } else if (s->engine == kEngineWave) {
+    std::vector<uint16_t> wt;
+    wave_tables(I0, Q, D, r, m, wt);
+    GPT_HIPCHK(s->wvtab.upload(wt.data(), wt.size()));
+    P.wvtab = s->wvtab.as<uint16_t>();
+  } else if (step_layout(n, D, r, Q, m).vcols) {
+    std::vector<int32_t> vt;
+    vphase_cols_tables(I0, n, D, r, Q, m, vt);
+    GPT_HIPCHK(s->vtab.upload(vt.data(), vt.size()));
+    P.vtab = s->vtab.as<int32_t>();
+  }
+  return GPT_OK;
+}
+
+// X mode: the steps per launch, the stager's parameters (but o_rows: the block layout gives it)
+// and the chains' feature scales.
+static int session_x_setup(gpt_sgld_session* s, const XInputs& x) {
+  const StepParams& P = s->P;
+  s->xmode = true;
+  s->xspan = s->engine == kEngineChain ? kXSpanCap : 1;
+  if (const char* ev = std::getenv("GPTSGLD_XSPAN")) {   // measurement (scripts/time_xmode.py)
+    const int v = std::atoi(ev);
+    if (s->engine == kEngineChain && (v == 4 || v == 8 || v == 16)) s->xspan = v;
+  }
+  const size_t KR = (size_t)s->xspan + 1;
+  s->stage_bytes = (long long)(KR * P.m * (8 * (size_t)P.n * P.D + 8 + 4) + 4 * 2 * (size_t)P.N);
+  StageParams& S = s->S;
+  S.X = x.X; S.Z = x.Z; S.b = x.b; S.ls = x.ls; S.ls_len = x.ls_len;
+  S.N = P.N; S.n = P.n; S.D = P.D; S.m = P.m; S.nb = P.nb; S.KR = (int)KR;
+  S.total_steps = s->total_steps;
+  std::vector<double> cf(s->nchains);                    // c of gpt_feature, per chain
+  for (int c = 0; c < s->nchains; ++c)
+    cf[c] = x.phi_scale * std::pow(x.sigma_rbf[c], 1.0 / (double)P.D) * std::sqrt(2.0 / (double)P.n);
+  GPT_HIPCHK(s->xcoef.upload(cf.data(), cf.size()));
+  S.cfeat = s->xcoef.as<double>();
+  s->view_h.resize(s->nchains);
+  return GPT_OK;
+}
+
+// A chain's device block, one allocation: the arrays of its descriptor in this order, each on a
+// 256-byte boundary.  X mode appends the feature ring (KR batch slots of m rows: the chain
+// engine's LDS-DMA takes 16-byte pieces), the target ring, the staged row numbers and the order
+// view; the three the engines read come back in ring.phi / .y / .order.  Returned: the byte
+// offsets at which the parts that session_init_chain zero-fills begin.
+struct ChainSpans { size_t stores, diag, wave, x, rows, end; };
+static ChainSpans carve_chain(Carve& k, const gpt_sgld_session& s, ChainDesc& C, ChainDesc& ring) {
+  const StepParams& P = s.P;
+  const size_t Q = P.Q, N = P.N, nrD = (size_t)P.n * P.r * P.D, Drm = (size_t)P.D * P.r * P.m;
+  const bool wave = s.engine == kEngineWave;
+  ChainSpans o{};
+  C.w = k.take<double>(2 * Q);
+  C.U = k.take<double>(nrD);
+  C.temp = k.take<double>(2 * Drm);
+  C.order = k.take<int32_t>(2 * N);
+  o.stores = k.off;
+  C.w_store = s.store ? k.take<double>(Q * s.nstore) : nullptr;
+  C.U_store = s.store ? k.take<double>(nrD * s.nstore) : nullptr;
+  o.diag = k.off;
+  C.diag = s.diag ? k.take<double>((size_t)(1 + P.D) * s.total_steps) : nullptr;
+  o.wave = k.off;
+  C.coef = wave ? k.take<double>(Drm) : nullptr;
+  C.park = wave ? k.take<double>(nrD) : nullptr;
+  o.x = o.rows = k.off;
+  if (s.xmode) {
+    const size_t rows = (size_t)s.S.KR * P.m;
+    ring.phi = k.take<double>(rows * P.n * P.D);
+    ring.y = k.take<double>(rows);
+    o.rows = k.off;
+    k.take<int32_t>(rows);
+    ring.order = k.take<int32_t>(2 * N);
+  }
+  o.end = k.off;
+  return o;
+}
+
+// Chain c's hyper-parameters, in its descriptor and in the X view's copy of it.
+static void chain_set_hyper(gpt_sgld_session* s, int c, double epsw, double epsU,
+                            double signal_var, double sigma_w) {
+  for (std::vector<ChainDesc>* v : {&s->chains_h, &s->view_h}) {
+    if (v->empty()) continue;
+    ChainDesc& C = (*v)[c];
+    C.epsw = epsw; C.epsU = epsU; C.signal_var = signal_var; C.sigma_w = sigma_w;
+  }
+}
+
+// Chain c of a new session: its block (laid out as `o` counted it), the descriptor and the X view
+// on the host, the initial state, and zeros where a kernel adds to or may read before it writes.
+static int session_init_chain(gpt_sgld_session* s, int c, const ChainSpans& o, const double* phi,
+                              const double* y, uint64_t seed, std::vector<double>& w0,
+                              std::vector<double>& U0) {
+  const gpt_sgld_config& cfg = s->cfg;
+  Carve k;
+  GPT_HIPCHK(s->chain_mem.alloc(&k.base, o.end));
+  ChainDesc& C = s->chains_h[c];
+  ChainDesc ring{};
+  carve_chain(k, *s, C, ring);
+  C.phi = phi;
+  C.y = y;
+  C.status = s->status.as<int32_t>() + c;
+  C.seed = seed;
+  if (s->xmode) {
+    ChainDesc& V = s->view_h[c];
+    V = C;
+    V.phi = ring.phi; V.y = ring.y; V.order = ring.order;
+  }
+  chain_set_hyper(s, c, cfg.epsw, cfg.epsU, cfg.signal_var, cfg.sigma_w);
+  host_init_state((int)cfg.n, (int)cfg.r, (int)cfg.D, (int)cfg.Q, seed, cfg.stiefel != 0,
+                  cfg.sigma_w, w0.data(), U0.data());
+  GPT_HIPCHK(hipMemcpy(C.w, w0.data(), 8 * w0.size(), hipMemcpyHostToDevice));
+  GPT_HIPCHK(hipMemcpy(C.U, U0.data(), 8 * U0.size(), hipMemcpyHostToDevice));
+  if (s->store) GPT_HIPCHK(hipMemset(k.base + o.stores, 0, o.diag - o.stores));
+  if (s->diag) GPT_HIPCHK(hipMemset(k.base + o.diag, 0, o.wave - o.diag));
+  // every view entry is a ring row at all times: a read the engines discard stays in the ring
+  if (s->xmode) GPT_HIPCHK(hipMemset(k.base + o.x, 0, o.end - o.x));
+  return GPT_OK;
+}
+
 // A phi session (phi_dev, xin null) or an X session (xin, phi_dev null).
 static int session_create(const gpt_sgld_config* cfg, int32_t nchains, const uint64_t* seeds,
                           const double* const* phi_dev, const double* const* y_dev,
@@ -256,157 +439,51 @@ static int session_create(const gpt_sgld_config* cfg, int32_t nchains, const uin
                           const XInputs* xin, gpt_sgld_session** out) {
   if (!out) { set_error("null out"); return GPT_ERR_BAD_DIMS; }
   *out = nullptr;
+  // what needs no device: the configuration, the chain arguments, I, the engine asked for
   if (!valid_cfg(cfg)) return GPT_ERR_BAD_DIMS;
   if (nchains < 1 || !seeds || (!phi_dev && !xin) || !y_dev || !I_host) {
     set_error("bad chain arguments"); return GPT_ERR_BAD_DIMS;
   }
-  const int n = (int)cfg->n, D = (int)cfg->D, N = (int)cfg->N, r = (int)cfg->r, Q = (int)cfg->Q,
-            m = (int)cfg->m;
   std::vector<int32_t> I0;
-  if (!zero_based_I(I_host, Q, D, r, I0)) return GPT_ERR_BAD_DIMS;
-  hipError_t he = set_lds_limits();
+  if (!zero_based_I(I_host, cfg->Q, cfg->D, cfg->r, I0)) return GPT_ERR_BAD_DIMS;
+  int engine = 0;
+  GPT_TRY(pick_engine(cfg, I_host, store_flags, nchains, &engine));
+  const hipError_t he = set_lds_limits();
   if (he != hipSuccess) return hip_fail(he, "hipFuncSetAttribute");
 
   std::unique_ptr<gpt_sgld_session> s(new gpt_sgld_session());
-  {
-    const int rc = pick_engine(cfg, I_host, store_flags, nchains, &s->engine);
-    if (rc != GPT_OK) return rc;
-  }
+  const SessionCounts cnt = session_counts(cfg);
   s->cfg = *cfg;
   s->nchains = nchains;
-  s->numbatches = (N + m - 1) / m;
-  s->epochs = (int)(cfg->burnin + cfg->maxepoch);
-  s->total_steps = (long long)s->epochs * s->numbatches;
-  if (cfg->max_steps > 0) s->total_steps = std::min<long long>(s->total_steps, cfg->max_steps);
-  s->nstore = (cfg->maxepoch * s->numbatches) / cfg->store_every;
-  s->store = (store_flags & 1) != 0;
-  s->diag = (store_flags & 2) != 0;
+  s->engine = engine;
+  s->numbatches = cnt.nb; s->epochs = cnt.epochs; s->total_steps = cnt.total; s->nstore = cnt.nstore;
+  s->store = (store_flags & kFlagStore) != 0;
+  s->diag = (store_flags & kFlagDiag) != 0;
   if (hip_stream) s->stream = (hipStream_t)hip_stream;
   else {
     GPT_HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     s->own_stream = true;
   }
-  StepParams& P = s->P;
-  P.n = n; P.D = D; P.N = N; P.r = r; P.Q = Q; P.m = m; P.nb = (int)s->numbatches;
-  P.burnin_steps = (int)(cfg->burnin * s->numbatches);
-  P.total_steps = s->total_steps;
-  P.store_every = (int)cfg->store_every;
-  P.langevin = cfg->langevin; P.stiefel = cfg->stiefel;
-
-  GPT_HIPCHK(s->I0.upload(I0.data(), I0.size()));
-  P.I0 = s->I0.as<int32_t>();
-  P.runq = nullptr;
-  if (s->engine == kEngineChain) {
-    std::vector<int32_t> rq;
-    chain_runq(I0, Q, D, r, rq);
-    GPT_HIPCHK(s->runq.upload(rq.data(), rq.size()));
-    P.runq = s->runq.as<int32_t>();
-  }
-  P.wvtab = nullptr;
-  if (s->engine == kEngineWave) {
-    std::vector<uint16_t> wt;
-    wave_tables(I0, Q, D, r, m, wt);
-    GPT_HIPCHK(s->wvtab.upload(wt.data(), wt.size()));
-    P.wvtab = s->wvtab.as<uint16_t>();
-  }
-  P.vtab = nullptr;
-  if (s->engine != kEngineChain && s->engine != kEngineWave && step_layout(n, D, r, Q, m).vcols) {
-    std::vector<int32_t> vt;
-    vphase_cols_tables(I0, n, D, r, Q, m, vt);
-    GPT_HIPCHK(s->vtab.upload(vt.data(), vt.size()));
-    P.vtab = s->vtab.as<int32_t>();
-  }
-  P.stamps = nullptr;
-  P.tline = nullptr;
-  P.rms = 0; P.rms_eps = 0.0; P.rms_alpha = 0.0;
-  P.wonly = (store_flags & 16) ? 1 : 0;
-  P.ncls = (store_flags & 32) ? nchains : 0;
+  GPT_TRY(session_step_params(s.get(), I0, store_flags));
   GPT_HIPCHK(s->tbase.alloc<long long>(1));
   GPT_HIPCHK(s->tbase.zero());
   GPT_HIPCHK(s->status.alloc<int32_t>(nchains));
   GPT_HIPCHK(s->status.zero());
+  if (xin) GPT_TRY(session_x_setup(s.get(), *xin));
 
-  constexpr size_t a = 256;
-  auto up = [](size_t x) { return (x + a - 1) / a * a; };
-  const size_t b_w = up(8 * 2 * (size_t)Q), b_U = up(8 * (size_t)n * r * D),
-               b_temp = up(8 * 2 * (size_t)D * r * m),
-               b_ord = up(4 * 2 * (size_t)N),
-               b_ws = s->store ? up(8 * (size_t)Q * s->nstore) : 0,
-               b_Us = s->store ? up(8 * (size_t)n * r * D * s->nstore) : 0,
-               b_dg = s->diag ? up(8 * (size_t)(1 + D) * s->total_steps) : 0,
-               b_wv = s->engine == kEngineWave ? up(8 * (size_t)D * m * r) + up(8 * (size_t)n * r * D) : 0;
-  // X mode: per chain the feature ring (KR batch slots of m rows, 256-byte aligned: the chain
-  // engine's LDS-DMA takes 16-byte pieces), the target ring, the staged row numbers and the view
-  size_t b_ring = 0, b_yr = 0, b_rows = 0, b_view = 0;
-  if (xin) {
-    s->xmode = true;
-    s->xspan = s->engine == kEngineChain ? kXSpanCap : 1;
-    if (const char* ev = std::getenv("GPTSGLD_XSPAN")) {   // measurement (scripts/time_xmode.py)
-      const int v = std::atoi(ev);
-      if (s->engine == kEngineChain && (v == 4 || v == 8 || v == 16)) s->xspan = v;
-    }
-    const size_t KR = (size_t)s->xspan + 1;
-    b_ring = up(8 * KR * m * n * D); b_yr = up(8 * KR * m); b_rows = up(4 * KR * m);
-    b_view = up(4 * 2 * (size_t)N);
-    s->stage_bytes = (long long)(KR * m * (8 * (size_t)n * D + 8 + 4) + 4 * 2 * (size_t)N);
-    StageParams& S = s->S;
-    S.X = xin->X; S.Z = xin->Z; S.b = xin->b; S.ls = xin->ls; S.ls_len = xin->ls_len;
-    S.N = N; S.n = n; S.D = D; S.m = m; S.nb = (int)s->numbatches; S.KR = (int)KR;
-    S.total_steps = s->total_steps;
-    S.o_rows = b_ring + b_yr;
-    // c of gpt_feature, per chain
-    std::vector<double> cf(nchains);
-    for (int c = 0; c < nchains; ++c)
-      cf[c] = xin->phi_scale * std::pow(xin->sigma_rbf[c], 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
-    GPT_HIPCHK(s->xcoef.upload(cf.data(), cf.size()));
-    S.cfeat = s->xcoef.as<double>();
-    s->view_h.resize(nchains);
-  }
-  const size_t b_x = b_ring + b_yr + b_rows + b_view;
-  std::vector<double> w0(Q), U0((size_t)n * r * D);
+  // one allocation per chain: the layout is counted once, then handed out chain by chain
+  Carve count;
+  ChainDesc unused{};
+  const ChainSpans o = carve_chain(count, *s, unused, unused);
+  s->S.o_rows = o.rows - o.x;
+  std::vector<double> w0((size_t)cfg->Q), U0((size_t)(cfg->n * cfg->r * cfg->D));
   s->chains_h.resize(nchains);
-  for (int c = 0; c < nchains; ++c) {
-    char* base = nullptr;
-    GPT_HIPCHK(s->chain_mem.alloc(&base, b_w + b_U + b_temp + b_ord + b_ws + b_Us + b_dg + b_wv + b_x));
-    ChainDesc& C = s->chains_h[c];
-    C.phi = xin ? nullptr : phi_dev[c];
-    C.y = y_dev[c];
-    C.w = (double*)base;
-    C.U = (double*)(base + b_w);
-    C.temp = (double*)(base + b_w + b_U);
-    C.order = (int32_t*)(base + b_w + b_U + b_temp);
-    C.w_store = s->store ? (double*)(base + b_w + b_U + b_temp + b_ord) : nullptr;
-    C.U_store = s->store ? (double*)(base + b_w + b_U + b_temp + b_ord + b_ws) : nullptr;
-    C.diag = s->diag ? (double*)(base + b_w + b_U + b_temp + b_ord + b_ws + b_Us) : nullptr;
-    C.status = s->status.as<int32_t>() + c;
-    C.seed = seeds[c];
-    C.gw = C.gU = C.res = nullptr;
-    C.coef = C.park = nullptr;
-    if (b_wv) {
-      char* wv = base + b_w + b_U + b_temp + b_ord + b_ws + b_Us + b_dg;
-      C.coef = (double*)wv;
-      C.park = (double*)(wv + up(8 * (size_t)D * m * r));
-    }
-    C.epsw = cfg->epsw; C.epsU = cfg->epsU; C.signal_var = cfg->signal_var; C.sigma_w = cfg->sigma_w;
-    host_init_state(n, r, D, Q, seeds[c], cfg->stiefel != 0, cfg->sigma_w, w0.data(), U0.data());
-    GPT_HIPCHK(hipMemcpy(C.w, w0.data(), 8 * (size_t)Q, hipMemcpyHostToDevice));
-    GPT_HIPCHK(hipMemcpy(C.U, U0.data(), 8 * U0.size(), hipMemcpyHostToDevice));
-    if (s->store) GPT_HIPCHK(hipMemset(C.w_store, 0, b_ws + b_Us));
-    if (s->diag) GPT_HIPCHK(hipMemset(C.diag, 0, b_dg));
-    if (xin) {
-      char* xb = base + b_w + b_U + b_temp + b_ord + b_ws + b_Us + b_dg + b_wv;
-      // every view entry is a ring row at all times: a read the engines discard stays in the ring
-      GPT_HIPCHK(hipMemset(xb, 0, b_x));
-      ChainDesc& V = s->view_h[c];
-      V = C;
-      V.phi = (const double*)xb;
-      V.y = (const double*)(xb + b_ring);
-      V.order = (int32_t*)(xb + b_ring + b_yr + b_rows);
-    }
-  }
+  for (int c = 0; c < nchains; ++c)
+    GPT_TRY(session_init_chain(s.get(), c, o, xin ? nullptr : phi_dev[c], y_dev[c], seeds[c], w0, U0));
   GPT_HIPCHK(s->chains_d.upload(s->chains_h.data(), s->chains_h.size()));
   if (xin) GPT_HIPCHK(s->view_d.upload(s->view_h.data(), s->view_h.size()));
   // order_0 of every chain (the first step builds order_1, session_epoch_order)
+  const int N = (int)cfg->N;
   if (const size_t wsi = epoch_order_ws_ints(N, nchains)) GPT_HIPCHK(s->ord_ws.alloc<int32_t>(wsi));
   GPT_HIPCHK(launch_epoch_order(s->chains_d.as<ChainDesc>(), nchains, N, (int)s->numbatches,
                                 s->total_steps, s->tbase.as<long long>(), 0, 0,
@@ -472,7 +549,7 @@ bool valid_x_args(const gpt_sgld_config* cfg, int32_t nchains, const uint64_t* s
   }
   for (int c = 0; c < nchains; ++c)
     if (!y[c]) { set_error("X mode: null per-chain y"); return false; }
-  if (store_flags & ~(1 | 2 | 4 | 8 | 128)) {
+  if (store_flags & ~(kFlagStore | kFlagDiag | kFlagGrid | kFlagChain | kFlagWave)) {
     set_error("X mode runs the regression steps of the grid, chain and wave engines (store_flags "
               "bits 2, 3, 7): no w-only, classification or split-engine sessions");
     return false;
@@ -533,26 +610,13 @@ extern "C" int gpt_sgld_session_set_hyper(gpt_sgld_session* s, int32_t chain, do
                                           double epsU, double signal_var, double sigma_w) {
   if (!s || chain < 0 || chain >= s->nchains) { set_error("bad chain"); return GPT_ERR_BAD_DIMS; }
   if (!(signal_var > 0) || !(sigma_w > 0)) { set_error("variances must be > 0"); return GPT_ERR_BAD_DIMS; }
-  ChainDesc& C = s->chains_h[chain];
-  C.epsw = epsw; C.epsU = epsU; C.signal_var = signal_var; C.sigma_w = sigma_w;
-  GPT_HIPCHK(hipMemcpy(s->chains_d.as<ChainDesc>() + chain, &C, sizeof(ChainDesc), hipMemcpyHostToDevice));
-  if (s->xmode) {                          // the engines read the view's copy
-    ChainDesc& V = s->view_h[chain];
-    V.epsw = epsw; V.epsU = epsU; V.signal_var = signal_var; V.sigma_w = sigma_w;
-    GPT_HIPCHK(hipMemcpy(s->view_d.as<ChainDesc>() + chain, &V, sizeof(ChainDesc), hipMemcpyHostToDevice));
-  }
+  chain_set_hyper(s, chain, epsw, epsU, signal_var, sigma_w);
+  GPT_HIPCHK(hipMemcpy(s->chains_d.as<ChainDesc>() + chain, &s->chains_h[chain], sizeof(ChainDesc),
+                       hipMemcpyHostToDevice));
+  if (s->xmode)                            // the engines read the view's copy
+    GPT_HIPCHK(hipMemcpy(s->view_d.as<ChainDesc>() + chain, &s->view_h[chain], sizeof(ChainDesc),
+                         hipMemcpyHostToDevice));
   return GPT_OK;
-}
-
-// Destroy every captured graph (after the stream has drained: a launched graph may still run).
-static void session_drop_graphs(gpt_sgld_session* s) {
-  if (s->graphs.empty()) return;
-  (void)hipStreamSynchronize(s->stream);
-  for (auto& g : s->graphs) {
-    (void)hipGraphExecDestroy(g.x);
-    (void)hipGraphDestroy(g.g);
-  }
-  s->graphs.clear();
 }
 
 extern "C" int gpt_sgld_session_set_rmsprop(gpt_sgld_session* s, double epsilon, double alpha) {
@@ -570,12 +634,11 @@ extern "C" int gpt_sgld_session_set_rmsprop(gpt_sgld_session* s, double epsilon,
   if (!(epsilon > 0) || !(alpha >= 0 && alpha < 1)) {
     set_error("RMSprop needs epsilon > 0 and 0 <= alpha < 1"); return GPT_ERR_BAD_DIMS;
   }
-  const int rc = session_alloc_aux(s);     // moving averages start at 0 (:1143-1144)
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(session_alloc_aux(s));           // moving averages start at 0 (:1143-1144)
   s->P.rms = 1; s->P.rms_eps = epsilon; s->P.rms_alpha = alpha;
   // graphs prepared before this call (gpt_sgld_session_prepare) captured plain SGLD steps: drop
   // them so the next run captures RMSprop steps
-  session_drop_graphs(s);
+  s->drop_graphs();
   return GPT_OK;
 }
 
@@ -638,15 +701,9 @@ extern "C" int gpt_sgld_session_run(gpt_sgld_session* s, int64_t nsteps) {
   if (!s) { set_error("null session"); return GPT_ERR_BAD_DIMS; }
   long long remaining = std::min<long long>(nsteps, s->total_steps - s->steps_done);
   if (remaining <= 0) return GPT_OK;
-  {
-    const int rc = session_prime(s);
-    if (rc != GPT_OK) return rc;
-  }
+  GPT_TRY(session_prime(s));
   while (remaining > 0) {
-    {
-      const int rc = session_throttle(s);
-      if (rc != GPT_OK) return rc;
-    }
+    GPT_TRY(session_throttle(s));
     const int chunk = session_next_chunk(s, remaining, s->steps_done);
     // a whole canonical chunk, or any chunk prepared beforehand (gpt_sgld_session_prepare), runs as
     // one graph; other partial chunks are launched directly
@@ -655,20 +712,15 @@ extern "C" int gpt_sgld_session_run(gpt_sgld_session* s, int64_t nsteps) {
     for (auto& g : s->graphs) cached |= (g.b0 == b0 && g.len == chunk);
     if (chunk == s->graph_steps || cached) {
       hipGraphExec_t x = nullptr;
-      const int rc = session_graph(s, chunk, &x);
-      if (rc != GPT_OK) return rc;
+      GPT_TRY(session_graph(s, chunk, &x));
       GPT_HIPCHK(hipGraphLaunch(x, s->stream));
       s->ran = true;
     } else {
-      const int rc = session_enqueue(s, chunk);
-      if (rc != GPT_OK) return rc;
+      GPT_TRY(session_enqueue(s, chunk));
     }
     s->steps_done += chunk;
     remaining -= chunk;
-    {
-      const int rc = session_mark(s);
-      if (rc != GPT_OK) return rc;
-    }
+    GPT_TRY(session_mark(s));
   }
   return GPT_OK;
 }
@@ -696,41 +748,28 @@ extern "C" int gpt_sgld_session_time_steps(gpt_sgld_session* s, int64_t nsteps, 
   const long long cnt = std::min<long long>(nsteps, s->total_steps - s->steps_done);
   if (avg_us) *avg_us = 0.0;
   if (cnt <= 0) return GPT_OK;
-  {
-    const int rc = session_prime(s);
-    if (rc != GPT_OK) return rc;
-  }
+  GPT_TRY(session_prime(s));
   ScopedEvents evs;
   GPT_HIPCHK(evs.create(2 * cnt));
   std::vector<hipEvent_t>& ev = evs.e;
-  int rc = GPT_OK;
-  s->ran = true;
-  // one event pair per launch (a launch runs `span` steps on the chain engine)
+  // one event pair per launch (a launch runs `span` steps on the chain engine), around the step
+  // kernel alone: the epoch order and the stager's call stay outside it
   long long nl = 0;
-  for (long long i = 0; i < cnt && rc == GPT_OK; ++nl) {
-    hipError_t eo = session_epoch_order(s, s->steps_done + i, (int)i);   // outside the event pair
-    if (eo != hipSuccess) return hip_fail(eo, "launch_epoch_order");
-    const int span = session_span(s, s->steps_done + i, cnt - i);
-    eo = session_stage_ahead(s, (int)i, span);                           // likewise
-    if (eo != hipSuccess) return hip_fail(eo, "launch_stage_batches");
+  const int rc = session_launches(s, cnt, kAnySpan, [&](long long, auto&& launch) {
     GPT_HIPCHK(hipEventRecord(ev[2 * nl], s->stream));
-    hipError_t e = session_launch(s, s->P, (int)i, span);
-    if (e != hipSuccess) rc = hip_fail(e, "launch_step");
+    GPT_TRY(launch(s->P));
     GPT_HIPCHK(hipEventRecord(ev[2 * nl + 1], s->stream));
-    i += span;
-  }
-  if (rc == GPT_OK) {
-    hipError_t e = launch_advance(s->tbase.as<long long>(), cnt, s->stream);
-    if (e != hipSuccess) rc = hip_fail(e, "launch_advance");
-  }
+    ++nl;
+    return (int)GPT_OK;
+  });
   GPT_HIPCHK(hipStreamSynchronize(s->stream));
+  if (rc != GPT_OK) return rc;
   double tot = 0.0;
   for (long long i = 0; i < nl; ++i) {
     float ms = 0.f;
     GPT_HIPCHK(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
     tot += ms;
   }
-  if (rc != GPT_OK) return rc;
   s->steps_done += cnt;
   if (avg_us) *avg_us = 1000.0 * tot / (double)cnt;
   return GPT_OK;
@@ -741,26 +780,17 @@ extern "C" int gpt_sgld_session_stamps(gpt_sgld_session* s, int64_t nsteps, int6
   if (s->xmode) { set_error("stamps are not available on an X session"); return GPT_ERR_BAD_DIMS; }
   const long long cnt = std::min<long long>(nsteps, s->total_steps - s->steps_done);
   if (cnt <= 0) return GPT_OK;
-  {
-    const int rc = session_prime(s);
-    if (rc != GPT_OK) return rc;
-  }
+  GPT_TRY(session_prime(s));
   // one slot row per workgroup of a step: D+1 per chain
   const size_t per = (size_t)(s->P.D + 1) * s->nchains * kStamps;
   DevMem buf;
   GPT_HIPCHK(buf.alloc<int64_t>(per * cnt));
   GPT_HIPCHK(buf.zero());
   StepParams P = s->P;
-  s->ran = true;
-  for (long long i = 0; i < cnt; ++i) {
+  GPT_TRY(session_launches(s, cnt, 1, [&](long long i, auto&& launch) {   // a launch per step
     P.stamps = buf.as<long long>() + per * i;
-    hipError_t eo = session_epoch_order(s, s->steps_done + i, (int)i);
-    if (eo != hipSuccess) return hip_fail(eo, "launch_epoch_order");
-    hipError_t e = session_launch(s, P, (int)i);
-    if (e != hipSuccess) return hip_fail(e, "launch_step");
-  }
-  hipError_t e = launch_advance(s->tbase.as<long long>(), cnt, s->stream);
-  if (e != hipSuccess) return hip_fail(e, "launch_advance");
+    return launch(P);
+  }));
   GPT_HIPCHK(hipStreamSynchronize(s->stream));
   GPT_HIPCHK(buf.download(out, per * cnt));
   s->steps_done += cnt;
@@ -786,22 +816,17 @@ extern "C" int gpt_sgld_session_timeline(gpt_sgld_session* s, int64_t nsteps, in
   GPT_HIPCHK(hipMemsetAsync(buf.p, 0, buf.bytes, s->stream));
   StepParams P = s->P;
   P.tline = buf.as<long long>();
-  s->ran = true;
-  hipError_t eo = session_epoch_order(s, s->steps_done, 0);
-  if (eo != hipSuccess) return hip_fail(eo, "launch_epoch_order");
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  GPT_HIPCHK(hipEventCreate(&e0));
-  GPT_HIPCHK(hipEventCreate(&e1));
-  hipError_t e = hipEventRecord(e0, s->stream);
-  if (e == hipSuccess) e = session_launch(s, P, 0, (int)nsteps);
-  if (e == hipSuccess) e = hipEventRecord(e1, s->stream);
-  if (e == hipSuccess) e = launch_advance(s->tbase.as<long long>(), nsteps, s->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  ScopedEvents evs;
+  GPT_HIPCHK(evs.create(2));
+  GPT_TRY(session_launches(s, nsteps, kAnySpan, [&](long long, auto&& launch) {   // the one launch
+    GPT_HIPCHK(hipEventRecord(evs.e[0], s->stream));
+    GPT_TRY(launch(P));
+    GPT_HIPCHK(hipEventRecord(evs.e[1], s->stream));
+    return (int)GPT_OK;
+  }));
+  GPT_HIPCHK(hipStreamSynchronize(s->stream));
   float ms = 0.f;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (e != hipSuccess) return hip_fail(e, "timeline launch");
+  GPT_HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
   if (event_us) *event_us = 1000.0 * ms;
   GPT_HIPCHK(buf.download(out, per));
   s->steps_done += nsteps;
@@ -891,14 +916,7 @@ extern "C" int gpt_sgld_session_fetch(gpt_sgld_session* s, int32_t chain, double
   return GPT_OK;
 }
 
-extern "C" void gpt_sgld_session_destroy(gpt_sgld_session* s) {
-  if (!s) return;
-  (void)hipStreamSynchronize(s->stream);
-  session_drop_graphs(s);
-  for (auto e : s->inflight) if (e) (void)hipEventDestroy(e);
-  if (s->own_stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
+extern "C" void gpt_sgld_session_destroy(gpt_sgld_session* s) { delete s; }
 
 // ====================================================================== test entries
 // expm of `count` row-major nn × nn host matrices on the device, by the wave engine's

@@ -23,6 +23,17 @@ constexpr int kEngineGrid = 0;     // sgld.hip: grid (D+1, chains), two batch re
 constexpr int kEngineChain = 1;    // chain.hip: one workgroup per chain, one batch read per step
 constexpr int kEngineWave = 3;     // wave.hip: per step a V-phase workgroup per chain, then one
                                    // wave per (chain, dimension) (ranks past the chain engine)
+// The store_flags bits of gpt_sgld_session_create (the key closes include/gptsgld.h).
+enum SessionFlag : int32_t {
+  kFlagStore = 1 << 0,             // keep w_store / U_store
+  kFlagDiag = 1 << 1,              // keep the per-step gradient norms
+  kFlagGrid = 1 << 2,              // force the grid engine (RMSprop-capable sessions)
+  kFlagChain = 1 << 3,             // force the chain engine
+  kFlagWonly = 1 << 4,             // GPT_SGLDERMw steps (grid engine)
+  kFlagCls = 1 << 5,               // GPTclassification: the chains are the classes (grid engine)
+  kFlagSplit = 1 << 6,             // the removed split engine: rejected
+  kFlagWave = 1 << 7,              // force the wave engine
+};
 
 // Per-chain device state.  All pointers are device pointers.
 struct ChainDesc {

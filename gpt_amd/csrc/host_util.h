@@ -15,6 +15,12 @@ namespace gpt {
     hipError_t _e = (call);                            \
     if (_e != hipSuccess) return hip_fail(_e, #call);  \
   } while (0)
+// Return the first GPT_* code of a callee that is not GPT_OK.
+#define GPT_TRY(call)                    \
+  do {                                   \
+    const int _rc = (call);              \
+    if (_rc != GPT_OK) return _rc;       \
+  } while (0)
 
 // Owner of one device allocation.  Sizes are element counts of T: the byte count of a buffer is
 // formed once, in alloc, and zero / download work from it.
@@ -60,6 +66,22 @@ struct DevSet {
   template <class T> hipError_t upload(T** out, const T* host, size_t count) {
     const hipError_t e = alloc(out, count);
     return e != hipSuccess ? e : hipMemcpy(*out, host, sizeof(T) * count, hipMemcpyHostToDevice);
+  }
+};
+
+// Carves typed arrays out of one device allocation.  Every array starts on a 256-byte boundary,
+// the alignment of a hipMalloc of its own, so a kernel may assume of a carved pointer whatever it
+// may of an allocated one.  The same take() calls run twice: without a base they count the bytes,
+// with one they hand the arrays out and copy `host` in (the first failed copy is kept in err).
+struct Carve {
+  char* base = nullptr;
+  size_t off = 0;
+  hipError_t err = hipSuccess;
+  template <class T> T* take(size_t count, const T* host = nullptr) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += (sizeof(T) * count + 255) / 256 * 256;
+    if (p && host && err == hipSuccess) err = hipMemcpy(p, host, sizeof(T) * count, hipMemcpyHostToDevice);
+    return p;
   }
 };
 

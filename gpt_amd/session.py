@@ -11,10 +11,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import SGLDConfig, check, lib
-from .GPT_SGLD import make_config
+from .GPT_SGLD import _run_counts, make_config
 
 
-# store_flags bits selecting the step engine (include/gptsgld.h, gpt_sgld_session_info)
+# store_flags bits selecting the step engine: kFlagGrid, kFlagChain and kFlagWave of enum
+# SessionFlag (gpt_amd/csrc/gpt_internal.h; include/gptsgld.h, gpt_sgld_session_info)
 ENGINES = {"auto": 0, "grid": 4, "chain": 8, "wave": 128}
 ENGINE_NAMES = {0: "grid", 1: "chain", 3: "wave"}
 
@@ -41,30 +42,39 @@ class SGLDSession:
                 raise ValueError("phi must be a contiguous float64 device tensor of torch shape "
                                  "(N, D, n) == Julia phi (n, D, N)")
         N, D, n = phis[0].shape     # torch (N, D, n) row-major == Julia (n, D, N) column-major
-        self._keep = (phis, ys)
+        pp = (C.c_void_p * nch)(*[p.data_ptr() for p in phis])
+        self._open((phis, ys), (n, D, N), ys, I, r, Q, m, epsw, epsU, signal_var, burnin, maxepoch,
+                   seeds, sigma_w, langevin, stiefel, store_every, max_steps, store, diag, stream,
+                   engine, lambda cfg, k, sd, yy, *rest: lib().gpt_sgld_session_create(
+                       cfg, k, sd, pp, yy, *rest))
+
+    def _open(self, keep, dims, ys, I, r, Q, m, epsw, epsU, signal_var, burnin, maxepoch, seeds,
+              sigma_w, langevin, stiefel, store_every, max_steps, store, diag, stream, engine, create):
+        """What __init__ and from_X share: the configuration, the seeds, the flags, the handle and
+        the step counts.  ``create(cfg, nchains, seeds, ys, I, flags, stream, handle)`` is the
+        library entry with the caller's own inputs bound."""
+        self._h = None
+        self._keep = keep
+        n, D, N = dims
         self.n, self.D, self.N, self.r, self.Q, self.m = int(n), int(D), int(N), r, Q, m
-        self.nchains = nch
+        self.nchains = nch = len(seeds)
         I = np.asfortranarray(np.asarray(I, dtype=np.int32))
         self.cfg = make_config(self.n, self.D, self.N, r, Q, m, epsw, epsU, signal_var, sigma_w,
                                burnin, maxepoch, 0, langevin, stiefel, store_every, max_steps)
-        pp = (C.c_void_p * nch)(*[p.data_ptr() for p in phis])
         yy = (C.c_void_p * nch)(*[y.data_ptr() for y in ys])
         sd = (C.c_uint64 * nch)(*[int(s) & (2 ** 64 - 1) for s in seeds])
-        h = C.c_void_p()
         if engine not in ENGINES:
             raise ValueError("engine must be one of %s" % sorted(ENGINES))
         flags = (1 if store else 0) | (2 if diag else 0) | ENGINES[engine]
-        st = C.c_void_p(stream) if stream else None
-        check(lib().gpt_sgld_session_create(C.byref(self.cfg), nch, sd, pp, yy,
-                                            I.ctypes.data_as(_lib.P_I32), flags, st, C.byref(h)))
+        h = C.c_void_p()
+        check(create(C.byref(self.cfg), nch, sd, yy, I.ctypes.data_as(_lib.P_I32), flags,
+                     C.c_void_p(stream) if stream else None, C.byref(h)))
         self._h = h
         self._counts(burnin, maxepoch, store_every, max_steps)
 
     def _counts(self, burnin, maxepoch, store_every, max_steps):
-        self.numbatches = -(-self.N // self.m)
-        total = (burnin + maxepoch) * self.numbatches
-        self.total_steps = total if max_steps <= 0 else min(total, max_steps)
-        self.nstore = (maxepoch * self.numbatches) // store_every
+        self.numbatches, self.total_steps, self.nstore = _run_counts(
+            self.N, self.m, burnin, maxepoch, store_every, max_steps)
 
     @classmethod
     def from_X(cls, X, ys, length_scales, sigma_RBFs, phi_scale, Z, b, I, r, Q, m, epsw, epsU,
@@ -112,26 +122,12 @@ class SGLDSession:
         if len(ys) != nch or any(y.numel() != N for y in ys):
             raise ValueError("need one y of length N per chain or a shared one")
         self = cls.__new__(cls)
-        self._keep = (Xd, Zd, bd, lsd, ys)
-        self.n, self.D, self.N, self.r, self.Q, self.m = int(n), int(D), int(N), r, Q, m
-        self.nchains = nch
-        I = np.asfortranarray(np.asarray(I, dtype=np.int32))
-        self.cfg = make_config(self.n, self.D, self.N, r, Q, m, epsw, epsU, signal_var, sigma_w,
-                               burnin, maxepoch, 0, langevin, stiefel, store_every, max_steps)
-        yy = (C.c_void_p * nch)(*[y.data_ptr() for y in ys])
-        sd = (C.c_uint64 * nch)(*[int(s) & (2 ** 64 - 1) for s in seeds])
-        if engine not in ENGINES:
-            raise ValueError("engine must be one of %s" % sorted(ENGINES))
-        flags = (1 if store else 0) | (2 if diag else 0) | ENGINES[engine]
-        h = C.c_void_p()
-        self._h = None
-        check(lib().gpt_sgld_session_create_x(
-            C.byref(self.cfg), nch, sd, C.c_void_p(Xd.data_ptr()), yy, C.c_void_p(lsd.data_ptr()),
-            int(lsd.shape[1]), sg.ctypes.data_as(_lib.P_D), float(phi_scale),
-            C.c_void_p(Zd.data_ptr()), C.c_void_p(bd.data_ptr()), I.ctypes.data_as(_lib.P_I32),
-            flags, C.c_void_p(stream) if stream else None, C.byref(h)))
-        self._h = h
-        self._counts(burnin, maxepoch, store_every, max_steps)
+        self._open((Xd, Zd, bd, lsd, ys), (n, D, N), ys, I, r, Q, m, epsw, epsU, signal_var, burnin,
+                   maxepoch, seeds, sigma_w, langevin, stiefel, store_every, max_steps, store, diag,
+                   stream, engine, lambda cfg, k, sd, yy, *rest: lib().gpt_sgld_session_create_x(
+                       cfg, k, sd, C.c_void_p(Xd.data_ptr()), yy, C.c_void_p(lsd.data_ptr()),
+                       int(lsd.shape[1]), sg.ctypes.data_as(_lib.P_D), float(phi_scale),
+                       C.c_void_p(Zd.data_ptr()), C.c_void_p(bd.data_ptr()), *rest))
         return self
 
     def staging(self):
