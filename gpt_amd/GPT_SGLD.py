@@ -883,6 +883,103 @@ def predictive_last_timing():
     return float(out[0])
 
 
+# ------------------------------------------------------------------ chain diagnostics of a store
+class ChainDiag:
+    """Diagnostics of a store x[p, s, m] over a window of S samples of M chains (diag.hip), per
+    parameter (or test row) p:
+
+    ``mean``, ``sd``   the mean of the chain means and sqrt(var+), var+ = W·(S−1)/S + B/S
+    ``rhat``           split R-hat: every chain's first and last ⌊S/2⌋ samples as 2M sequences
+    ``acf``            (P, K+1), with ``acf=True``: the combined autocorrelation ρ̂_k of BDA3 §11.5
+    ``tau``, ``ess``, ``mcse``   Geyer's initial-monotone-sequence autocorrelation time (at least
+                       1/log10(M·S)), M·S/tau and sd/sqrt(ess)
+    ``truncated``      1 where the K lags ran out before a pair of autocorrelations summed to <= 0:
+                       ``ess`` is then an upper bound (max_lag too small, or chains that disagree)
+    ``chain_mean``, ``chain_var``   (P, M): every chain's mean and variance (divisor S − 1)
+    ``chain_acf``      (P, K+1, M), with ``chain_acf=True``: acov_m(k)/acov_m(0) of every chain
+    ``max_rhat``, ``min_ess``   over the parameters that are not constant (NaN when all are)
+    ``n_truncated``    the number of parameters with ``truncated`` set
+    A constant parameter (var+ == 0) has NaN rhat, ess, mcse, tau and acf and truncated 0.
+    ``window`` is the half-open 0-based sample range, ``max_lag`` the K in use."""
+    __slots__ = ("mean", "sd", "rhat", "ess", "mcse", "tau", "truncated", "chain_mean", "chain_var",
+                 "acf", "chain_acf", "max_rhat", "min_ess", "n_truncated", "window", "max_lag")
+
+    def __repr__(self):
+        return "ChainDiag(P=%d, window=%r, max_lag=%d, max_rhat=%.4g, min_ess=%.4g, n_truncated=%d)" % (
+            len(self.mean), self.window, self.max_lag, self.max_rhat, self.min_ess, self.n_truncated)
+
+
+def _diag_store(store):
+    """The store as one column-major (P, T, M) array."""
+    if isinstance(store, (list, tuple)):
+        chains = [np.asarray(c, dtype=np.float64) for c in store]
+        if not chains or any(c.ndim < 1 or c.shape != chains[0].shape for c in chains):
+            raise ValueError("a list store needs M arrays (..., T) of one shape")
+        T = chains[0].shape[-1]
+        x = np.empty((chains[0].size // max(T, 1), T, len(chains)), order="F")
+        for m, c in enumerate(chains):
+            x[:, :, m] = c.reshape((-1, T), order="F")
+        return x
+    x = np.asarray(store, dtype=np.float64)
+    if x.ndim == 2:
+        x = x.reshape(x.shape + (1,))
+    if x.ndim != 3:
+        raise ValueError("store must be (P, T), (P, T, M) or a list of M arrays (..., T)")
+    return _f64(x)
+
+
+def _diag_summary(rhat, ess, truncated):
+    live = ~np.isnan(rhat)
+    return (float(rhat[live].max()) if live.any() else float("nan"),
+            float(ess[live].min()) if live.any() else float("nan"), int(truncated.sum()))
+
+
+def chain_diagnostics(store, window=None, max_lag=None, acf=False, chain_acf=False):
+    """Split R-hat, ESS, MCSE and the autocorrelation of a store on the device (gpt_chain_diag).
+
+    ``store``: (P, T) of one chain, (P, T, M), or a list of M arrays (..., T) whose leading axes
+    are flattened in column-major order: ``[w for w, U, st in GPTregression_chains(...)]``,
+    ``GPNT_SGLD_chains``'s (n, T, nchains) store, ``[res.theta_store]`` of an HMCResult, or stacked
+    predictions (Ntest, T, M).  ``window=(a, b)`` is the half-open 0-based sample range (default
+    all; b − a >= 4), ``max_lag`` the largest lag (default min(S − 1, 256)).  Returns a ChainDiag."""
+    x = _diag_store(store)
+    P, T, M = x.shape
+    first, last = _window(window, T)
+    if not 0 <= first < last <= T or last - first < 4:
+        raise ValueError("the window must satisfy 0 <= first < last <= %d with last - first >= 4" % T)
+    S = last - first
+    max_lag = min(S - 1, 256) if max_lag is None else int(max_lag)
+    K = min(max_lag, S - 1)
+    rows = [np.empty(P) for _ in range(6)]
+    trunc = np.empty(P, dtype=np.int32)
+    cm, cv = np.empty((P, M), order="F"), np.empty((P, M), order="F")
+    ac = np.empty((P, K + 1), order="F") if acf else None
+    ca = np.empty((P, K + 1, M), order="F") if chain_acf else None
+    check(lib().gpt_chain_diag(_ptr(x), P, T, M, first, last, max_lag, *[_ptr(r) for r in rows],
+                               _ptr(trunc, P_I32), _ptr(cm), _ptr(cv), _opt_ptr(ac), _opt_ptr(ca)))
+    d = ChainDiag()
+    d.mean, d.sd, d.rhat, d.ess, d.mcse, d.tau = rows
+    d.truncated, d.chain_mean, d.chain_var, d.acf, d.chain_acf = trunc, cm, cv, ac, ca
+    d.max_rhat, d.min_ess, d.n_truncated = _diag_summary(d.rhat, d.ess, trunc)
+    d.window, d.max_lag = (first, last), K
+    return d
+
+
+def diag_last_timing():
+    """Device-event ms of the kernels alone in the last chain_diagnostics call on this thread
+    (gpt_diag_last_timing)."""
+    out = np.zeros(1)
+    check(lib().gpt_diag_last_timing(_ptr(out)))
+    return float(out[0])
+
+
+def diag_tiling():
+    """dict(time_chunk, lag_block, lag_group) of the autocovariance kernel (gpt_diag_tiling)."""
+    out = np.zeros(3, dtype=np.int32)
+    check(lib().gpt_diag_tiling(_ptr(out, P_I32), out.size))
+    return dict(time_chunk=int(out[0]), lag_block=int(out[1]), lag_group=int(out[2]))
+
+
 # ------------------------------------------------------------------ classification
 def GPNT_SGLDclass(phi, y, sigma_theta, m, eps_theta, decay_rate, burnin, maxepoch, param_seed=0):
     """Full-theta softmax SGLD (GPT_SGLD.jl:851-901), labels y in 1..C.  Returns theta_store

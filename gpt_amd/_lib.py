@@ -140,6 +140,10 @@ SIGNATURES = {
                                         C.c_double, P_D, P_D, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_int64, C.c_double, C.c_double] + [P_D] * 8),
     "gpt_predictive_last_timing": (C.c_int, [P_D]),
+    "gpt_chain_diag": (C.c_int, [P_D] + [C.c_int64] * 6 + [P_D] * 6 + [P_I32] + [P_D] * 4),
+    "gpt_chain_diag_dev": (C.c_int, [C.c_void_p] + [C.c_int64] * 7 + [C.c_void_p] * 12),
+    "gpt_diag_last_timing": (C.c_int, [P_D]),
+    "gpt_diag_tiling": (C.c_int, [P_I32, C.c_int32]),
     "gpt_gpnt_sgld_class": (C.c_int, [P_D, P_D, C.c_int64, C.c_int64, C.c_double, C.c_int64,
                                       C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_uint64,
                                       P_D]),

@@ -417,6 +417,21 @@ hipError_t launch_class_eval(const double* scores, const int32_t* y, long long N
 hipError_t launch_class_mean(const double* scores, long long Ntest, int C, int first, int last,
                              double* mean_out, hipStream_t st);
 
+// Chain diagnostics (diag.hip) of the window x (P, S, M), sample s of chain m at x + P·s +
+// cstride·m, at lags 0 … K <= S − 1: the per-parameter rows (P each), chain_mean / chain_var (P, M),
+// acf (P, K + 1) and chain_acf (P, K + 1, M), the last four optional.  ws holds
+// diag_ws_doubles(P, M, K) doubles.  The tiling: samples per time chunk, lags per wave and per
+// workgroup, and the workgroups along the lags.
+int diag_time_chunk();
+int diag_lag_block();
+int diag_lag_group();
+int diag_lag_groups(int K);
+size_t diag_ws_doubles(long long P, int M, int K);
+hipError_t launch_chain_diag(const double* x, long long P, long long cstride, int S, int M, int K,
+                             double* ws, double* mean, double* sd, double* rhat, double* ess,
+                             double* mcse, double* tau, int32_t* truncated, double* chain_mean,
+                             double* chain_var, double* acf, double* chain_acf, hipStream_t st);
+
 // Posterior predictive of stored predictions F (Ntest, S) against y at noise variance noise_var
 // (predictive.hip): fmu, fs2, lp, lpmix (Ntest, each optional); part (2 per tile) and part_cov
 // (1 per tile) hold the predictive_tiles(Ntest) partial sums; sums[0..1] = Σ lp, Σ lpmix and

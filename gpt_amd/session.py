@@ -286,6 +286,53 @@ def predictive_device(fhat, ytest, signal_var, window=None, stream=None, rows=Tr
     return tuple(out) + (float(sums[0]), float(sums[1]), int(covered[0]))
 
 
+def diagnostics_device(x, window=None, max_lag=None, stream=None, acf=False, chain_acf=False):
+    """Chain diagnostics (gpt_chain_diag_dev) of a device store ``x``, a float64 torch (M, T, P)
+    tensor [Julia (P, T, M)]: chain m's (T, P) block contiguous, the chains at any constant stride
+    of at least T·P elements (a view of M separately filled predictions needs no copy).  ``window``
+    and ``max_lag`` as in GPT_SGLD.chain_diagnostics.  Returns a ChainDiag whose arrays are device
+    tensors (chain_mean, chain_var (M, P); acf (K+1, P), chain_acf (M, K+1, P) where asked); only
+    its three scalars max_rhat, min_ess and n_truncated visit the host."""
+    import torch
+    from .GPT_SGLD import ChainDiag
+    if x.dtype != torch.float64 or not x.is_cuda or x.dim() != 3:
+        raise ValueError("x must be a float64 device tensor of torch shape (M, T, P)")
+    M, T, P = x.shape
+    cs = x.stride(0) if M > 1 else T * P
+    if x.stride(2) != 1 or x.stride(1) != P or cs < T * P:
+        raise ValueError("every chain of x must be a contiguous (T, P) block, the chains at a "
+                         "constant stride >= T*P")
+    first, last = (0, T) if window is None else (int(window[0]), int(window[1]))
+    if not 0 <= first < last <= T or last - first < 4:
+        raise ValueError("the window must satisfy 0 <= first < last <= %d with last - first >= 4" % T)
+    S = last - first
+    max_lag = min(S - 1, 256) if max_lag is None else int(max_lag)
+    K = min(max_lag, S - 1)
+
+    def new(*shape, dtype=torch.float64):
+        return torch.empty(shape, dtype=dtype, device=x.device)
+    d = ChainDiag()
+    d.mean, d.sd, d.rhat, d.ess, d.mcse, d.tau = (new(P) for _ in range(6))
+    d.truncated = new(P, dtype=torch.int32)
+    d.chain_mean, d.chain_var = new(M, P), new(M, P)
+    d.acf = new(K + 1, P) if acf else None
+    d.chain_acf = new(M, K + 1, P) if chain_acf else None
+    outs = [d.mean, d.sd, d.rhat, d.ess, d.mcse, d.tau, d.truncated, d.chain_mean, d.chain_var,
+            d.acf, d.chain_acf]
+    check(lib().gpt_chain_diag_dev(C.c_void_p(x.data_ptr()), P, T, M, cs, first, last, max_lag,
+                                   *[None if t is None else C.c_void_p(t.data_ptr()) for t in outs],
+                                   C.c_void_p(stream) if stream else None))
+    live = ~torch.isnan(d.rhat)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=x.device)
+    three = torch.stack([torch.where(live, d.rhat, -torch.inf).max(),
+                         torch.where(live, d.ess, torch.inf).min(),
+                         d.truncated.sum().double()])
+    three = torch.where(live.any(), three, torch.stack([nan, nan, three[2]])).cpu()
+    d.max_rhat, d.min_ess, d.n_truncated = float(three[0]), float(three[1]), int(three[2])
+    d.window, d.max_lag = (first, last), K
+    return d
+
+
 VPHASE_KERNELS = {0: "pred_vphase_pairs_kernel", 1: "pred_vphase_rows_pf_kernel",
                   2: "pred_vphase_rows_kernel", 4: "pred_kernel (direct, no separate V-phase)"}
 

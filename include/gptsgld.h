@@ -475,6 +475,55 @@ int gpt_gpnt_predictive_x(const double* theta, const double* Xtest, const double
  * on this thread (measurement, scripts/time_predictive.py). */
 int gpt_predictive_last_timing(double* ms);
 
+/* ---- chain diagnostics of a store: split R-hat, ESS, autocorrelation ------------------- */
+/* Diagnostics of store x (P, T, M) column-major: parameter (or test row) p, kept sample s, chain m
+ * at store + p + P*(s + T*m).  The window is first <= s < last (0-based, half open), S = last -
+ * first >= 4, the lags k = 0..K with K = min(max_lag, S - 1).  Per parameter and chain, in sample
+ * order:
+ *   chain_mean_m = (sum_s x)/S;  c_s = x_s - chain_mean_m (two passes, the deviations taken about
+ *   the chain's first sample, so equal samples give c = 0 exactly);
+ *   acov_m(k) = (sum_{s=0}^{S-1-k} c_s c_{s+k})/S (divisor S at every lag);
+ *   chain_var_m = acov_m(0)*S/(S - 1);  chain_acf_m(k) = acov_m(k)/acov_m(0).
+ * Per parameter, the chains in the order m = 0..M-1:
+ *   W = mean_m chain_var_m;  B/S = the variance of the chain means (divisor M - 1; 0 at M = 1);
+ *   var+ = W*(S - 1)/S + B/S;  mean = mean_m chain_mean_m;  sd = sqrt(var+);
+ *   acf[k] = 1 - (W - mean_m acov_m(k))/var+            (the combined rho_k of BDA3 11.5 / Stan)
+ *   Geyer's initial monotone sequence: P_j = acf[2j] + acf[2j+1] for 2j + 1 <= K, stopped at the
+ *   first P_j <= 0, else P_j = min(P_j, P_{j-1});  tau = max(-1 + 2 sum_j P_j, 1/log10(M*S));
+ *   ess = M*S/tau;  mcse = sd/sqrt(ess);  truncated = 1 when the lags ran out before a stop (ess
+ *   is then an upper bound: max_lag too small, or chains that disagree);
+ *   split R-hat: H = floor(S/2), the first and the last H samples of every chain (the middle one
+ *   dropped at odd S) as 2M sequences, W_h the mean of their variances (divisor H - 1), B_h/H the
+ *   variance of their means (divisor 2M - 1), rhat = sqrt(((H - 1)/H*W_h + B_h/H)/W_h).
+ * A parameter with var+ == 0 is constant: its rhat, ess, mcse, tau and acf are NaN, truncated 0.
+ * No atomics; every sum runs in an order fixed by S and K; a parameter's results depend on its
+ * own values alone, a chain's chain_mean, chain_var and chain_acf on that chain's alone, and
+ * acf[k] has the same bits for every max_lag >= k.
+ * Outputs: mean, sd, rhat, ess, mcse, tau, truncated (P each); optional (NULL to skip) chain_mean
+ * and chain_var (P, M), acf (P, K+1) and chain_acf (P, K+1, M).  GPT_ERR_BAD_DIMS with a message
+ * before any device work for a null required pointer, P < 1, T outside 4..2^22, M outside 1..1024,
+ * max_lag outside 1..4096, a window outside 0 <= first < last <= T or shorter than 4, and, for the
+ * host entry, a store of more than 2^31 doubles (16 GiB, one upload).
+ * The _dev form takes device pointers throughout and chain m at store + chain_stride*m
+ * (chain_stride >= P*T elements: separately allocated (P, T) predictions at a constant stride need
+ * no copy); it synchronises hip_stream. */
+int gpt_chain_diag(const double* store, int64_t P, int64_t T, int64_t M, int64_t first,
+                   int64_t last, int64_t max_lag, double* mean, double* sd, double* rhat,
+                   double* ess, double* mcse, double* tau, int32_t* truncated, double* chain_mean,
+                   double* chain_var, double* acf, double* chain_acf);
+int gpt_chain_diag_dev(const double* store_dev, int64_t P, int64_t T, int64_t M,
+                       int64_t chain_stride, int64_t first, int64_t last, int64_t max_lag,
+                       double* mean_dev, double* sd_dev, double* rhat_dev, double* ess_dev,
+                       double* mcse_dev, double* tau_dev, int32_t* truncated_dev,
+                       double* chain_mean_dev, double* chain_var_dev, double* acf_dev,
+                       double* chain_acf_dev, void* hip_stream);
+/* Device-event time in ms of the evaluator's kernels alone in the last gpt_chain_diag* call on
+ * this thread (measurement, scripts/time_diag.py). */
+int gpt_diag_last_timing(double* ms);
+/* out[0..2] = the samples per time chunk, the lags per wave and the lags per workgroup of the
+ * autocovariance kernel (the edges the tests place their shapes at); entries past 2 are 0. */
+int gpt_diag_tiling(int32_t* out, int32_t len);
+
 /* ---- classification: the full-theta softmax sampler and the evaluation of scores ------ */
 /* GPNT_SGLDclass(phi,y,sigma_theta,m,eps_theta,decay_rate,burnin,maxepoch,param_seed)
  * GPT_SGLD.jl:851-901.  phi (n, N); y (N) integer labels in 1..C, C = max(y) - min(y) + 1 <= 32

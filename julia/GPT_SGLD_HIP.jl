@@ -16,6 +16,7 @@ export datawhitening, feature, feature_inputs, featureNotensor, samplenz, GPTreg
        GPNT_SGLDclass, GPNT_SGLDclass_chains, class_eval, GPNT_pred_class, pred_class,
        neglogjointlkhd, gradneglogjointlkhd, joint_langevin, joint_scores, joint_hmc, joint_mala,
        predictive, pred_predictive, pred_predictive_x, GPNT_predictive, GPNT_predictive_x,
+       chain_diagnostics,
        GPrand, GPpost_rand, GPNT_draw_theta, fhatdraw, createmesh
 
 const LIB = get(ENV, "GPTSGLD_LIB", joinpath(@__DIR__, "..", "gpt_amd", "libgptsgld.so"))
@@ -525,6 +526,42 @@ function predictive(scores::Array{Float64,2}, ytest::Array{Float64}, signal_var:
                 o.covered, o.rmse, o.srm))
     o.rmse .*= scale; o.srm .*= scale
     return predictive_result(o, Nt, signal_var, scale)
+end
+
+# ---- chain diagnostics of a store: split R-hat, ESS, autocorrelation (gpt_chain_diag) ----
+struct ChainDiag
+    mean::Vector{Float64}; sd::Vector{Float64}; rhat::Vector{Float64}; ess::Vector{Float64}
+    mcse::Vector{Float64}; tau::Vector{Float64}; truncated::Vector{Int32}
+    chain_mean::Array{Float64,2}; chain_var::Array{Float64,2}
+    acf::Union{Nothing,Array{Float64,2}}; chain_acf::Union{Nothing,Array{Float64,3}}
+    max_rhat::Float64; min_ess::Float64; n_truncated::Int
+end
+
+# store (P, T, M): parameter or test row, kept sample, chain ((P, T): one chain).  window = a:b
+# selects the samples (1-based, default all; at least 4), max_lag defaults to min(S - 1, 256).
+# truncated[p] == 1: the lags ran out before Geyer's sequence turned negative; ess[p] is then an
+# upper bound.  A constant parameter has NaN rhat, ess, mcse, tau and acf.
+function chain_diagnostics(store::Array{Float64}; window=nothing, max_lag=nothing, acf::Bool=false,
+                           chain_acf::Bool=false)
+    ndims(store) in (2, 3) || error("store must be (P, T) or (P, T, M)")
+    P, T = size(store, 1), size(store, 2); M = size(store, 3); a, b = class_window(window, T)
+    length(store) == P * T * M || error("store must hold P*T*M values")
+    0 <= a < b <= T || error("the window must lie in 1:$T")
+    b - a >= 4 || error("the window needs at least 4 samples")
+    S = b - a; lag = max_lag === nothing ? min(S - 1, 256) : Int(max_lag); K = min(lag, S - 1)
+    1 <= lag <= 4096 || error("max_lag must be in 1:4096")
+    rows = [zeros(P) for _ = 1:6]; tr = zeros(Int32, P); cm = zeros(P, M); cv = zeros(P, M)
+    ac = acf ? zeros(P, K + 1) : nothing; ca = chain_acf ? zeros(P, K + 1, M) : nothing
+    check(ccall((:gpt_chain_diag, LIB), Cint,
+                (Ptr{Float64}, Int64, Int64, Int64, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                store, P, T, M, a, b, lag, rows[1], rows[2], rows[3], rows[4], rows[5], rows[6], tr,
+                cm, cv, ac === nothing ? C_NULL : ac, ca === nothing ? C_NULL : ca))
+    live = .!isnan.(rows[3])
+    return ChainDiag(rows[1], rows[2], rows[3], rows[4], rows[5], rows[6], tr, cm, cv, ac, ca,
+                     any(live) ? maximum(rows[3][live]) : NaN, any(live) ? minimum(rows[4][live]) : NaN,
+                     Int(sum(tr)))
 end
 
 # GPTregression's stored samples w_store (Q, S), U_store (n, r, D, S) on phitest (n, D, Ntest)
