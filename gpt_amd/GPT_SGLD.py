@@ -63,6 +63,11 @@ def _f64(a):
     return np.asfortranarray(np.asarray(a, dtype=np.float64))
 
 
+def _hvec(h):
+    """A hyper-parameter vector as contiguous doubles."""
+    return _f64(np.asarray(h, dtype=np.float64).ravel())
+
+
 def _ptr(a, t=P_D):
     return a.ctypes.data_as(t)
 
@@ -1137,7 +1142,99 @@ def pred_class(w_store, U_store, I, phitest, ytest, cols=None, window=None, scor
 
 
 # ------------------------------------------------------------------ full-theta model: hyper-parameters
-class NoTensorMarginal:
+GPPrediction = collections.namedtuple("GPPrediction", "ymu ys2 fmu fs2 lp")
+GPPosteriorDraw = collections.namedtuple("GPPosteriorDraw", "fmu samples cov z")
+RFFKernelError = collections.namedtuple("RFFKernelError", "frob norm_K max_abs")
+
+
+def _bad_dims(msg):
+    return GPTError(GPT_ERR_BAD_DIMS, msg)
+
+
+def _gpnt_test_args(Xtest, ytest, D):
+    Xtest = _f64(Xtest)
+    if Xtest.ndim != 2 or Xtest.shape[1] != D or Xtest.shape[0] < 1:
+        raise _bad_dims("Xtest must be (Ntest, D) with Ntest >= 1")
+    yt = None
+    if ytest is not None:
+        yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+        if yt.size != Xtest.shape[0]:
+            raise _bad_dims("ytest must have length Ntest")
+    return Xtest, yt
+
+
+def _gp_test_args(Xtest, ytest, D):
+    """ExactGP's and SoftmaxJoint's form of the check: a badly shaped argument is a ValueError."""
+    Xtest = _f64(Xtest)
+    if Xtest.ndim != 2 or Xtest.shape[1] != D:
+        raise ValueError("Xtest must be (Ntest, D)")
+    yt = None
+    if ytest is not None:
+        yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+        if yt.size != Xtest.shape[0]:
+            raise ValueError("ytest must have length Ntest")
+    return Xtest, yt
+
+
+def _predict_call(fn, head, h, Xtest, yt, chunk=()):
+    """fn(*head, h, len(h), Xtest, Ntest, ytest, *chunk, fmu, fs2, lp) as a GPPrediction."""
+    Nt = Xtest.shape[0]
+    fmu, fs2 = np.empty(Nt), np.empty(Nt)
+    lp = np.empty(Nt) if yt is not None else None
+    check(fn(*head, _ptr(h), h.size, _ptr(Xtest), Nt, _ptr(yt) if yt is not None else None, *chunk,
+             _ptr(fmu), _ptr(fs2), _ptr(lp) if lp is not None else None))
+    return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+
+
+class _Handle:
+    """Owner of one library handle, ``_h``; ``_destroy`` names the entry that frees it."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # interpreter shutdown: the library may be gone already
+            pass
+
+
+class _Marginal(_Handle):
+    """What NoTensorMarginal and ExactGP share: the evaluation at ``h`` through ``_eval_entry``
+    (its third output has ``_nextra`` entries) and the prediction through ``_predict_entry``,
+    whose test arguments ``_test_args`` checks."""
+    _eval_entry = _predict_entry = _test_args = None
+
+    def _eval(self, h, want_grad, want_extra=False):
+        h = _hvec(h)
+        val = C.c_double()
+        grad = np.empty(h.size) if want_grad else None
+        extra = np.empty(self._nextra) if want_extra else None
+        check(getattr(lib(), self._eval_entry)(self._h, _ptr(h), h.size, 1 if want_grad else 0,
+                                               C.byref(val), _ptr(grad) if want_grad else None,
+                                               _ptr(extra) if want_extra else None))
+        return val.value, grad, extra
+
+    def nlogmarginal(self, h):
+        return self._eval(h, False)[0]
+
+    def gradnlogmarginal(self, h):
+        return self._eval(h, True)[1]
+
+    def value_and_grad(self, h):
+        return self._eval(h, True)[:2]
+
+    def _predict(self, h, Xtest, ytest, chunk):
+        h = _hvec(h)
+        Xtest, yt = self._test_args(Xtest, ytest, self.D)
+        return _predict_call(getattr(lib(), self._predict_entry), [self._h], h, Xtest, yt,
+                             (0 if chunk is None else int(chunk),))
+
+
+class NoTensorMarginal(_Marginal):
     """Device-resident Gaussian marginal likelihood of the no-tensor RFF GP (GPT_SGLD.jl:921-962
     with featureNotensor / gradfeatureNotensor as the feature closures).
 
@@ -1145,6 +1242,8 @@ class NoTensorMarginal:
     ``h = [length_scale (D entries, or one: the scalar form); sigma_RBF; signal_var]``.
     n <= 1024, D <= 16.  A failed Cholesky raises ``GPTError`` (GPT_ERR_NOT_SPD), as the
     reference's ``cholfact`` throws."""
+    _destroy, _eval_entry, _predict_entry = "gpt_nlml_destroy", "gpt_nlml_eval", "gpt_nlml_predict"
+    _test_args = staticmethod(_gpnt_test_args)
 
     def __init__(self, X, y, Z, b):
         X = _f64(X)
@@ -1158,38 +1257,9 @@ class NoTensorMarginal:
         if Z.shape != (n, D) or b.size != n or y.size != N:
             raise ValueError("Z must be (n, D), b of length n and y of length N")
         self.n, self.N, self.D = n, N, D
+        self._nextra = n
         self._h = C.c_void_p()
         check(lib().gpt_nlml_create(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), n, C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gpt_nlml_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:          # interpreter shutdown: the library may be gone already
-            pass
-
-    def _eval(self, h, want_grad, want_theta=False):
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
-        val = C.c_double()
-        grad = np.empty(h.size) if want_grad else None
-        theta = np.empty(self.n) if want_theta else None
-        check(lib().gpt_nlml_eval(self._h, _ptr(h), h.size, 1 if want_grad else 0, C.byref(val),
-                                  _ptr(grad) if want_grad else None,
-                                  _ptr(theta) if want_theta else None))
-        return val.value, grad, theta
-
-    def nlogmarginal(self, h):
-        return self._eval(h, False)[0]
-
-    def gradnlogmarginal(self, h):
-        return self._eval(h, True)[1]
-
-    def value_and_grad(self, h):
-        return self._eval(h, True)[:2]
 
     def theta_mean(self, h):
         """l = A^-1 phi y at h: the posterior mean of the full-theta weights."""
@@ -1202,7 +1272,6 @@ class NoTensorMarginal:
         check(lib().gpt_nlml_features(self._h, _ptr(phi), _ptr(S) if sin else None))
         return (phi, S) if sin else phi
 
-
     def predict(self, h, Xtest, ytest=None, chunk=None):
         """The closed-form predictive of the model at ``h``: GPkit's named tuple (ymu, ys2, fmu,
         fs2, lp) for ``Xtest`` (Ntest, D), as ``ExactGP.predict`` returns it; lp is None without
@@ -1210,23 +1279,14 @@ class NoTensorMarginal:
         colsum((L^-1 phi*)^2), a sum of squares.  The factor of the last evaluation is reused when
         ``h`` equals its hyper-parameters bit for bit.  ``chunk`` test rows go through the device
         at a time (None: the library's choice); the results do not depend on it."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
-        Xtest, yt = _gpnt_test_args(Xtest, ytest, self.D)
-        Nt = Xtest.shape[0]
-        fmu, fs2 = np.empty(Nt), np.empty(Nt)
-        lp = np.empty(Nt) if yt is not None else None
-        check(lib().gpt_nlml_predict(self._h, _ptr(h), h.size, _ptr(Xtest), Nt,
-                                     _ptr(yt) if yt is not None else None,
-                                     0 if chunk is None else int(chunk), _ptr(fmu), _ptr(fs2),
-                                     _ptr(lp) if lp is not None else None))
-        return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+        return self._predict(h, Xtest, ytest, chunk)
 
     def draw_theta(self, h, S, seed=0, z=None, return_z=False):
         """``S`` exact draws from the posterior theta | y ~ N(l, signal_var A^-1) at ``h``:
         (n, S) = l + sqrt(signal_var) L^-T z, the layout of a GPNT_SGLD store, so it goes straight
         to GPNT_pred, GPNT_predictive and their ``_x`` forms.  ``z`` (n, S) replaces the Philox
         normals (stream 25, kind 2); column s depends on column s of the normals only."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        h = _hvec(h)
         S = int(S)
         z = _draw_z(z, self.n, S)
         theta = np.empty((self.n, max(S, 0)), order="F")
@@ -1249,27 +1309,6 @@ def _draw_z(z, M, S):
     return z
 
 
-GPPrediction = collections.namedtuple("GPPrediction", "ymu ys2 fmu fs2 lp")
-GPPosteriorDraw = collections.namedtuple("GPPosteriorDraw", "fmu samples cov z")
-RFFKernelError = collections.namedtuple("RFFKernelError", "frob norm_K max_abs")
-
-
-def _bad_dims(msg):
-    return GPTError(GPT_ERR_BAD_DIMS, msg)
-
-
-def _gpnt_test_args(Xtest, ytest, D):
-    Xtest = _f64(Xtest)
-    if Xtest.ndim != 2 or Xtest.shape[1] != D or Xtest.shape[0] < 1:
-        raise _bad_dims("Xtest must be (Ntest, D) with Ntest >= 1")
-    yt = None
-    if ytest is not None:
-        yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
-        if yt.size != Xtest.shape[0]:
-            raise _bad_dims("ytest must have length Ntest")
-    return Xtest, yt
-
-
 def _gpnt_feature_args(X, Z, b):
     X, Z = _f64(X), _f64(Z)
     b = _f64(np.asarray(b, dtype=np.float64).ravel())
@@ -1285,15 +1324,10 @@ def gpnt_predict_oneshot(X, y, Z, b, hyperparams, Xtest, ytest=None):
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
     if y.size != N:
         raise _bad_dims("y must have length N")
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
     Xtest, yt = _gpnt_test_args(Xtest, ytest, D)
-    Nt = Xtest.shape[0]
-    fmu, fs2 = np.empty(Nt), np.empty(Nt)
-    lp = np.empty(Nt) if yt is not None else None
-    check(lib().gpt_gpnt_predict(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), Z.shape[0], _ptr(h),
-                                 h.size, _ptr(Xtest), Nt, _ptr(yt) if yt is not None else None,
-                                 _ptr(fmu), _ptr(fs2), _ptr(lp) if lp is not None else None))
-    return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+    return _predict_call(lib().gpt_gpnt_predict,
+                         [_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), Z.shape[0]],
+                         _hvec(hyperparams), Xtest, yt)
 
 
 def rff_kernel_error(X, Z, b, hyperparams):
@@ -1306,7 +1340,7 @@ def rff_kernel_error(X, Z, b, hyperparams):
     8 n N <= 2 GiB."""
     X, Z, b = _gpnt_feature_args(X, Z, b)
     N, D = X.shape
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    h = _hvec(hyperparams)
     out = np.empty(3)
     check(lib().gpt_rff_kernel_error(_ptr(X), N, D, _ptr(Z), _ptr(b), Z.shape[0], _ptr(h), h.size,
                                      _ptr(out)))
@@ -1346,7 +1380,7 @@ def gpnt_nlogmarginal_oneshot(X, y, Z, b, hyperparams, want_grad=True):
     Z = _f64(Z)
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
     b = _f64(np.asarray(b, dtype=np.float64).ravel())
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    h = _hvec(hyperparams)
     val = C.c_double()
     grad = np.empty(h.size)
     check(lib().gpt_gpnt_nlogmarginal(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), Z.shape[0], _ptr(h),
@@ -1355,7 +1389,7 @@ def gpnt_nlogmarginal_oneshot(X, y, Z, b, hyperparams, want_grad=True):
 
 
 # ------------------------------------------------------------------ exact GP regression
-class ExactGP:
+class ExactGP(_Marginal):
     """Device-resident exact GP regression: squared-exponential kernel (iso or ARD), Gaussian
     noise, zero mean — GP_nlogmarginal (GPT_SGLD.jl:905-915) and GPkit's InfExact / prediction
     with CovSEiso or CovSEard and LikGauss, the reference's quality ceiling.
@@ -1370,6 +1404,8 @@ class ExactGP:
     ``GPNT_hyperparameters(gp.nlogmarginal, gp.gradnlogmarginal, init, lbounds)``.  GPkit's
     ``dnlZ`` (with respect to log l, log sigma_RBF, log sqrt(signal_var)) is the gradient times
     ``[l..., sigma_RBF, 2 signal_var]``."""
+    _destroy, _eval_entry, _predict_entry = "gpt_egp_destroy", "gpt_egp_eval", "gpt_egp_predict"
+    _test_args = staticmethod(_gp_test_args)
 
     def __init__(self, X, y):
         X = _f64(X)
@@ -1380,38 +1416,9 @@ class ExactGP:
         if y.size != N:
             raise ValueError("y must have length N")
         self.N, self.D = N, D
+        self._nextra = N
         self._h = C.c_void_p()
         check(lib().gpt_egp_create(_ptr(X), N, D, _ptr(y), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gpt_egp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:          # interpreter shutdown: the library may be gone already
-            pass
-
-    def _eval(self, h, want_grad, want_alpha=False):
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
-        val = C.c_double()
-        grad = np.empty(h.size) if want_grad else None
-        alpha = np.empty(self.N) if want_alpha else None
-        check(lib().gpt_egp_eval(self._h, _ptr(h), h.size, 1 if want_grad else 0, C.byref(val),
-                                 _ptr(grad) if want_grad else None,
-                                 _ptr(alpha) if want_alpha else None))
-        return val.value, grad, alpha
-
-    def nlogmarginal(self, h):
-        return self._eval(h, False)[0]
-
-    def gradnlogmarginal(self, h):
-        return self._eval(h, True)[1]
-
-    def value_and_grad(self, h):
-        return self._eval(h, True)[:2]
 
     def alpha(self, h):
         """(K + signal_var I)^-1 y at h."""
@@ -1422,29 +1429,13 @@ class ExactGP:
         (Ntest, D); lp is None without ``ytest``.  The factor of the last evaluation is reused
         when ``h`` equals its hyper-parameters bit for bit.  ``chunk`` test rows go through the
         device at a time (None: the library's choice); the results do not depend on it."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
-        Xtest = _f64(Xtest)
-        if Xtest.ndim != 2 or Xtest.shape[1] != self.D:
-            raise ValueError("Xtest must be (Ntest, D)")
-        Nt = Xtest.shape[0]
-        yt = None
-        if ytest is not None:
-            yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
-            if yt.size != Nt:
-                raise ValueError("ytest must have length Ntest")
-        fmu, fs2 = np.empty(Nt), np.empty(Nt)
-        lp = np.empty(Nt) if yt is not None else None
-        check(lib().gpt_egp_predict(self._h, _ptr(h), h.size, _ptr(Xtest), Nt,
-                                    _ptr(yt) if yt is not None else None,
-                                    0 if chunk is None else int(chunk), _ptr(fmu), _ptr(fs2),
-                                    _ptr(lp) if lp is not None else None))
-        return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+        return self._predict(h, Xtest, ytest, chunk)
 
     def draw_prior(self, h, S=1, seed=0, jitter=1e-6, z=None, return_z=False):
         """GPrand (GaussianProcess.jl:66-80) at the object's X: (N, S) = R'z with R = chol(K +
         jitter I); signal_var in ``h`` is not used.  ``z`` (N, S) replaces the Philox normals
         (stream 25, kind 0).  The next ``predict`` refits."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        h = _hvec(h)
         S = int(S)
         z = _draw_z(z, self.N, S)
         F = np.empty((self.N, max(S, 0)), order="F")
@@ -1456,10 +1447,8 @@ class ExactGP:
         return (F, zout) if return_z else F
 
     def _posterior(self, h, Xtest, S, seed, jitter, observed, z, want_f, want_cov, want_z):
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
-        Xtest = _f64(Xtest)
-        if Xtest.ndim != 2 or Xtest.shape[1] != self.D:
-            raise ValueError("Xtest must be (Ntest, D)")
+        h = _hvec(h)
+        Xtest, _ = _gp_test_args(Xtest, None, self.D)
         Nt, S = Xtest.shape[0], int(S)
         z = _draw_z(z, Nt, S) if want_f else None
         fmu = np.empty(Nt)
@@ -1498,7 +1487,7 @@ def gp_nlogmarginal_oneshot(X, y, hyperparams, want_grad=True):
     X = _f64(X)
     N, D = X.shape
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    h = _hvec(hyperparams)
     val = C.c_double()
     grad = np.empty(h.size)
     check(lib().gpt_gp_nlogmarginal(_ptr(X), N, D, _ptr(y), _ptr(h), h.size,
@@ -1510,16 +1499,10 @@ def gp_predict_oneshot(X, y, hyperparams, Xtest, ytest=None):
     """The one-shot host-pointer prediction the Julia shim binds (gpt_gp_predict)."""
     X, Xtest = _f64(X), _f64(Xtest)
     N, D = X.shape
-    Nt = Xtest.shape[0]
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
     yt = _f64(np.asarray(ytest, dtype=np.float64).ravel()) if ytest is not None else None
-    fmu, fs2 = np.empty(Nt), np.empty(Nt)
-    lp = np.empty(Nt) if yt is not None else None
-    check(lib().gpt_gp_predict(_ptr(X), N, D, _ptr(y), _ptr(h), h.size, _ptr(Xtest), Nt,
-                               _ptr(yt) if yt is not None else None, _ptr(fmu), _ptr(fs2),
-                               _ptr(lp) if lp is not None else None))
-    return GPPrediction(fmu, fs2 + h[-1], fmu, fs2, lp)
+    return _predict_call(lib().gpt_gp_predict, [_ptr(X), N, D, _ptr(y)], _hvec(hyperparams), Xtest,
+                         yt)
 
 
 def gp_posterior_draw_oneshot(X, y, hyperparams, Xtest, S=1, seed=0, jitter=1e-6, observed=False,
@@ -1534,7 +1517,7 @@ def gp_posterior_draw_oneshot(X, y, hyperparams, Xtest, S=1, seed=0, jitter=1e-6
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
     if y.size != N:
         raise _bad_dims("y must have length N")
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    h = _hvec(hyperparams)
     z = _draw_z(z, Nt, S)
     fmu = np.empty(Nt)
     F = np.empty((Nt, max(S, 0)), order="F")
@@ -1555,7 +1538,7 @@ def gpnt_draw_theta_oneshot(X, y, Z, b, hyperparams, S, seed=0, z=None):
     y = _f64(np.asarray(y, dtype=np.float64).ravel())
     if y.size != N:
         raise _bad_dims("y must have length N")
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    h = _hvec(hyperparams)
     z = _draw_z(z, n, S)
     theta = np.empty((n, max(S, 0)), order="F")
     check(lib().gpt_gpnt_draw_theta(_ptr(X), N, D, _ptr(y), _ptr(Z), _ptr(b), n, _ptr(h), h.size, S,
@@ -1672,7 +1655,7 @@ class HMCResult:
             self.theta_store.shape[2], self.accept.size, self.accept_rate, self.ndivergent)
 
 
-class SoftmaxJoint:
+class SoftmaxJoint(_Handle):
     """Device-resident joint likelihood -log p(y, theta; h) of the full-theta softmax classifier
     and its gradient (neglogjointlkhd / gradneglogjointlkhd, ImageExperiment.jl:135-204, with
     featureNotensor / gradfeatureNotensor at ``Z``, ``b`` in place of the seed).
@@ -1683,6 +1666,7 @@ class SoftmaxJoint:
     theta (n, C) is resident on the device: a ``theta_vec`` argument (length n*C, column-major,
     or an (n, C) array) is uploaded and becomes the resident theta, ``None`` means the resident
     one.  n <= 1024, D <= 16, C <= 32.  Nothing of size n*N*D, or n*N, is stored."""
+    _destroy = "gpt_cjoint_destroy"
 
     def __init__(self, X, y, Z, b, C=None):
         X = _f64(X)
@@ -1702,17 +1686,6 @@ class SoftmaxJoint:
         check(lib().gpt_cjoint_create(_ptr(X), N, D, _ptr(y), self.C, _ptr(Z), _ptr(b), n,
                                       _lib.C.byref(self._h)))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gpt_cjoint_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:          # interpreter shutdown: the library may be gone already
-            pass
-
     def _theta_arg(self, theta):
         if theta is None:
             return None
@@ -1722,7 +1695,7 @@ class SoftmaxJoint:
         return _f64(t.reshape((self.n, self.C), order="F"))
 
     def _eval(self, theta, h, want_grad, want_theta_grad=True):
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        h = _hvec(h)
         th = self._theta_arg(theta)
         val = _lib.C.c_double()
         nC = self.n * self.C
@@ -1769,7 +1742,7 @@ class SoftmaxJoint:
         0-based step t and class c is normals(n, seed, t, THETA_NOISE, c).  ``t0`` sets the step
         counter first (None: it continues).  A non-finite theta raises GPTError
         (GPT_ERR_NAN_THETA) and the remaining steps are not taken."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        h = _hvec(h)
         check(lib().gpt_cjoint_langevin(self._h, _ptr(h), h.size, float(eps), int(nsteps),
                                         int(seed), -1 if t0 is None else int(t0)))
 
@@ -1782,7 +1755,7 @@ class SoftmaxJoint:
         counter is the one ``langevin`` uses (``t0`` sets it first, None continues).  Returns an
         HMCResult.  A transition whose end Hamiltonian is not finite is rejected and counted in
         ``ndivergent``; a non-finite starting theta raises GPTError (GPT_ERR_NAN_THETA)."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        h = _hvec(h)
         burnin, nsamples, thin = int(burnin), int(nsamples), int(thin)
         ntrans = max(burnin, 0) + max(nsamples, 0)
         ncols = max(nsamples, 0) // thin if thin >= 1 else 0
@@ -1807,7 +1780,7 @@ class SoftmaxJoint:
     def leapfrog(self, h, eps, L, p):
         """The integrator alone: ``L`` leapfrog steps of size sqrt(``eps``) from the resident theta
         (left unchanged) on the momentum ``p`` (n, C).  Returns ``(q, p_new, H0, H1)``."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        h = _hvec(h)
         pn = np.array(self._theta_arg(p), dtype=np.float64, order="F", copy=True)
         q = np.empty((self.n, self.C), order="F")
         H = np.empty(2)
@@ -1816,14 +1789,11 @@ class SoftmaxJoint:
         return q, pn, float(H[0]), float(H[1])
 
     def _xtest(self, Xtest):
-        Xtest = _f64(Xtest)
-        if Xtest.ndim != 2 or Xtest.shape[1] != self.D:
-            raise ValueError("Xtest must be (Ntest, D)")
-        return Xtest
+        return _gp_test_args(Xtest, None, self.D)[0]
 
     def scores(self, h, Xtest):
         """featureNotensor(Xtest)' theta at ``h``: (Ntest, C)."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        h = _hvec(h)
         Xtest = self._xtest(Xtest)
         out = np.empty((Xtest.shape[0], self.C), order="F")
         check(lib().gpt_cjoint_scores(self._h, _ptr(h), h.size, _ptr(Xtest), Xtest.shape[0],
@@ -1833,7 +1803,7 @@ class SoftmaxJoint:
     def evaluate(self, h, Xtest, ytest):
         """The prop_missed / mean_nlp line of the reference's loop (ImageExperiment.jl:258-268) as
         a ClassEval of one sample; the scores never leave the device before they are evaluated."""
-        h = _f64(np.asarray(h, dtype=np.float64).ravel())
+        h = _hvec(h)
         Xtest = self._xtest(Xtest)
         Nt = Xtest.shape[0]
         yi = _labels(ytest, Nt)
@@ -1863,7 +1833,7 @@ def gpnt_neglogjoint_oneshot(X, y, Z, b, theta, hyperparams, C=None, want_grad=T
     if C is None:
         C = int(y.max() - y.min() + 1)
     th = _f64(np.asarray(theta, dtype=np.float64).reshape((n, C), order="F"))
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    h = _hvec(hyperparams)
     val = _lib.C.c_double()
     grad = np.empty(n * C + h.size)
     check(lib().gpt_gpnt_neglogjoint(_ptr(X), N, D, _ptr(y), C, _ptr(Z), _ptr(b), n, _ptr(th),
@@ -1885,7 +1855,7 @@ def gpnt_joint_hmc_oneshot(X, y, Z, b, theta, hyperparams, eps, L, nsamples, see
     if C is None:
         C = int(y.max() - y.min() + 1)
     th = np.array(np.asarray(theta, dtype=np.float64).reshape((n, C), order="F"), order="F", copy=True)
-    h = _f64(np.asarray(hyperparams, dtype=np.float64).ravel())
+    h = _hvec(hyperparams)
     burnin, nsamples, thin = int(burnin), int(nsamples), int(thin)
     ntrans = max(burnin, 0) + max(nsamples, 0)
     res = HMCResult()

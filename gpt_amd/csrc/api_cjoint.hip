@@ -6,7 +6,7 @@
 #include <memory>
 #include <vector>
 
-#include "host_util.h"
+#include "gp_handle.h"
 
 using namespace gpt;
 
@@ -18,11 +18,11 @@ struct gpt_cjoint {
          *part_theta = nullptr, *part_tx = nullptr, *part_sc = nullptr, *out = nullptr;
   int32_t *y0 = nullptr, *status = nullptr;
   int64_t step = 0;                   // 0-based counter of the next Langevin step / HMC transition
-  // HMC (chmc.hip), allocated by the first call that needs it.  cache_ok: sc[0] and g_cur hold U
-  // and grad U of the resident theta at cache_hyper (compared by bits).
+  // HMC (chmc.hip), allocated by the first call that needs it.  cache: sc[0] and g_cur hold U
+  // and grad U of the resident theta at these hyper-parameters (compared by bits).
   HmcDev hmc = {};
-  bool hmc_alloc = false, cache_ok = false;
-  std::vector<double> cache_hyper;
+  bool hmc_alloc = false;
+  FactorKey cache;
   DevSet mem;
 };
 
@@ -37,14 +37,7 @@ static bool cj_dims_ok(const void* X, int64_t N, int64_t D, int64_t C, const voi
 }
 
 static bool cj_hyper_ok(const double* hyper, int64_t Lh, int64_t D) {
-  if (!hyper) { set_error("cjoint: null hyperparams"); return false; }
-  if (Lh != 2 && Lh != D + 1) { set_error("cjoint: hyperparams must have 2 or D + 1 entries"); return false; }
-  for (int64_t k = 0; k < Lh; ++k)
-    if (!(hyper[k] > 0.0) || !std::isfinite(hyper[k])) {
-      set_error("cjoint: hyperparams must be positive and finite");
-      return false;
-    }
-  return true;
+  return hyper_ok("cjoint", hyper, Lh, D, 1);
 }
 
 extern "C" int gpt_cjoint_create(const double* X, int64_t N, int64_t D, const double* y, int64_t C,
@@ -82,17 +75,11 @@ extern "C" int gpt_cjoint_create(const double* X, int64_t N, int64_t D, const do
   return GPT_OK;
 }
 
-extern "C" int gpt_cjoint_destroy(gpt_cjoint* h) {
-  if (h) {
-    (void)hipDeviceSynchronize();
-    delete h;
-  }
-  return GPT_OK;
-}
+extern "C" int gpt_cjoint_destroy(gpt_cjoint* h) { return destroy_handle(h); }
 
 extern "C" int gpt_cjoint_set_theta(gpt_cjoint* h, const double* theta) {
   if (!h || !theta) { set_error("cjoint: null handle or theta"); return GPT_ERR_BAD_DIMS; }
-  h->cache_ok = false;
+  h->cache.clear();
   GPT_HIPCHK(hipMemcpy(h->theta, theta, 8 * (size_t)h->n * h->C, hipMemcpyHostToDevice));
   return GPT_OK;
 }
@@ -114,7 +101,7 @@ static int cj_args(gpt_cjoint* h, const double* hyper, int64_t Lh, hipStream_t s
                    double* sigma_out) {
   const int D = h->D;
   double lsv[kDMax];
-  for (int k = 0; k < D; ++k) lsv[k] = hyper[Lh == 2 ? 0 : k];
+  length_scales(hyper, Lh, D, 1, lsv);
   const double sigma = hyper[Lh - 1];
   GPT_HIPCHK(hipMemcpyAsync(h->ls, lsv, 8 * (size_t)D, hipMemcpyHostToDevice, st));
   GPT_HIPCHK(hipStreamSynchronize(st));               // lsv is on this frame
@@ -154,13 +141,7 @@ extern "C" int gpt_cjoint_eval(gpt_cjoint* h, const double* hyper, int64_t Lh, c
   if (full && grad_theta)
     GPT_HIPCHK(hipMemcpy(grad_theta, h->out + 2 + D, 8 * nC, hipMemcpyDeviceToHost));
   if (full && grad_hyper) {
-    if (Lh == D + 1) {
-      for (int k = 0; k < D; ++k) grad_hyper[k] = head[2 + k];
-    } else {
-      double s = 0.0;
-      for (int k = 0; k < D; ++k) s += head[2 + k];
-      grad_hyper[0] = s;
-    }
+    fold_ls_grad(head + 2, D, Lh, 1, grad_hyper);
     grad_hyper[Lh - 1] = head[1];
   }
   return GPT_OK;
@@ -184,7 +165,7 @@ extern "C" int gpt_cjoint_langevin(gpt_cjoint* h, const double* hyper, int64_t L
   if (rc != GPT_OK) return rc;
   GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
   A.status = h->status;
-  h->cache_ok = false;
+  h->cache.clear();
   for (int64_t t = first; t < first + nsteps; ++t) {
     GPT_HIPCHK(launch_cjoint_eval(A, h->L, kCjTheta, st));
     GPT_HIPCHK(launch_cjoint_update(A, h->L, h->theta, eps, seed, (uint32_t)t, h->status, st));
@@ -237,10 +218,8 @@ static int cj_hmc_prepare(gpt_cjoint* h, const double* hyper, int64_t Lh, hipStr
   if (rc != GPT_OK) return rc;
   GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
   A->status = h->status;
-  const bool same = h->cache_ok && h->cache_hyper.size() == (size_t)Lh &&
-                    std::memcmp(h->cache_hyper.data(), hyper, 8 * (size_t)Lh) == 0;
-  if (same) return GPT_OK;
-  h->cache_ok = false;
+  if (h->cache.matches(hyper, Lh)) return GPT_OK;
+  h->cache.clear();
   const HmcDev& S = h->hmc;
   GPT_HIPCHK(launch_cjoint_eval(*A, h->L, kCjTheta, st));
   GPT_HIPCHK(launch_hmc_prime(S, h->part_theta, h->L.nblk, st));
@@ -251,8 +230,7 @@ static int cj_hmc_prepare(gpt_cjoint* h, const double* hyper, int64_t Lh, hipStr
     set_error("cjoint: theta or its joint likelihood is not finite at the start of the run");
     return GPT_ERR_NAN_THETA;
   }
-  h->cache_hyper.assign(hyper, hyper + Lh);
-  h->cache_ok = true;
+  h->cache.set(hyper, Lh);
   return GPT_OK;
 }
 
@@ -296,7 +274,7 @@ extern "C" int gpt_chmc_run(gpt_cjoint* h, const double* hyper, int64_t Lh, doub
   GPT_HIPCHK(ddh.alloc<double>(nrec));
   GPT_HIPCHK(dval.alloc<double>(nrec));
   GPT_HIPCHK(hipMemsetAsync(S.ndiv, 0, 16, st));
-  h->cache_ok = false;                                  // until the run has gone through
+  h->cache.clear();                                     // until the run has gone through
   for (int64_t i = 0; i < ntrans; ++i) {
     const uint32_t t = (uint32_t)(first + i);
     GPT_HIPCHK(launch_hmc_begin(S, true, seed, t, st));
@@ -320,7 +298,7 @@ extern "C" int gpt_chmc_run(gpt_cjoint* h, const double* hyper, int64_t Lh, doub
     if (dH_out) GPT_HIPCHK(ddh.download(dH_out, (size_t)ntrans));
     if (value_out) GPT_HIPCHK(dval.download(value_out, (size_t)ntrans));
   }
-  h->cache_ok = true;                                   // U and grad U of the kept state stand
+  h->cache.set(hyper, Lh);                              // U and grad U of the kept state stand
   return GPT_OK;
 }
 
@@ -446,8 +424,16 @@ extern "C" int gpt_cjoint_time(gpt_cjoint* h, const double* hyper, int64_t Lh, i
   return GPT_OK;
 }
 
-// One-shot host-pointer forms (create, one call, destroy).  grad_out = [vec(grad theta); grad
-// length_scale; grad sigma_RBF], n*C + Lh entries, the reference's layout.
+// One-shot host-pointer forms (create, body on the fresh handle, destroy).
+template <class Body>
+static int cj_one_shot(const double* X, int64_t N, int64_t D, const double* y, int64_t C,
+                       const double* Z, const double* b, int64_t n, Body&& body) {
+  return one_shot<gpt_cjoint>(
+      [&](gpt_cjoint** h) { return gpt_cjoint_create(X, N, D, y, C, Z, b, n, h); }, body);
+}
+
+// grad_out = [vec(grad theta); grad length_scale; grad sigma_RBF], n*C + Lh entries, the
+// reference's layout.
 extern "C" int gpt_gpnt_neglogjoint(const double* X, int64_t N, int64_t D, const double* y,
                                     int64_t C, const double* Z, const double* b, int64_t n,
                                     const double* theta, const double* hyper, int64_t Lh,
@@ -456,13 +442,10 @@ extern "C" int gpt_gpnt_neglogjoint(const double* X, int64_t N, int64_t D, const
   if (!theta || !value_out || (want_grad && !grad_out)) {
     set_error("cjoint: null theta or output"); return GPT_ERR_BAD_DIMS;
   }
-  gpt_cjoint* h = nullptr;
-  int rc = gpt_cjoint_create(X, N, D, y, C, Z, b, n, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_cjoint_eval(h, hyper, Lh, theta, want_grad ? 1 : 0, value_out, grad_out,
-                       want_grad ? grad_out + n * C : nullptr);
-  gpt_cjoint_destroy(h);
-  return rc;
+  return cj_one_shot(X, N, D, y, C, Z, b, n, [&](gpt_cjoint* h) {
+    return gpt_cjoint_eval(h, hyper, Lh, theta, want_grad ? 1 : 0, value_out, grad_out,
+                           want_grad ? grad_out + n * C : nullptr);
+  });
 }
 
 extern "C" int gpt_gpnt_joint_langevin(const double* X, int64_t N, int64_t D, const double* y,
@@ -471,14 +454,11 @@ extern "C" int gpt_gpnt_joint_langevin(const double* X, int64_t N, int64_t D, co
                                        int64_t nsteps, uint64_t seed, int64_t t0) {
   if (!cj_dims_ok(X, N, D, C, Z, b, n) || !cj_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
   if (!theta || t0 < 0) { set_error("cjoint: null theta or negative t0"); return GPT_ERR_BAD_DIMS; }
-  gpt_cjoint* h = nullptr;
-  int rc = gpt_cjoint_create(X, N, D, y, C, Z, b, n, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_cjoint_set_theta(h, theta);
-  if (rc == GPT_OK) rc = gpt_cjoint_langevin(h, hyper, Lh, eps, nsteps, seed, t0);
-  if (rc == GPT_OK) rc = gpt_cjoint_get_theta(h, theta);
-  gpt_cjoint_destroy(h);
-  return rc;
+  return cj_one_shot(X, N, D, y, C, Z, b, n, [&](gpt_cjoint* h) {
+    GPT_TRY(gpt_cjoint_set_theta(h, theta));
+    GPT_TRY(gpt_cjoint_langevin(h, hyper, Lh, eps, nsteps, seed, t0));
+    return gpt_cjoint_get_theta(h, theta);
+  });
 }
 
 extern "C" int gpt_gpnt_joint_hmc(const double* X, int64_t N, int64_t D, const double* y, int64_t C,
@@ -489,18 +469,14 @@ extern "C" int gpt_gpnt_joint_hmc(const double* X, int64_t N, int64_t D, const d
                                   double* dH_out, double* value_out, int32_t* ndivergent_out) {
   if (!cj_dims_ok(X, N, D, C, Z, b, n) || !cj_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
   if (!theta || t0 < 0) { set_error("cjoint: null theta or negative t0"); return GPT_ERR_BAD_DIMS; }
-  gpt_cjoint* h = nullptr;
-  int rc = gpt_cjoint_create(X, N, D, y, C, Z, b, n, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_cjoint_set_theta(h, theta);
-  int64_t ndiv = 0;
-  if (rc == GPT_OK)
-    rc = gpt_chmc_run(h, hyper, Lh, eps, L, burnin, nsamples, thin, seed, t0, theta_store,
-                        accept_out, dH_out, value_out, &ndiv);
-  if (rc == GPT_OK && ndivergent_out) *ndivergent_out = (int32_t)ndiv;   // at most 2^25 transitions
-  if (rc == GPT_OK) rc = gpt_cjoint_get_theta(h, theta);
-  gpt_cjoint_destroy(h);
-  return rc;
+  return cj_one_shot(X, N, D, y, C, Z, b, n, [&](gpt_cjoint* h) {
+    int64_t ndiv = 0;
+    GPT_TRY(gpt_cjoint_set_theta(h, theta));
+    GPT_TRY(gpt_chmc_run(h, hyper, Lh, eps, L, burnin, nsamples, thin, seed, t0, theta_store,
+                         accept_out, dH_out, value_out, &ndiv));
+    if (ndivergent_out) *ndivergent_out = (int32_t)ndiv;                 // at most 2^25 transitions
+    return gpt_cjoint_get_theta(h, theta);
+  });
 }
 
 // scores (Ntest, C) = featureNotensor(Xtest)'theta at hyper: no training data is needed.
@@ -511,11 +487,8 @@ extern "C" int gpt_gpnt_joint_scores(const double* Xtest, int64_t Ntest, int64_t
   if (!cj_dims_ok(Xtest, Ntest, D, C, Z, b, n) || !cj_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
   if (!theta || !scores_out) { set_error("cjoint: null theta or output"); return GPT_ERR_BAD_DIMS; }
   const std::vector<double> ones((size_t)Ntest, 1.0);          // labels are not read by the scores
-  gpt_cjoint* h = nullptr;
-  int rc = gpt_cjoint_create(Xtest, Ntest, D, ones.data(), C, Z, b, n, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_cjoint_set_theta(h, theta);
-  if (rc == GPT_OK) rc = gpt_cjoint_scores(h, hyper, Lh, Xtest, Ntest, scores_out);
-  gpt_cjoint_destroy(h);
-  return rc;
+  return cj_one_shot(Xtest, Ntest, D, ones.data(), C, Z, b, n, [&](gpt_cjoint* h) {
+    GPT_TRY(gpt_cjoint_set_theta(h, theta));
+    return gpt_cjoint_scores(h, hyper, Lh, Xtest, Ntest, scores_out);
+  });
 }

@@ -515,21 +515,18 @@ __global__ __launch_bounds__(256) void egp_pred_kernel(const double* __restrict_
 using namespace gpt;
 
 // ------------------------------------------------------------------------------ host side
+#include "gp_handle.h"
+
 constexpr int kEgpPhases = 6;        // build, Cholesky, solves, inverse, P, gradient pass
 struct gpt_egp {
   int N = 0, D = 0;
   double *X = nullptr, *y = nullptr, *A = nullptr, *W = nullptr, *P = nullptr, *r = nullptr,
-         *z = nullptr, *alpha = nullptr, *part = nullptr, *sums = nullptr, *scal = nullptr,
-         *Ks = nullptr;
-  size_t ks_cols = 0;
+         *z = nullptr, *alpha = nullptr, *part = nullptr, *sums = nullptr, *scal = nullptr;
   int32_t* status = nullptr;
-  bool have_factor = false;            // A holds L and alpha the weights of hyper `last`
-  double last[kDMax + 2];
-  int64_t last_Lh = 0;
+  FactorKey factor;                    // A holds L and alpha the weights of these hyper-parameters
   DevSet mem;
-  DevMem ks_mem;                       // Ks: regrown when a call asks for more columns
-  std::vector<hipEvent_t> ev;
-  ~gpt_egp() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+  GrowBlock Ks;                        // regrown when a call asks for more columns
+  PhaseMarks marks;                    // gpt_egp_eval_timed's
 };
 
 static bool egp_dims_ok(const void* X, int64_t N, int64_t D, const void* y) {
@@ -540,25 +537,7 @@ static bool egp_dims_ok(const void* X, int64_t N, int64_t D, const void* y) {
 }
 
 static bool egp_hyper_ok(const double* hyper, int64_t Lh, int64_t D) {
-  if (!hyper) { set_error("exact GP: null hyperparams"); return false; }
-  if (Lh != 3 && Lh != D + 2) {
-    set_error("exact GP: hyperparams must have 3 or D + 2 entries"); return false;
-  }
-  for (int64_t k = 0; k < Lh; ++k)
-    if (!(hyper[k] > 0.0) || !std::isfinite(hyper[k])) {
-      set_error("exact GP: hyperparams must be positive and finite");
-      return false;
-    }
-  return true;
-}
-
-static bool egp_test_ok(const void* Xtest, int64_t Ntest, const void* ytest, int64_t chunk,
-                        const void* fmu, const void* fs2, const void* lp) {
-  if (!Xtest || !fmu || !fs2) { set_error("exact GP: null test input or output"); return false; }
-  if (lp && !ytest) { set_error("exact GP: lp needs ytest"); return false; }
-  if (Ntest < 1 || Ntest > (1LL << 31) - 1) { set_error("exact GP: Ntest must be in 1..2^31-1"); return false; }
-  if (chunk < 0) { set_error("exact GP: chunk must be >= 0"); return false; }
-  return true;
+  return hyper_ok("exact GP", hyper, Lh, D, 2);
 }
 
 extern "C" int gpt_egp_create(const double* X, int64_t N, int64_t D, const double* y,
@@ -584,17 +563,19 @@ extern "C" int gpt_egp_create(const double* X, int64_t N, int64_t D, const doubl
   return GPT_OK;
 }
 
-extern "C" int gpt_egp_destroy(gpt_egp* h) {
-  if (h) {
-    (void)hipDeviceSynchronize();
-    delete h;
-  }
-  return GPT_OK;
+extern "C" int gpt_egp_destroy(gpt_egp* h) { return destroy_handle(h); }
+
+// The one-shot forms: create, body on the fresh handle, destroy.
+template <class Body>
+static int egp_one_shot(const double* X, int64_t N, int64_t D, const double* y, Body&& body) {
+  return one_shot<gpt_egp>([&](gpt_egp** h) { return gpt_egp_create(X, N, D, y, h); }, body);
 }
 
 static EgpHyp egp_hyp(const double* hyper, int64_t Lh, int D) {
   EgpHyp H;
-  for (int k = 0; k < kDMax; ++k) H.invl[k] = k < D ? 1.0 / hyper[Lh == D + 2 ? k : 0] : 0.0;
+  double ls[kDMax];
+  length_scales(hyper, Lh, D, 2, ls);
+  for (int k = 0; k < kDMax; ++k) H.invl[k] = k < D ? 1.0 / ls[k] : 0.0;
   H.sig2 = hyper[Lh - 2] * hyper[Lh - 2];
   H.s2 = hyper[Lh - 1];
   H.D = D;
@@ -634,10 +615,6 @@ static hipError_t egp_chol(double* A, int N, int32_t* status, hipStream_t st) {
   return hipGetLastError();
 }
 
-static void egp_nan_fill(double* p, int64_t n) {
-  if (p) for (int64_t k = 0; k < n; ++k) p[k] = std::nan("");
-}
-
 static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t want_grad,
                          double* nlml, double* grad, double* alpha_out, double* phase_ms) {
   if (!h || !nlml || (want_grad && !grad)) {
@@ -647,20 +624,13 @@ static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t wa
   const int N = h->N, D = h->D;
   const EgpHyp H = egp_hyp(hyper, Lh, D);
   hipStream_t st = nullptr;
-  h->have_factor = false;
+  h->factor.clear();
   if (want_grad && !h->W) {
     GPT_HIPCHK(h->mem.alloc(&h->W, (size_t)N * N));
     GPT_HIPCHK(h->mem.alloc(&h->P, (size_t)N * N));
   }
-  if (phase_ms && h->ev.empty()) {
-    h->ev.resize(kEgpPhases + 1);
-    for (auto& e : h->ev) GPT_HIPCHK(hipEventCreate(&e));
-  }
-  int marks = 0;
-  auto mark = [&]() {
-    if (phase_ms) (void)hipEventRecord(h->ev[marks], st);
-    ++marks;
-  };
+  GPT_HIPCHK(h->marks.begin(phase_ms != nullptr, kEgpPhases));
+  auto mark = [&]() { h->marks.mark(st); };
   const int nblk = (N + 63) / 64;
   const long long npair = (long long)nblk * (nblk + 1) / 2;
   GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
@@ -715,42 +685,35 @@ static int egp_eval_impl(gpt_egp* h, const double* hyper, int64_t Lh, int32_t wa
   if (alpha_out) GPT_HIPCHK(hipMemcpyAsync(ah.data(), h->alpha, 8 * (size_t)N, hipMemcpyDeviceToHost, st));
   if (want_grad) GPT_HIPCHK(hipMemcpyAsync(sums, h->sums, 8 * kEgpPart, hipMemcpyDeviceToHost, st));
   GPT_HIPCHK(hipStreamSynchronize(st));
-  if (phase_ms)
-    for (int q = 0; q < kEgpPhases; ++q) {
-      float ms = 0.f;
-      GPT_HIPCHK(hipEventElapsedTime(&ms, h->ev[q], h->ev[q + 1]));
-      phase_ms[q] = ms;
-    }
+  GPT_HIPCHK(h->marks.read(phase_ms));
   if (bad) {
-    egp_nan_fill(nlml, 1);
-    if (want_grad) egp_nan_fill(grad, Lh);
-    egp_nan_fill(alpha_out, N);
+    nan_fill(nlml, 1);
+    if (want_grad) nan_fill(grad, Lh);
+    nan_fill(alpha_out, N);
     set_error("exact GP: K + signal_var*I is not positive definite (PosDefException)");
     return GPT_ERR_NOT_SPD;
   }
   *nlml = sc[0] + 0.5 * sc[1] + 0.5 * (double)N * std::log(2 * M_PI);
   if (want_grad) {
     const double sigma = hyper[Lh - 2];
-    double gl[kDMax];
-    for (int k = 0; k < D; ++k) {
-      const double l = hyper[Lh == D + 2 ? k : 0];
-      gl[k] = 0.5 * sums[1 + k] / (l * l * l);
-    }
-    if (Lh == D + 2) {
-      for (int k = 0; k < D; ++k) grad[k] = gl[k];
-    } else {
-      double s = 0.0;
-      for (int k = 0; k < D; ++k) s += gl[k];
-      grad[0] = s;
-    }
+    double ls[kDMax], gl[kDMax];
+    length_scales(hyper, Lh, D, 2, ls);
+    for (int k = 0; k < D; ++k) gl[k] = 0.5 * sums[1 + k] / (ls[k] * ls[k] * ls[k]);
+    fold_ls_grad(gl, D, Lh, 2, grad);
     grad[Lh - 2] = sums[0] / sigma;
     grad[Lh - 1] = 0.5 * sums[kDMax + 1];
   }
   if (alpha_out) std::memcpy(alpha_out, ah.data(), 8 * (size_t)N);
-  std::memcpy(h->last, hyper, 8 * (size_t)Lh);
-  h->last_Lh = Lh;
-  h->have_factor = true;
+  h->factor.set(hyper, Lh);
   return GPT_OK;
+}
+
+// The factor of hyper in A and its weights in alpha: the resident ones when they are those of
+// these bits, else an evaluation without gradient.
+static int egp_ensure_factor(gpt_egp* h, const double* hyper, int64_t Lh) {
+  if (h->factor.matches(hyper, Lh)) return GPT_OK;
+  double val = 0.0;
+  return egp_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
 }
 
 extern "C" int gpt_egp_eval(gpt_egp* h, const double* hyper, int64_t Lh, int32_t want_grad,
@@ -768,59 +731,44 @@ extern "C" int gpt_egp_predict(gpt_egp* h, const double* hyper, int64_t Lh, cons
                                int64_t Ntest, const double* ytest, int64_t chunk, double* fmu,
                                double* fs2, double* lp) {
   if (!h) { set_error("exact GP: null handle"); return GPT_ERR_BAD_DIMS; }
-  if (!egp_hyper_ok(hyper, Lh, h->D) || !egp_test_ok(Xtest, Ntest, ytest, chunk, fmu, fs2, lp))
+  if (!egp_hyper_ok(hyper, Lh, h->D) ||
+      !test_args_ok("exact GP", Xtest, Ntest, ytest, chunk, fmu, fs2, lp))
     return GPT_ERR_BAD_DIMS;
   const int N = h->N, D = h->D;
-  if (!(h->have_factor && h->last_Lh == Lh && std::memcmp(h->last, hyper, 8 * (size_t)Lh) == 0)) {
-    double val = 0.0;
-    const int rc = egp_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
-    if (rc != GPT_OK) {
-      egp_nan_fill(fmu, Ntest);
-      egp_nan_fill(fs2, Ntest);
-      egp_nan_fill(lp, Ntest);
-      return rc;
-    }
+  const int rc = egp_ensure_factor(h, hyper, Lh);
+  if (rc != GPT_OK) {
+    nan_fill(fmu, Ntest);
+    nan_fill(fs2, Ntest);
+    nan_fill(lp, Ntest);
+    return rc;
   }
   const EgpHyp H = egp_hyp(hyper, Lh, D);
   hipStream_t st = nullptr;
   const int64_t want = chunk == 0 ? kEgpChunk : std::min<int64_t>(chunk, kEgpChunkMax);
   const int cw = (int)std::min<int64_t>(want, Ntest);
-  if (h->ks_cols < (size_t)cw) {
-    h->Ks = nullptr;
-    h->ks_cols = 0;
-    h->ks_mem = DevMem();                // the old block is freed before the larger one is taken
-    GPT_HIPCHK(h->ks_mem.alloc<double>((size_t)N * cw));
-    h->Ks = h->ks_mem.as<double>();
-    h->ks_cols = (size_t)cw;
-  }
+  GPT_HIPCHK(h->Ks.reserve((size_t)N, (size_t)cw));
   // test inputs, targets and the three outputs on the device for the call
-  DevSet tmp;
-  double *dX = nullptr, *dy = nullptr, *dmu = nullptr, *dv = nullptr, *dlp = nullptr;
-  GPT_HIPCHK(tmp.alloc(&dX, (size_t)Ntest * D));
-  GPT_HIPCHK(tmp.alloc(&dmu, (size_t)Ntest));
-  GPT_HIPCHK(tmp.alloc(&dv, (size_t)Ntest));
+  DevMem xmem;
+  TestBuffers T;
+  GPT_HIPCHK(xmem.alloc<double>((size_t)Ntest * D));
+  GPT_HIPCHK(T.alloc((size_t)Ntest, lp != nullptr));
+  double *dX = xmem.as<double>(), *dy = T.y, *dmu = T.mu, *dv = T.v, *dlp = T.lp;
   GPT_HIPCHK(hipMemcpyAsync(dX, Xtest, 8 * (size_t)Ntest * D, hipMemcpyHostToDevice, st));
-  if (lp) {
-    GPT_HIPCHK(tmp.alloc(&dy, (size_t)Ntest));
-    GPT_HIPCHK(tmp.alloc(&dlp, (size_t)Ntest));
-    GPT_HIPCHK(hipMemcpyAsync(dy, ytest, 8 * (size_t)Ntest, hipMemcpyHostToDevice, st));
-  }
+  if (lp) GPT_HIPCHK(hipMemcpyAsync(dy, ytest, 8 * (size_t)Ntest, hipMemcpyHostToDevice, st));
   for (int64_t c0 = 0; c0 < Ntest; c0 += cw) {
     const int nc = (int)std::min<int64_t>(cw, Ntest - c0);
     hipLaunchKernelGGL(egp_cross_kernel, dim3((N + 63) / 64, (nc + 15) / 16), dim3(256), 0, st,
-                       h->X, N, dX, (long long)Ntest, (long long)c0, nc, H, h->Ks);
-    hipLaunchKernelGGL(egp_pred_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->Ks, N, nc,
+                       h->X, N, dX, (long long)Ntest, (long long)c0, nc, H, h->Ks.p);
+    hipLaunchKernelGGL(egp_pred_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->Ks.p, N, nc,
                        h->alpha, 0, H.sig2, H.s2, (const double*)nullptr, dmu + c0, dv + c0,
                        (double*)nullptr);
-    GPT_HIPCHK(egp_trsm(h->A, N, h->Ks, nc, false, st));
-    hipLaunchKernelGGL(egp_pred_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->Ks, N, nc,
+    GPT_HIPCHK(egp_trsm(h->A, N, h->Ks.p, nc, false, st));
+    hipLaunchKernelGGL(egp_pred_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->Ks.p, N, nc,
                        h->alpha, 1, H.sig2, H.s2, lp ? dy + c0 : (const double*)nullptr, dmu + c0,
                        dv + c0, lp ? dlp + c0 : (double*)nullptr);
     GPT_HIPCHK(hipGetLastError());
   }
-  GPT_HIPCHK(hipMemcpyAsync(fmu, dmu, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
-  GPT_HIPCHK(hipMemcpyAsync(fs2, dv, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
-  if (lp) GPT_HIPCHK(hipMemcpyAsync(lp, dlp, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(T.download(fmu, fs2, lp, st));
   GPT_HIPCHK(hipStreamSynchronize(st));
   return GPT_OK;
 }
@@ -864,7 +812,7 @@ extern "C" int gpt_egp_draw_prior(gpt_egp* h, const double* hyper, int64_t Lh, d
   EgpHyp H = egp_hyp(hyper, Lh, h->D);
   H.s2 = jitter;                                        // GPrand adds the jitter alone
   hipStream_t st = nullptr;
-  h->have_factor = false;
+  h->factor.clear();
   DevSet tmp;
   double *dZ = nullptr, *dF = nullptr;
   const size_t NS = (size_t)N * S;
@@ -888,8 +836,8 @@ extern "C" int gpt_egp_draw_prior(gpt_egp* h, const double* hyper, int64_t Lh, d
   GPT_HIPCHK(hipStreamSynchronize(st));
   tm.read();
   if (bad) {
-    egp_nan_fill(F, (int64_t)NS);
-    egp_nan_fill(Zout, (int64_t)NS);
+    nan_fill(F, (int64_t)NS);
+    nan_fill(Zout, (int64_t)NS);
     set_error("exact GP draw: K + jitter*I is not positive definite (PosDefException)");
     return GPT_ERR_NOT_SPD;
   }
@@ -910,26 +858,16 @@ extern "C" int gpt_egp_draw_posterior(gpt_egp* h, const double* hyper, int64_t L
   const int N = h->N, D = h->D, Nt = (int)Ntest, Sd = F ? (int)S : 0;
   const size_t TS = (size_t)Nt * Sd, TT = (size_t)Nt * Nt;
   auto nan_all = [&]() {
-    egp_nan_fill(fmu, Nt);
-    egp_nan_fill(F, (int64_t)TS);
-    egp_nan_fill(cov, (int64_t)TT);
-    if (F) egp_nan_fill(Zout, (int64_t)TS);
+    nan_fill(fmu, Nt);
+    nan_fill(F, (int64_t)TS);
+    nan_fill(cov, (int64_t)TT);
+    if (F) nan_fill(Zout, (int64_t)TS);
   };
-  if (!(h->have_factor && h->last_Lh == Lh && std::memcmp(h->last, hyper, 8 * (size_t)Lh) == 0)) {
-    double val = 0.0;
-    const int rc = egp_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
-    if (rc != GPT_OK) { nan_all(); return rc; }
-  }
+  const int rc = egp_ensure_factor(h, hyper, Lh);
+  if (rc != GPT_OK) { nan_all(); return rc; }
   const EgpHyp H = egp_hyp(hyper, Lh, D);
   hipStream_t st = nullptr;
-  if (h->ks_cols < (size_t)Nt) {
-    h->Ks = nullptr;
-    h->ks_cols = 0;
-    h->ks_mem = DevMem();
-    GPT_HIPCHK(h->ks_mem.alloc<double>((size_t)N * Nt));
-    h->Ks = h->ks_mem.as<double>();
-    h->ks_cols = (size_t)Nt;
-  }
+  GPT_HIPCHK(h->Ks.reserve((size_t)N, (size_t)Nt));
   DevSet tmp;
   double *dX = nullptr, *dmu = nullptr, *dSig = nullptr, *dcov = nullptr, *dZ = nullptr,
          *dF = nullptr;
@@ -947,16 +885,16 @@ extern "C" int gpt_egp_draw_posterior(gpt_egp* h, const double* hyper, int64_t L
   if (F) GPT_HIPCHK(gpd_normals(dZ, Nt, Sd, seed, kGpdPosterior, Zin, st));
   tm.mark(0);
   hipLaunchKernelGGL(egp_cross_kernel, dim3((N + 63) / 64, (Nt + 15) / 16), dim3(256), 0, st, h->X,
-                     N, dX, (long long)Nt, 0LL, Nt, H, h->Ks);
-  hipLaunchKernelGGL(egp_pred_kernel, dim3((Nt + 3) / 4), dim3(256), 0, st, h->Ks, N, Nt, h->alpha,
+                     N, dX, (long long)Nt, 0LL, Nt, H, h->Ks.p);
+  hipLaunchKernelGGL(egp_pred_kernel, dim3((Nt + 3) / 4), dim3(256), 0, st, h->Ks.p, N, Nt, h->alpha,
                      0, H.sig2, H.s2, (const double*)nullptr, dmu, (double*)nullptr,
                      (double*)nullptr);
   GPT_HIPCHK(hipGetLastError());
   tm.mark(1);
   if (F || cov) {
-    GPT_HIPCHK(egp_trsm(h->A, N, h->Ks, Nt, false, st));
+    GPT_HIPCHK(egp_trsm(h->A, N, h->Ks.p, Nt, false, st));
     tm.mark(2);
-    GPT_HIPCHK(gpd_postcov(h->Ks, N, dX, Nt, H, jitter + (observed ? H.s2 : 0.0), dSig, dcov, st));
+    GPT_HIPCHK(gpd_postcov(h->Ks.p, N, dX, Nt, H, jitter + (observed ? H.s2 : 0.0), dSig, dcov, st));
     tm.mark(3);
   }
   if (F) {
@@ -993,12 +931,9 @@ extern "C" int gpt_gp_rand(const double* X, int64_t N, int64_t D, const double* 
     return GPT_ERR_BAD_DIMS;
   if (!F) { set_error("exact GP draw: null output"); return GPT_ERR_BAD_DIMS; }
   const std::vector<double> y((size_t)N, 0.0);
-  gpt_egp* h = nullptr;
-  int rc = gpt_egp_create(X, N, D, y.data(), &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_egp_draw_prior(h, hyper, Lh, jitter, S, seed, nullptr, F, nullptr);
-  gpt_egp_destroy(h);
-  return rc;
+  return egp_one_shot(X, N, D, y.data(), [&](gpt_egp* h) {
+    return gpt_egp_draw_prior(h, hyper, Lh, jitter, S, seed, nullptr, F, nullptr);
+  });
 }
 
 // One-shot GPpost + GPrand: create, gpt_egp_draw_posterior, destroy.
@@ -1009,13 +944,10 @@ extern "C" int gpt_gp_post_rand(const double* X, int64_t N, int64_t D, const dou
                                 double* cov) {
   if (!egp_dims_ok(X, N, D, y) || !egp_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
   if (!egp_post_ok(Xtest, Ntest, jitter, observed, S, fmu, F, cov)) return GPT_ERR_BAD_DIMS;
-  gpt_egp* h = nullptr;
-  int rc = gpt_egp_create(X, N, D, y, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_egp_draw_posterior(h, hyper, Lh, Xtest, Ntest, jitter, observed, S, seed, Zin, fmu, F,
-                              cov, nullptr);
-  gpt_egp_destroy(h);
-  return rc;
+  return egp_one_shot(X, N, D, y, [&](gpt_egp* h) {
+    return gpt_egp_draw_posterior(h, hyper, Lh, Xtest, Ntest, jitter, observed, S, seed, Zin, fmu,
+                                  F, cov, nullptr);
+  });
 }
 
 extern "C" int gpt_gp_nlogmarginal(const double* X, int64_t N, int64_t D, const double* y,
@@ -1025,24 +957,18 @@ extern "C" int gpt_gp_nlogmarginal(const double* X, int64_t N, int64_t D, const 
   if (!nlml_out || (want_grad && !grad_out)) {
     set_error("exact GP: null output"); return GPT_ERR_BAD_DIMS;
   }
-  gpt_egp* h = nullptr;
-  int rc = gpt_egp_create(X, N, D, y, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_egp_eval(h, hyper, Lh, want_grad ? 1 : 0, nlml_out, grad_out, nullptr);
-  gpt_egp_destroy(h);
-  return rc;
+  return egp_one_shot(X, N, D, y, [&](gpt_egp* h) {
+    return gpt_egp_eval(h, hyper, Lh, want_grad ? 1 : 0, nlml_out, grad_out, nullptr);
+  });
 }
 
 extern "C" int gpt_gp_predict(const double* X, int64_t N, int64_t D, const double* y,
                               const double* hyper, int64_t Lh, const double* Xtest, int64_t Ntest,
                               const double* ytest, double* fmu, double* fs2, double* lp) {
   if (!egp_dims_ok(X, N, D, y) || !egp_hyper_ok(hyper, Lh, D) ||
-      !egp_test_ok(Xtest, Ntest, ytest, 0, fmu, fs2, lp))
+      !test_args_ok("exact GP", Xtest, Ntest, ytest, 0, fmu, fs2, lp))
     return GPT_ERR_BAD_DIMS;
-  gpt_egp* h = nullptr;
-  int rc = gpt_egp_create(X, N, D, y, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_egp_predict(h, hyper, Lh, Xtest, Ntest, ytest, 0, fmu, fs2, lp);
-  gpt_egp_destroy(h);
-  return rc;
+  return egp_one_shot(X, N, D, y, [&](gpt_egp* h) {
+    return gpt_egp_predict(h, hyper, Lh, Xtest, Ntest, ytest, 0, fmu, fs2, lp);
+  });
 }

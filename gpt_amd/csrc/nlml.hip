@@ -472,6 +472,8 @@ __global__ __launch_bounds__(64) void kerr_finish_kernel(const double* __restric
 using namespace gpt;
 
 // ------------------------------------------------------------------------------ host side
+#include "gp_handle.h"
+
 struct gpt_nlml {
   int n = 0, D = 0, CB = 0, ncb = 0;
   long long N = 0;
@@ -480,17 +482,13 @@ struct gpt_nlml {
          *e = nullptr, *part = nullptr, *gl = nullptr, *scal = nullptr;
   int32_t* status = nullptr;
   bool have_features = false, have_sin = false;
-  // gpt_nlml_predict: A holds the factor of hyper-parameters `last` (have_factor), Xt its L⁻ᵀ
+  // gpt_nlml_predict: A holds the factor of the hyper-parameters of `factor`, Xt its L⁻ᵀ
   // (have_xt); phis is the test chunk's features, grown on demand
-  bool have_factor = false, have_xt = false;
-  double last[kDMax + 2] = {0};
-  int64_t last_Lh = 0;
-  double* phis = nullptr;
-  size_t phis_cols = 0;
-  DevMem phis_mem;
+  FactorKey factor;
+  bool have_xt = false;
+  GrowBlock phis;
   DevSet mem;
-  std::vector<hipEvent_t> ev;         // gpt_nlml_eval_timed's phase marks
-  ~gpt_nlml() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+  PhaseMarks marks;                   // gpt_nlml_eval_timed's
 };
 
 static bool nlml_dims_ok(const void* X, int64_t N, int64_t D, const void* y, const void* Z,
@@ -503,14 +501,7 @@ static bool nlml_dims_ok(const void* X, int64_t N, int64_t D, const void* y, con
 }
 
 static bool nlml_hyper_ok(const double* hyper, int64_t Lh, int64_t D) {
-  if (!hyper) { set_error("nlml: null hyperparams"); return false; }
-  if (Lh != 3 && Lh != D + 2) { set_error("nlml: hyperparams must have 3 or D + 2 entries"); return false; }
-  for (int64_t k = 0; k < Lh; ++k)
-    if (!(hyper[k] > 0.0) || !std::isfinite(hyper[k])) {
-      set_error("nlml: hyperparams must be positive and finite");
-      return false;
-    }
-  return true;
+  return hyper_ok("nlml", hyper, Lh, D, 2);
 }
 
 // column block of the gradient GEMM: the largest of 256 .. 32 columns that still gives 256
@@ -554,19 +545,15 @@ extern "C" int gpt_nlml_create(const double* X, int64_t N, int64_t D, const doub
   return GPT_OK;
 }
 
-extern "C" int gpt_nlml_destroy(gpt_nlml* h) {
-  if (h) {
-    (void)hipDeviceSynchronize();
-    delete h;
-  }
-  return GPT_OK;
-}
+extern "C" int gpt_nlml_destroy(gpt_nlml* h) { return destroy_handle(h); }
 
-static void nlml_nan_fill(int64_t Lh, int n, double* nlml, double* grad, double* theta) {
-  const double q = std::nan("");
-  if (nlml) *nlml = q;
-  if (grad) for (int64_t k = 0; k < Lh; ++k) grad[k] = q;
-  if (theta) for (int j = 0; j < n; ++j) theta[j] = q;
+// Xt := L⁻ᵀ of the factor in A
+static int nlml_build_xt(gpt_nlml* h, hipStream_t st) {
+  const int n = h->n;
+  GPT_HIPCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
+  GPT_HIPCHK(launch_big_lds<nlml_trinv_kernel>(kMaxLds, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
+                                               trinv_lds_bytes(n), st, h->A, n, h->Xt));
+  return GPT_OK;
 }
 
 // phase_ms (kNlmlPhases, optional): device-event times of features, SYRK, GEMV, Cholesky, the two
@@ -581,23 +568,17 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   const int n = h->n, D = h->D;
   const long long N = h->N;
   hipStream_t st = nullptr;
-  if (phase_ms && h->ev.empty()) {
-    h->ev.resize(kNlmlPhases + 1);
-    for (auto& e : h->ev) GPT_HIPCHK(hipEventCreate(&e));
-  }
-  int marks = 0;
-  auto mark = [&]() {
-    if (phase_ms) (void)hipEventRecord(h->ev[marks], st);
-    ++marks;
-  };
+  GPT_HIPCHK(h->marks.begin(phase_ms != nullptr, kNlmlPhases));
+  auto mark = [&]() { h->marks.mark(st); };
   double lsv[kDMax];
-  for (int k = 0; k < D; ++k) lsv[k] = hyper[Lh == D + 2 ? k : 0];
+  length_scales(hyper, Lh, D, 2, lsv);
   const double sigma = hyper[Lh - 2], s2 = hyper[Lh - 1];
   const double c = std::sqrt(2.0 / (double)n) * sigma;
   GPT_HIPCHK(hipMemcpyAsync(h->ls, lsv, 8 * (size_t)D, hipMemcpyHostToDevice, st));
   GPT_HIPCHK(hipMemsetAsync(h->status, 0, 16, st));
   h->have_features = h->have_sin = false;
-  h->have_factor = h->have_xt = false;
+  h->factor.clear();
+  h->have_xt = false;
   mark();
   {
     const long long total = (long long)n * N;
@@ -619,9 +600,7 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   GPT_HIPCHK(hipGetLastError());
   mark();
   if (want_grad) {
-    GPT_HIPCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
-    GPT_HIPCHK(launch_big_lds<nlml_trinv_kernel>(kMaxLds, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
-                                                 trinv_lds_bytes(n), st, h->A, n, h->Xt));
+    GPT_TRY(nlml_build_xt(h, st));
     mark();
     GPT_HIPCHK(dense_syrk(h->Xt, n, n, 1.0, 0.0, h->P, st));
     hipLaunchKernelGGL(nlml_mirror_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256),
@@ -657,16 +636,13 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   GPT_HIPCHK(hipMemcpyAsync(lh.data(), h->l, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
   if (want_grad) GPT_HIPCHK(hipMemcpyAsync(gl, h->gl, 8 * (size_t)D, hipMemcpyDeviceToHost, st));
   GPT_HIPCHK(hipStreamSynchronize(st));
-  if (phase_ms)
-    for (int q = 0; q < kNlmlPhases; ++q) {
-      float ms = 0.f;
-      GPT_HIPCHK(hipEventElapsedTime(&ms, h->ev[q], h->ev[q + 1]));
-      phase_ms[q] = ms;
-    }
+  GPT_HIPCHK(h->marks.read(phase_ms));
   h->have_features = true;
   h->have_sin = want_grad != 0;
   if (bad) {
-    nlml_nan_fill(Lh, n, nlml, want_grad ? grad : nullptr, theta_mean);
+    nan_fill(nlml, 1);
+    if (want_grad) nan_fill(grad, Lh);
+    nan_fill(theta_mean, n);
     set_error("nlml: phi*phi' + signal_var*I is not positive definite (PosDefException)");
     return GPT_ERR_NOT_SPD;
   }
@@ -675,22 +651,36 @@ static int nlml_eval_impl(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t 
   *nlml = (dN - dn) / 2 * std::log(s2) + logdet + (yy - bl) / (2 * s2) +
           dN / 2 * std::log(2 * M_PI);
   if (want_grad) {
-    if (Lh == D + 2) {
-      for (int k = 0; k < D; ++k) grad[k] = gl[k];
-    } else {
-      double s = 0.0;
-      for (int k = 0; k < D; ++k) s += gl[k];
-      grad[0] = s;
-    }
+    fold_ls_grad(gl, D, Lh, 2, grad);
     grad[Lh - 2] = (dn - s2 * trP) / sigma - ll / sigma;
     grad[Lh - 1] = (dN - dn) / (2 * s2) + trP / 2 + (bl - yy) / (2 * s2 * s2) + ll / (2 * s2);
   }
   if (theta_mean) std::memcpy(theta_mean, lh.data(), 8 * (size_t)n);
-  std::memcpy(h->last, hyper, 8 * (size_t)Lh);
-  h->last_Lh = Lh;
-  h->have_factor = true;
+  h->factor.set(hyper, Lh);
   h->have_xt = want_grad != 0;
   return GPT_OK;
+}
+
+// The factor of hyper in A: the resident one when it is that of these bits, else an evaluation
+// without gradient.
+static int nlml_ensure_factor(gpt_nlml* h, const double* hyper, int64_t Lh) {
+  if (h->factor.matches(hyper, Lh)) return GPT_OK;
+  double val = 0.0;
+  return nlml_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
+}
+
+static int nlml_ensure_xt(gpt_nlml* h, hipStream_t st) {
+  if (!h->have_xt) GPT_TRY(nlml_build_xt(h, st));
+  h->have_xt = true;
+  return GPT_OK;
+}
+
+// The one-shot forms: create, body on the fresh handle, destroy.
+template <class Body>
+static int nlml_one_shot(const double* X, int64_t N, int64_t D, const double* y, const double* Z,
+                         const double* b, int64_t n, Body&& body) {
+  return one_shot<gpt_nlml>([&](gpt_nlml** h) { return gpt_nlml_create(X, N, D, y, Z, b, n, h); },
+                            body);
 }
 
 extern "C" int gpt_nlml_eval(gpt_nlml* h, const double* hyper, int64_t Lh, int32_t want_grad,
@@ -724,12 +714,9 @@ extern "C" int gpt_gpnt_nlogmarginal(const double* X, int64_t N, int64_t D, cons
   if (!nlml_out || (want_grad && !grad_out)) {
     set_error("nlml: null output"); return GPT_ERR_BAD_DIMS;
   }
-  gpt_nlml* h = nullptr;
-  int rc = gpt_nlml_create(X, N, D, y, Z, b, n, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_nlml_eval(h, hyper, Lh, want_grad ? 1 : 0, nlml_out, grad_out, nullptr);
-  gpt_nlml_destroy(h);
-  return rc;
+  return nlml_one_shot(X, N, D, y, Z, b, n, [&](gpt_nlml* h) {
+    return gpt_nlml_eval(h, hyper, Lh, want_grad ? 1 : 0, nlml_out, grad_out, nullptr);
+  });
 }
 
 // ------------------------------------------------------------------ closed-form predictive
@@ -745,64 +732,32 @@ extern "C" int gpt_rff_last_timing(double* ms, int32_t len) {
 
 constexpr int kNlmlChunk = 4096;       // test columns per chunk when the caller passes 0, and at most
 
-static bool nlml_test_ok(const void* Xtest, int64_t Ntest, const void* ytest, int64_t chunk,
-                         const void* fmu, const void* fs2, const void* lp) {
-  if (!Xtest || !fmu || !fs2) { set_error("nlml: null test input or output"); return false; }
-  if (lp && !ytest) { set_error("nlml: lp needs ytest"); return false; }
-  if (Ntest < 1 || Ntest > (1LL << 31) - 1) { set_error("nlml: Ntest must be in 1..2^31-1"); return false; }
-  if (chunk < 0) { set_error("nlml: chunk must be >= 0"); return false; }
-  return true;
-}
-
-static void nlml_nan_fill_test(int64_t Ntest, double* fmu, double* fs2, double* lp) {
-  const double q = std::nan("");
-  for (int64_t i = 0; i < Ntest; ++i) {
-    fmu[i] = fs2[i] = q;
-    if (lp) lp[i] = q;
-  }
-}
-
 extern "C" int gpt_nlml_predict(gpt_nlml* h, const double* hyper, int64_t Lh, const double* Xtest,
                                 int64_t Ntest, const double* ytest, int64_t chunk, double* fmu,
                                 double* fs2, double* lp) {
   if (!h) { set_error("nlml: null handle"); return GPT_ERR_BAD_DIMS; }
-  if (!nlml_hyper_ok(hyper, Lh, h->D) || !nlml_test_ok(Xtest, Ntest, ytest, chunk, fmu, fs2, lp))
+  if (!nlml_hyper_ok(hyper, Lh, h->D) ||
+      !test_args_ok("nlml", Xtest, Ntest, ytest, chunk, fmu, fs2, lp))
     return GPT_ERR_BAD_DIMS;
   const int n = h->n, D = h->D;
-  if (!(h->have_factor && h->last_Lh == Lh && std::memcmp(h->last, hyper, 8 * (size_t)Lh) == 0)) {
-    double val = 0.0;
-    const int rc = nlml_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
-    if (rc != GPT_OK) {
-      nlml_nan_fill_test(Ntest, fmu, fs2, lp);
-      return rc;
-    }
+  const int rc = nlml_ensure_factor(h, hyper, Lh);
+  if (rc != GPT_OK) {
+    nan_fill(fmu, Ntest);
+    nan_fill(fs2, Ntest);
+    nan_fill(lp, Ntest);
+    return rc;
   }
   hipStream_t st = nullptr;
-  if (!h->have_xt) {
-    GPT_HIPCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
-    GPT_HIPCHK(launch_big_lds<nlml_trinv_kernel>(kMaxLds, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
-                                                 trinv_lds_bytes(n), st, h->A, n, h->Xt));
-    h->have_xt = true;
-  }
+  GPT_TRY(nlml_ensure_xt(h, st));
   const int cw = (int)std::min<int64_t>(chunk == 0 ? kNlmlChunk : std::min<int64_t>(chunk, kNlmlChunk),
                                         Ntest);
-  if (h->phis_cols < (size_t)cw) {
-    h->phis = nullptr;
-    h->phis_cols = 0;
-    h->phis_mem = DevMem();              // the old block is freed before the larger one is taken
-    GPT_HIPCHK(h->phis_mem.alloc<double>((size_t)n * cw));
-    h->phis = h->phis_mem.as<double>();
-    h->phis_cols = (size_t)cw;
-  }
-  DevSet tmp;
-  double *dX = nullptr, *dy = nullptr, *dmu = nullptr, *dv = nullptr, *dlp = nullptr;
-  GPT_HIPCHK(tmp.alloc(&dX, (size_t)cw * D));
-  GPT_HIPCHK(tmp.alloc(&dmu, (size_t)Ntest));
-  GPT_HIPCHK(tmp.alloc(&dv, (size_t)Ntest));
-  if (lp) {
-    GPT_HIPCHK(tmp.alloc(&dlp, (size_t)Ntest));
-    GPT_HIPCHK(tmp.upload(&dy, ytest, (size_t)Ntest));
-  }
+  GPT_HIPCHK(h->phis.reserve((size_t)n, (size_t)cw));
+  DevMem xmem;                                              // the chunk's rows of Xtest
+  TestBuffers T;
+  GPT_HIPCHK(xmem.alloc<double>((size_t)cw * D));
+  GPT_HIPCHK(T.alloc((size_t)Ntest, lp != nullptr));
+  if (lp) GPT_HIPCHK(hipMemcpy(T.y, ytest, 8 * (size_t)Ntest, hipMemcpyHostToDevice));
+  double *dX = xmem.as<double>(), *dy = T.y, *dmu = T.mu, *dv = T.v, *dlp = T.lp;
   const double sigma = hyper[Lh - 2], s2 = hyper[Lh - 1];
   const double c = std::sqrt(2.0 / (double)n) * sigma;      // h->ls holds the factor's length scales
   EventTimer tm(&g_rff_ms[2], st);
@@ -813,24 +768,22 @@ extern "C" int gpt_nlml_predict(gpt_nlml* h, const double* hyper, int64_t Lh, co
                                 (size_t)D, hipMemcpyHostToDevice, st));
     const long long total = (long long)n * nc;
     hipLaunchKernelGGL(nlml_feature_kernel, dim3((unsigned)std::min((total + 255) / 256, 4096LL)),
-                       dim3(256), 0, st, dX, (long long)nc, D, h->ls, c, h->Z, h->b, n, h->phis,
+                       dim3(256), 0, st, dX, (long long)nc, D, h->ls, c, h->Z, h->b, n, h->phis.p,
                        (double*)nullptr);
-    hipLaunchKernelGGL(nlml_pmean_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->phis, h->l, n,
+    hipLaunchKernelGGL(nlml_pmean_kernel, dim3((nc + 3) / 4), dim3(256), 0, st, h->phis.p, h->l, n,
                        nc, dmu + c0);
     if (n % 2 == 0)
       hipLaunchKernelGGL(nlml_pvar_kernel<true>, dim3((nc + 31) / 32), dim3(256), 0, st, h->Xt,
-                         h->phis, n, nc, s2, dmu + c0, lp ? dy + c0 : (const double*)nullptr,
+                         h->phis.p, n, nc, s2, dmu + c0, lp ? dy + c0 : (const double*)nullptr,
                          dv + c0, lp ? dlp + c0 : (double*)nullptr);
     else
       hipLaunchKernelGGL(nlml_pvar_kernel<false>, dim3((nc + 31) / 32), dim3(256), 0, st, h->Xt,
-                         h->phis, n, nc, s2, dmu + c0, lp ? dy + c0 : (const double*)nullptr,
+                         h->phis.p, n, nc, s2, dmu + c0, lp ? dy + c0 : (const double*)nullptr,
                          dv + c0, lp ? dlp + c0 : (double*)nullptr);
     GPT_HIPCHK(hipGetLastError());
   }
   tm.stop();
-  GPT_HIPCHK(hipMemcpyAsync(fmu, dmu, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
-  GPT_HIPCHK(hipMemcpyAsync(fs2, dv, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
-  if (lp) GPT_HIPCHK(hipMemcpyAsync(lp, dlp, 8 * (size_t)Ntest, hipMemcpyDeviceToHost, st));
+  GPT_HIPCHK(T.download(fmu, fs2, lp, st));
   GPT_HIPCHK(hipStreamSynchronize(st));
   return GPT_OK;
 }
@@ -844,17 +797,11 @@ extern "C" int gpt_nlml_draw_theta(gpt_nlml* h, const double* hyper, int64_t Lh,
   if (!nlml_hyper_ok(hyper, Lh, h->D)) return GPT_ERR_BAD_DIMS;
   const int n = h->n;
   const size_t nS = (size_t)n * S;
-  if (!(h->have_factor && h->last_Lh == Lh && std::memcmp(h->last, hyper, 8 * (size_t)Lh) == 0)) {
-    double val = 0.0;
-    const int rc = nlml_eval_impl(h, hyper, Lh, 0, &val, nullptr, nullptr, nullptr);
-    if (rc != GPT_OK) {
-      const double q = std::nan("");
-      for (size_t x = 0; x < nS; ++x) {
-        theta[x] = q;
-        if (Zout) Zout[x] = q;
-      }
-      return rc;
-    }
+  const int rc = nlml_ensure_factor(h, hyper, Lh);
+  if (rc != GPT_OK) {
+    nan_fill(theta, (int64_t)nS);
+    nan_fill(Zout, (int64_t)nS);
+    return rc;
   }
   hipStream_t st = nullptr;
   DevSet tmp;
@@ -864,12 +811,7 @@ extern "C" int gpt_nlml_draw_theta(gpt_nlml* h, const double* hyper, int64_t Lh,
   GpdTimer tm(st);
   GPT_HIPCHK(gpd_normals(dZ, n, (int)S, seed, kGpdTheta, Zin, st));
   tm.mark(0);
-  if (!h->have_xt) {
-    GPT_HIPCHK(hipMemsetAsync(h->Xt, 0, 8 * (size_t)n * n, st));
-    GPT_HIPCHK(launch_big_lds<nlml_trinv_kernel>(kMaxLds, dim3((n + kTiRC - 1) / kTiRC), dim3(256),
-                                                 trinv_lds_bytes(n), st, h->A, n, h->Xt));
-    h->have_xt = true;
-  }
+  GPT_TRY(nlml_ensure_xt(h, st));
   tm.mark(2);
   GPT_HIPCHK(gpd_trimm(h->Xt, (size_t)n, n, true, dZ, (int)S, h->l, std::sqrt(hyper[Lh - 1]), dT, st));
   tm.mark(5);
@@ -888,12 +830,9 @@ extern "C" int gpt_gpnt_draw_theta(const double* X, int64_t N, int64_t D, const 
   if (!nlml_dims_ok(X, N, D, y, Z, b, n) || !nlml_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
   if (S < 1 || S > kGpdSMax) { set_error("nlml draw: S must be in 1..4096"); return GPT_ERR_BAD_DIMS; }
   if (!theta) { set_error("nlml draw: null output"); return GPT_ERR_BAD_DIMS; }
-  gpt_nlml* h = nullptr;
-  int rc = gpt_nlml_create(X, N, D, y, Z, b, n, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_nlml_draw_theta(h, hyper, Lh, S, seed, Zin, theta, nullptr);
-  gpt_nlml_destroy(h);
-  return rc;
+  return nlml_one_shot(X, N, D, y, Z, b, n, [&](gpt_nlml* h) {
+    return gpt_nlml_draw_theta(h, hyper, Lh, S, seed, Zin, theta, nullptr);
+  });
 }
 
 extern "C" int gpt_gpnt_predict(const double* X, int64_t N, int64_t D, const double* y,
@@ -901,14 +840,11 @@ extern "C" int gpt_gpnt_predict(const double* X, int64_t N, int64_t D, const dou
                                 int64_t Lh, const double* Xtest, int64_t Ntest, const double* ytest,
                                 double* fmu, double* fs2, double* lp) {
   if (!nlml_dims_ok(X, N, D, y, Z, b, n) || !nlml_hyper_ok(hyper, Lh, D) ||
-      !nlml_test_ok(Xtest, Ntest, ytest, 0, fmu, fs2, lp))
+      !test_args_ok("nlml", Xtest, Ntest, ytest, 0, fmu, fs2, lp))
     return GPT_ERR_BAD_DIMS;
-  gpt_nlml* h = nullptr;
-  int rc = gpt_nlml_create(X, N, D, y, Z, b, n, &h);
-  if (rc != GPT_OK) return rc;
-  rc = gpt_nlml_predict(h, hyper, Lh, Xtest, Ntest, ytest, 0, fmu, fs2, lp);
-  gpt_nlml_destroy(h);
-  return rc;
+  return nlml_one_shot(X, N, D, y, Z, b, n, [&](gpt_nlml* h) {
+    return gpt_nlml_predict(h, hyper, Lh, Xtest, Ntest, ytest, 0, fmu, fs2, lp);
+  });
 }
 
 // ------------------------------------------------------------------ kernel approximation error
@@ -928,7 +864,7 @@ extern "C" int gpt_rff_kernel_error(const double* X, int64_t N, int64_t D, const
   }
   if (!nlml_hyper_ok(hyper, Lh, D)) return GPT_ERR_BAD_DIMS;
   double lsv[kDMax];
-  for (int k = 0; k < D; ++k) lsv[k] = hyper[Lh == D + 2 ? k : 0];
+  length_scales(hyper, Lh, (int)D, 2, lsv);
   const double sigma = hyper[Lh - 2];
   const long long nb = (N + kKerrTile - 1) / kKerrTile, ntiles = nb * (nb + 1) / 2;
   DevSet mem;

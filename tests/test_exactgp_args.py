@@ -54,8 +54,22 @@ def _create(p, n=N, d=D, **null):
     return rc
 
 
+def _fails(rc, text):
+    from gpt_amd import _lib
+    assert rc == _lib.GPT_ERR_BAD_DIMS, rc
+    with pytest.raises(_lib.GPTError) as ei:
+        _lib.check(rc)
+    assert ei.value.code == _lib.GPT_ERR_BAD_DIMS
+    assert text in str(ei.value), (text, str(ei.value))
+
+
 BAD_DIMS = [dict(n=16385), dict(n=0), dict(d=17), dict(d=0), dict(X=True), dict(y=True)]
+BAD_DIMS_TEXT = ["exact GP: N must be in 1..16384"] * 2 + ["exact GP: D must be in 1..16"] * 2 + \
+                ["exact GP: null input array"] * 2
 BAD_HYPER = [dict(lh=4), dict(lh=2), dict(lh=D + 3), dict(h=True)]
+BAD_HYPER_TEXT = ["exact GP: hyperparams must have 3 or D + 2 entries"] * 3 + \
+                 ["exact GP: null hyperparams"]
+BAD_VALUE_TEXT = "exact GP: hyperparams must be positive and finite"
 
 
 @pytest.mark.parametrize("call", [_nlogmarginal, _predict, _create],
@@ -68,6 +82,7 @@ def test_bad_dimensions_fail_without_a_device(call, bad):
     with pytest.raises(_lib.GPTError) as ei:
         _lib.check(rc)
     assert ei.value.code == _lib.GPT_ERR_BAD_DIMS
+    _fails(call(_problem(), **bad), BAD_DIMS_TEXT[BAD_DIMS.index(bad)])
 
 
 @pytest.mark.parametrize("call", [_nlogmarginal, _predict], ids=["nlogmarginal", "predict"])
@@ -75,6 +90,7 @@ def test_bad_dimensions_fail_without_a_device(call, bad):
 def test_bad_hyper_vector_fails_without_a_device(call, bad):
     from gpt_amd import _lib
     assert call(_problem(), **bad) == _lib.GPT_ERR_BAD_DIMS
+    _fails(call(_problem(), **bad), BAD_HYPER_TEXT[BAD_HYPER.index(bad)])
 
 
 @pytest.mark.parametrize("call", [_nlogmarginal, _predict], ids=["nlogmarginal", "predict"])
@@ -85,8 +101,10 @@ def test_bad_hyper_values_fail_without_a_device(call, value, k):
     p = _problem()
     p["h"][k] = value
     assert call(p) == _lib.GPT_ERR_BAD_DIMS
+    _fails(call(p), BAD_VALUE_TEXT)
     p["h"] = np.array([1.0, value, 0.04]) if k == 1 else p["h"]
     assert call(p, lh=p["h"].size) == _lib.GPT_ERR_BAD_DIMS
+    _fails(call(p, lh=p["h"].size), BAD_VALUE_TEXT)
 
 
 def test_null_outputs_and_handles_fail_without_a_device():
@@ -109,6 +127,23 @@ def test_null_outputs_and_handles_fail_without_a_device():
                                p["fmu"].ctypes.data_as(P), p["fs2"].ctypes.data_as(P),
                                None) == _lib.GPT_ERR_BAD_DIMS
     assert lib.gpt_egp_destroy(None) == _lib.GPT_OK
+    _fails(_nlogmarginal(p, val=True), "exact GP: null output")
+    _fails(_nlogmarginal(p, grad=True), "exact GP: null output")
+    for name in ("Xt", "fmu", "fs2"):
+        _fails(_predict(p, **{name: True}), "exact GP: null test input or output")
+    _fails(_predict(p, yt=True), "exact GP: lp needs ytest")
+    _fails(_predict(p, nt=0), "exact GP: Ntest must be in 1..2^31-1")
+    _fails(lib.gpt_egp_create(p["X"].ctypes.data_as(P), N, D, p["y"].ctypes.data_as(P), None),
+           "exact GP: null handle pointer")
+    _fails(lib.gpt_egp_eval(None, h, D + 2, 0, p["val"].ctypes.data_as(P), None, None),
+           "exact GP: null handle or output")
+    _fails(lib.gpt_egp_eval_timed(None, h, D + 2, 0, p["val"].ctypes.data_as(P), None, None),
+           "exact GP: null phase_ms")
+    _fails(lib.gpt_egp_eval_timed(None, h, D + 2, 0, p["val"].ctypes.data_as(P), None,
+                                  p["grad"].ctypes.data_as(P)), "exact GP: null handle or output")
+    _fails(lib.gpt_egp_predict(None, h, D + 2, p["Xt"].ctypes.data_as(P), NT, None, 0,
+                               p["fmu"].ctypes.data_as(P), p["fs2"].ctypes.data_as(P), None),
+           "exact GP: null handle")
 
 
 def test_python_wrappers_raise_without_a_device():
