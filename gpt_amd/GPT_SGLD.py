@@ -494,12 +494,8 @@ def pred_mean_x(w_store, U_store, I, Xtest, ytest, length_scale, sigma_RBF, phi_
     n·D·Ntest phitest array; same doubles as ``feature(Xtest, length_scale, sigma_RBF,
     phi_scale, Z, b)``).  Returns (meanfhat, rmse, per-sample rmse) — the last is the
     ``testRMSE`` curve of kin40kExperiment.jl:78-83 when the samples are the epoch ends."""
-    X = _f64(Xtest)
+    X, ls, Z, b, n = _tensor_inputs(Xtest, length_scale, Z, b)
     Nt, D = X.shape
-    Z = _f64(Z)
-    n = Z.shape[0]
-    b = _f64(np.asarray(b, dtype=np.float64).reshape((n, D), order="F"))
-    ls = _f64(np.atleast_1d(length_scale))
     w_store = _f64(w_store)
     U_store = _f64(U_store)
     Q, S = w_store.shape
@@ -596,6 +592,24 @@ def GPNT_SGLD_chains(phi, y, signal_vars, sigma_thetas, m, eps_thetas, decay_rat
     return out, status
 
 
+def _targets(ytest, Nt):
+    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
+    if yt.size != Nt:
+        raise ValueError("ytest must have one target per test row")
+    return yt
+
+
+def _tensor_inputs(X, length_scale, Z, b):
+    """X (N, D), the length scale, Z (n, D) and b (n, D) of the tensor model's features, as the
+    *_x prediction entries take them; shapes are left to the entries' own checks."""
+    X = _f64(X)
+    _, D = X.shape
+    Z = _f64(Z)
+    n = Z.shape[0]
+    b = _f64(np.asarray(b, dtype=np.float64).reshape((n, D), order="F"))
+    return X, _f64(np.atleast_1d(length_scale)), Z, b, n
+
+
 def _notensor_inputs(X, length_scale, Z, b):
     X = _f64(X)
     if X.ndim != 2:
@@ -667,9 +681,7 @@ def _reg_samples(theta_store, cols, n, ytest, Nt, window):
     if theta.shape[0] != n:
         raise ValueError("theta_store and the test features disagree on n")
     T = theta.shape[1]
-    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
-    if yt.size != Nt:
-        raise ValueError("ytest must have one target per test row")
+    yt = _targets(ytest, Nt)
     first, last = _window(window, T)
     if not 0 <= first < last <= T:
         raise ValueError("the window must satisfy 0 <= first < last <= %d" % T)
@@ -783,9 +795,7 @@ def predictive(scores, ytest, signal_var, window=None, scale=1.0):
     if F.ndim != 2:
         raise ValueError("scores must be (Ntest, T)")
     Nt, T = F.shape
-    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
-    if yt.size != Nt:
-        raise ValueError("ytest must have one target per test row")
+    yt = _targets(ytest, Nt)
     first, last = _window(window, T)
     return _predictive_call(lib().gpt_predictive,
                             [_ptr(F), _ptr(yt), Nt, T, first, last, float(signal_var)], Nt, T,
@@ -821,9 +831,7 @@ def pred_predictive(w_store, U_store, I, phitest, ytest, signal_var, cols=None, 
     phitest = _f64(phitest)
     n, D, Nt = phitest.shape
     w, U, I, r, Q, S = _tensor_samples(w_store, U_store, I, cols, n, D)
-    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
-    if yt.size != Nt:
-        raise ValueError("ytest must have one target per test row")
+    yt = _targets(ytest, Nt)
     first, last = _window(window, S)
     return _predictive_call(lib().gpt_pred_predictive,
                             [_ptr(w), _ptr(U), _ptr(I, P_I32), _ptr(phitest), _ptr(yt), n, D, Nt, r,
@@ -835,16 +843,10 @@ def pred_predictive_x(w_store, U_store, I, Xtest, ytest, length_scale, sigma_RBF
                       signal_var, cols=None, window=None, scale=1.0):
     """pred_predictive with the test features formed on the device from Xtest, as pred_mean_x
     (the same doubles as ``feature(Xtest, length_scale, sigma_RBF, phi_scale, Z, b)``)."""
-    X = _f64(Xtest)
+    X, ls, Z, b, n = _tensor_inputs(Xtest, length_scale, Z, b)
     Nt, D = X.shape
-    Z = _f64(Z)
-    n = Z.shape[0]
-    b = _f64(np.asarray(b, dtype=np.float64).reshape((n, D), order="F"))
-    ls = _f64(np.atleast_1d(length_scale))
     w, U, I, r, Q, S = _tensor_samples(w_store, U_store, I, cols, n, D)
-    yt = _f64(np.asarray(ytest, dtype=np.float64).ravel())
-    if yt.size != Nt:
-        raise ValueError("ytest must have one target per test row")
+    yt = _targets(ytest, Nt)
     first, last = _window(window, S)
     return _predictive_call(lib().gpt_pred_predictive_x,
                             [_ptr(w), _ptr(U), _ptr(I, P_I32), _ptr(X), _ptr(yt), Nt, D, _ptr(ls),

@@ -6,7 +6,7 @@
 #include <memory>
 #include <vector>
 
-#include "host_util.h"
+#include "eval_frame.h"
 
 using namespace gpt;
 
@@ -87,9 +87,6 @@ extern "C" int gpt_sgld_classification(const gpt_sgld_config* cfg, const double*
 // [0] the sampler's launches, [1] the scores (nt_scores_kernel or the stacked prediction),
 // [2] the evaluation kernels.
 static thread_local double g_cls_ms[3] = {0.0, 0.0, 0.0};
-struct ClsTimer : EventTimer {
-  ClsTimer(int slot, hipStream_t st_) : EventTimer(&g_cls_ms[slot], st_) {}
-};
 extern "C" int gpt_class_last_timing(double* ms_out) {
   if (!ms_out) { set_error("gpt_class_last_timing: null argument"); return GPT_ERR_BAD_DIMS; }
   for (int k = 0; k < 3; ++k) ms_out[k] = g_cls_ms[k];
@@ -179,7 +176,7 @@ static int class_eval_core(const double* scores, const int32_t* y, int64_t Ntest
     GPT_HIPCHK(dms.alloc<double>((size_t)Ntest * C));
     mean_scores = dms.as<double>();
   }
-  ClsTimer tm(2, st);
+  EventTimer tm(&g_cls_ms[2], st);
   hipError_t e = launch_class_eval(scores, y, Ntest, (int)C, (int)T, dpn.as<double>(),
                                    dpm.as<int32_t>(), prop_missed, mean_nlp, nullptr, nullptr, st);
   if (e != hipSuccess) return hip_fail(e, "class_eval kernel");
@@ -200,10 +197,7 @@ static bool valid_class_eval(const void* scores, const void* ytest, int64_t Ntes
   if (Ntest < 1 || C < 1 || T < 1 || C > (1 << 20) || T > (1 << 24) || Ntest > (1LL << 40)) {
     set_error("class_eval: bad dimensions"); return false;
   }
-  if (avg_first < 0 || avg_last > T || avg_first >= avg_last) {
-    set_error("class_eval: the window must satisfy 0 <= avg_first < avg_last <= T"); return false;
-  }
-  return true;
+  return window_ok("class_eval", "avg_", avg_first, avg_last, T);
 }
 
 static bool valid_labels(const int32_t* y, int64_t Ntest, int64_t C) {
@@ -230,11 +224,12 @@ extern "C" int gpt_class_eval_dev(const double* scores_dev, const int32_t* ytest
                          (hipStream_t)hip_stream);
 }
 
-// The evaluation of device scores into host outputs (ytest already checked).
+// The evaluation of device scores (Ntest, C, T) into host outputs (ytest already checked); the
+// scores themselves come back too when asked for.
 static int class_eval_to_host(const double* dscores, const int32_t* ytest, int64_t Ntest, int64_t C,
                               int64_t T, int64_t avg_first, int64_t avg_last, double* prop_missed,
                               double* mean_nlp, double* avg, double* mean_scores,
-                              int32_t* prediction, double* nlp) {
+                              int32_t* prediction, double* nlp, double* scores_out) {
   DevMem dy, dpm, dnl, davg, dms, dpr, dnp;
   GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
   GPT_HIPCHK(dpm.alloc<double>((size_t)T));
@@ -252,6 +247,8 @@ static int class_eval_to_host(const double* dscores, const int32_t* ytest, int64
   if (mean_scores) GPT_HIPCHK(dms.download(mean_scores, (size_t)Ntest * C));
   if (prediction) GPT_HIPCHK(dpr.download(prediction, (size_t)Ntest));
   if (nlp) GPT_HIPCHK(dnp.download(nlp, (size_t)Ntest));
+  if (scores_out)
+    GPT_HIPCHK(hipMemcpy(scores_out, dscores, 8 * (size_t)Ntest * C * T, hipMemcpyDeviceToHost));
   return GPT_OK;
 }
 
@@ -266,7 +263,7 @@ extern "C" int gpt_class_eval(const double* scores, const int32_t* ytest, int64_
   GPT_HIPCHK(ds.upload(scores, (size_t)Ntest * C * T));
   return class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
                             prop_missed_out, mean_nlp_out, avg_out, mean_scores_out, prediction_out,
-                            nlp_out);
+                            nlp_out, nullptr);
 }
 
 // ImageNoTensorExperiment.jl:50-75 on T stored full-theta samples: scores = phitestᵀ·theta for
@@ -283,28 +280,23 @@ extern "C" int gpt_gpnt_pred_class(const double* theta, const double* phitest, c
                         mean_nlp_out, avg_out) || !valid_labels(ytest, Ntest, C))
     return GPT_ERR_BAD_DIMS;
   if ((C * T + 63) / 64 > 65535) { set_error("gpt_gpnt_pred_class: C*T too large"); return GPT_ERR_BAD_DIMS; }
-  DevMem dth, dphi, ds;
-  const size_t nscores = (size_t)Ntest * C * T;
-  GPT_HIPCHK(dth.upload(theta, (size_t)n * C * T));
+  ThetaScores sc{n, Ntest, C * T};
+  DevMem dphi;
+  GPT_TRY(sc.stage(theta));
   GPT_HIPCHK(dphi.upload(phitest, (size_t)n * Ntest));
-  GPT_HIPCHK(ds.alloc<double>(nscores));
   {
-    ClsTimer tm(1, nullptr);
-    hipError_t e = launch_nt_scores(dphi.as<double>(), dth.as<double>(), (int)n, Ntest, C * T,
-                                    ds.as<double>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "nt_scores kernel");
+    EventTimer tm(&g_cls_ms[1], nullptr);
+    GPT_TRY(sc.launch(dphi.as<double>()));
     tm.stop();
   }
-  GPT_TRY(class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
-                             prop_missed_out, mean_nlp_out, avg_out, mean_scores_out,
-                             prediction_out, nlp_out));
-  if (scores_out) GPT_HIPCHK(ds.download(scores_out, nscores));
-  return GPT_OK;
+  return class_eval_to_host(sc.s.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
+                            prop_missed_out, mean_nlp_out, avg_out, mean_scores_out, prediction_out,
+                            nlp_out, scores_out);
 }
 
 // ImageExperiment.jl:50-72 on T stored samples of GPTclassification: w (Q, C, T) and
 // U (n, r, D, C, T) are S = C·T stacked samples in (c, t) order, so launch_pred's fhat (Ntest, S)
-// is the scores array; phitest is uploaded once.
+// (pred_store_fhat, as gpt_pred_mean's) is the scores array; phitest is uploaded once.
 extern "C" int gpt_pred_class(const double* w, const double* U, const int32_t* I,
                               const double* phitest, const int32_t* ytest, int64_t n, int64_t D,
                               int64_t Ntest, int64_t r, int64_t Q, int64_t C, int64_t T,
@@ -317,25 +309,9 @@ extern "C" int gpt_pred_class(const double* w, const double* U, const int32_t* I
                         avg_out) || !valid_labels(ytest, Ntest, C))
     return GPT_ERR_BAD_DIMS;
   if (C * T > (1LL << 30)) { set_error("gpt_pred_class: C*T too large"); return GPT_ERR_BAD_DIMS; }
-  const int64_t S = C * T;
-  std::vector<int32_t> I0;
-  if (!zero_based_I(I, Q, D, r, I0)) return GPT_ERR_BAD_DIMS;
-  DevMem dw, dU, dI, dphi, ds;
-  const size_t nscores = (size_t)Ntest * S;
-  GPT_HIPCHK(dw.upload(w, (size_t)Q * S));
-  GPT_HIPCHK(dU.upload(U, (size_t)n * r * D * S));
-  GPT_HIPCHK(dI.upload(I0.data(), I0.size()));
-  GPT_HIPCHK(dphi.upload(phitest, (size_t)n * D * Ntest));
-  GPT_HIPCHK(ds.alloc<double>(nscores));
-  {
-    ClsTimer tm(1, nullptr);
-    GPT_TRY(gpt_pred_dev(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(), n, D,
-                         Ntest, r, Q, S, ds.as<double>(), nullptr));
-    tm.stop();
-  }
-  GPT_TRY(class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
-                             prop_missed_out, mean_nlp_out, avg_out, mean_scores_out,
-                             prediction_out, nlp_out));
-  if (scores_out) GPT_HIPCHK(ds.download(scores_out, nscores));
-  return GPT_OK;
+  DevMem ds;
+  GPT_TRY(pred_store_fhat(w, U, I, phitest, n, D, Ntest, r, Q, C * T, ds, &g_cls_ms[1]));
+  return class_eval_to_host(ds.as<double>(), ytest, Ntest, C, T, avg_first, avg_last,
+                            prop_missed_out, mean_nlp_out, avg_out, mean_scores_out, prediction_out,
+                            nlp_out, scores_out);
 }

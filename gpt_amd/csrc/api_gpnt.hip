@@ -2,11 +2,10 @@
 // and the evaluation of stored samples: test RMSE per sample and of the prediction averaged over
 // a window of samples (PowerPlantNoTensorExperiment.jl:42-63).
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
 #include <vector>
 
-#include "host_util.h"
+#include "eval_frame.h"
 
 using namespace gpt;
 
@@ -103,37 +102,6 @@ extern "C" int gpt_gpnt_sgld_chains(const double* phi, const double* y, int64_t 
                           decay_rate, seeds, nchains, store_every, R, theta_store, status);
 }
 
-bool gpt::valid_feature_args(const double* ls, int64_t ls_len, int64_t D, const double* Z,
-                             const double* b) {
-  if (!ls || !Z || !b || D < 1 || D > (1 << 20)) { set_error("bad feature arguments"); return false; }
-  if (ls_len != 1 && ls_len != D) {
-    set_error("dimensions of X and length_scale do not match"); return false;
-  }
-  return true;
-}
-
-// dphi (n, rows) = featureNotensor(X, length_scale, sigma_rbf, Z, b) formed on the device: the
-// doubles gpt_feature_notensor makes, with no n x rows host array.
-int gpt::device_features(const double* X, int64_t rows, int64_t D, const double* ls,
-                         int64_t ls_len, double sigma_rbf, const double* Z, const double* b,
-                         int64_t n, DevMem& dphi) {
-  std::vector<double> lsv(D);
-  for (int64_t k = 0; k < D; ++k) lsv[k] = ls[ls_len == 1 ? 0 : k];
-  DevMem dX, dls, dZ, db;
-  GPT_HIPCHK(dX.upload(X, (size_t)rows * D));
-  GPT_HIPCHK(dls.upload(lsv.data(), lsv.size()));
-  GPT_HIPCHK(dZ.upload(Z, (size_t)n * D));
-  GPT_HIPCHK(db.upload(b, (size_t)n));
-  GPT_HIPCHK(dphi.alloc<double>((size_t)n * rows));
-  const double c = std::sqrt(2.0 / (double)n) * sigma_rbf;
-  const hipError_t e = launch_feature_notensor(dX.as<double>(), rows, (int)D, dls.as<double>(), c,
-                                               dZ.as<double>(), db.as<double>(), (int)n,
-                                               dphi.as<double>(), nullptr);
-  if (e != hipSuccess) return hip_fail(e, "feature kernel");
-  GPT_HIPCHK(hipStreamSynchronize(nullptr));                 // the inputs are freed on return
-  return GPT_OK;
-}
-
 extern "C" int gpt_gpnt_sgld_chains_x(const double* X, const double* y, int64_t N, int64_t D,
                                       const double* length_scale, int64_t ls_len, double sigma_rbf,
                                       const double* Z, const double* b, int64_t n, int64_t m,
@@ -149,8 +117,7 @@ extern "C" int gpt_gpnt_sgld_chains_x(const double* X, const double* y, int64_t 
   for (int k = 0; k < nchains; ++k) status[k] = 0;
   if (R.total == 0) return GPT_OK;
   DevMem dphi;
-  const int rc = device_features(X, N, D, length_scale, ls_len, sigma_rbf, Z, b, n, dphi);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(device_features(false, X, N, D, length_scale, ls_len, sigma_rbf, 1.0, Z, b, n, dphi));
   return gpnt_chains_core(dphi.as<double>(), y, n, N, m, signal_var, sigma_theta, eps_theta,
                           decay_rate, seeds, nchains, store_every, R, theta_store, status);
 }
@@ -165,48 +132,29 @@ static bool valid_gpnt_pred(const void* theta, const void* data, const void* yte
   if (n < 1 || Ntest < 1 || T < 1 || n > (1 << 24) || T > (1 << 22) || Ntest > (1LL << 40)) {
     set_error("gpt_gpnt_pred: bad dimensions"); return false;
   }
-  if (avg_first < 0 || avg_last > T || avg_first >= avg_last) {
-    set_error("gpt_gpnt_pred: the window must satisfy 0 <= avg_first < avg_last <= T"); return false;
-  }
-  return true;
+  return window_ok("gpt_gpnt_pred", "avg_", avg_first, avg_last, T);
 }
 
-// scores (Ntest, T) = phitestᵀ·theta on device features, then mean_sse_kernel twice: on all T
-// samples for the per-sample figures and on the window's columns for its mean and error.
+// scores (Ntest, T) = phitestᵀ·theta on device features, then the window's figures and its mean.
 static int gpnt_pred_core(const double* theta, const double* dphi, const double* ytest, int64_t n,
                           int64_t Ntest, int64_t T, int64_t avg_first, int64_t avg_last,
                           double scale, double* sample_rmse_out, double* mean_out,
                           double* rmse_out, double* scores_out) {
-  const int64_t S = avg_last - avg_first;
-  const size_t nscores = (size_t)Ntest * T;
-  DevMem dth, dy, ds, dmean, dsse, dwin;
-  GPT_HIPCHK(dth.upload(theta, (size_t)n * T));
+  DevMem dy;
+  ThetaScores sc{n, Ntest, T};
+  WindowRmse ev{Ntest, T, avg_first, avg_last - avg_first};
+  GPT_TRY(sc.stage(theta));
   GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
-  GPT_HIPCHK(ds.alloc<double>(nscores));
-  GPT_HIPCHK(dmean.alloc<double>((size_t)Ntest));
-  GPT_HIPCHK(dsse.alloc<double>((size_t)T + 1));
-  GPT_HIPCHK(dwin.alloc<double>((size_t)S + 1));
+  GPT_TRY(ev.stage(true));
   {
     EventTimer tm(&g_gpnt_ms[1], nullptr);
-    hipError_t e = launch_nt_scores(dphi, dth.as<double>(), (int)n, Ntest, T, ds.as<double>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "nt_scores kernel");
-    e = launch_mean_rmse(ds.as<double>(), dy.as<double>(), Ntest, (int)T, nullptr,
-                         dsse.as<double>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
-    e = launch_mean_rmse(ds.as<double>() + (size_t)avg_first * Ntest, dy.as<double>(), Ntest, (int)S,
-                         dmean.as<double>(), dwin.as<double>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
+    GPT_TRY(sc.launch(dphi));
+    GPT_TRY(ev.launch(sc.s.as<double>(), dy.as<double>()));
     tm.stop();
     GPT_HIPCHK(hipStreamSynchronize(nullptr));
   }
-  std::vector<double> sse((size_t)T + 1);
-  double wsse = 0.0;
-  GPT_HIPCHK(dsse.download(sse.data(), sse.size()));
-  GPT_HIPCHK(dwin.download(&wsse, 1));
-  GPT_HIPCHK(dmean.download(mean_out, (size_t)Ntest));
-  for (int64_t t = 0; t < T; ++t) sample_rmse_out[t] = scale * std::sqrt(sse[1 + t] / (double)Ntest);
-  *rmse_out = scale * std::sqrt(wsse / (double)Ntest);
-  if (scores_out) GPT_HIPCHK(ds.download(scores_out, nscores));
+  GPT_TRY(ev.fetch(scale, sample_rmse_out, rmse_out, mean_out));
+  if (scores_out) GPT_HIPCHK(sc.s.download(scores_out, (size_t)Ntest * T));
   return GPT_OK;
 }
 
@@ -234,8 +182,7 @@ extern "C" int gpt_gpnt_pred_x(const double* theta, const double* Xtest, const d
       !valid_feature_args(length_scale, ls_len, D, Z, b))
     return GPT_ERR_BAD_DIMS;
   DevMem dphi;
-  const int rc = device_features(Xtest, Ntest, D, length_scale, ls_len, sigma_rbf, Z, b, n, dphi);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(device_features(false, Xtest, Ntest, D, length_scale, ls_len, sigma_rbf, 1.0, Z, b, n, dphi));
   return gpnt_pred_core(theta, dphi.as<double>(), ytest, n, Ntest, T, avg_first, avg_last, scale,
                         sample_rmse_out, mean_out, rmse_out, scores_out);
 }

@@ -1,13 +1,30 @@
 // Features and predictions from host arrays (gpt_feature*, gpt_pred*), the device-pointer
 // prediction entries and the prediction route queries.
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <vector>
+#include <optional>
 
-#include "host_util.h"
+#include "eval_frame.h"
 
 using namespace gpt;
+
+// dphi = feature (n, D, rows) or featureNotensor (n, rows) of X formed on the device, the doubles
+// of gpt_feature*.  The inputs are freed on return, after the stream has drained.
+int gpt::device_features(bool tensor, const double* X, int64_t rows, int64_t D, const double* ls,
+                         int64_t ls_len, double sigma_rbf, double phi_scale, const double* Z,
+                         const double* b, int64_t n, DevMem& dphi) {
+  FeatureInputs in;
+  GPT_TRY(in.upload(X, rows, D, ls, ls_len, Z, b, n, tensor));
+  GPT_HIPCHK(dphi.alloc<double>((size_t)n * rows * (tensor ? D : 1)));
+  const double c = tensor ? tensor_feature_c(sigma_rbf, phi_scale, D, n)
+                          : notensor_feature_c(sigma_rbf, n);
+  const hipError_t e = (tensor ? launch_feature : launch_feature_notensor)(
+      in.X.as<double>(), rows, (int)D, in.ls.as<double>(), c, in.Z.as<double>(), in.b.as<double>(),
+      (int)n, dphi.as<double>(), nullptr);
+  if (e != hipSuccess) return hip_fail(e, "feature kernel");
+  GPT_HIPCHK(hipStreamSynchronize(nullptr));
+  return GPT_OK;
+}
 
 static int feature_common(bool tensor, const double* X, int64_t N, int64_t D, const double* ls,
                           int64_t ls_len, double sigma_rbf, double phi_scale, const double* Z,
@@ -15,30 +32,10 @@ static int feature_common(bool tensor, const double* X, int64_t N, int64_t D, co
   if (!X || !ls || !Z || !b || !phi_out || N < 1 || D < 1 || n < 1) {
     set_error("bad feature arguments"); return GPT_ERR_BAD_DIMS;
   }
-  if (ls_len != 1 && ls_len != D) {
-    set_error("dimensions of X and length_scale do not match"); return GPT_ERR_BAD_DIMS;
-  }
-  std::vector<double> lsv(D);
-  for (int64_t k = 0; k < D; ++k) lsv[k] = ls[ls_len == 1 ? 0 : k];
-  const size_t nphi = tensor ? (size_t)n * D * N : (size_t)n * N;
-  DevMem dX, dls, dZ, db, dphi;
-  GPT_HIPCHK(dX.upload(X, (size_t)N * D));
-  GPT_HIPCHK(dls.upload(lsv.data(), lsv.size()));
-  GPT_HIPCHK(dZ.upload(Z, (size_t)n * D));
-  GPT_HIPCHK(db.upload(b, tensor ? (size_t)n * D : (size_t)n));
-  GPT_HIPCHK(dphi.alloc<double>(nphi));
-  hipError_t e;
-  if (tensor) {
-    const double c = phi_scale * std::pow(sigma_rbf, 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
-    e = launch_feature(dX.as<double>(), N, (int)D, dls.as<double>(), c, dZ.as<double>(),
-                       db.as<double>(), (int)n, dphi.as<double>(), nullptr);
-  } else {
-    const double c = std::sqrt(2.0 / (double)n) * sigma_rbf;
-    e = launch_feature_notensor(dX.as<double>(), N, (int)D, dls.as<double>(), c, dZ.as<double>(),
-                                db.as<double>(), (int)n, dphi.as<double>(), nullptr);
-  }
-  if (e != hipSuccess) return hip_fail(e, "feature kernel");
-  GPT_HIPCHK(dphi.download(phi_out, nphi));
+  if (!ls_len_ok(ls_len, D)) return GPT_ERR_BAD_DIMS;
+  DevMem dphi;
+  GPT_TRY(device_features(tensor, X, N, D, ls, ls_len, sigma_rbf, phi_scale, Z, b, n, dphi));
+  GPT_HIPCHK(dphi.download(phi_out, dphi.bytes / sizeof(double)));
   return GPT_OK;
 }
 
@@ -49,9 +46,9 @@ extern "C" int gpt_feature_dev(const double* X_dev, int64_t N, int64_t D, const 
   if (!X_dev || !ls_dev || !Z_dev || !b_dev || !phi_dev || N < 1 || D < 1 || n < 1 || ls_len != D) {
     set_error("bad gpt_feature_dev arguments (ls_len must equal D)"); return GPT_ERR_BAD_DIMS;
   }
-  const double c = phi_scale * std::pow(sigma_rbf, 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
-  hipError_t e = launch_feature(X_dev, N, (int)D, ls_dev, c, Z_dev, b_dev, (int)n, phi_dev,
-                                (hipStream_t)hip_stream);
+  const double c = tensor_feature_c(sigma_rbf, phi_scale, D, n);
+  const hipError_t e = launch_feature(X_dev, N, (int)D, ls_dev, c, Z_dev, b_dev, (int)n, phi_dev,
+                                      (hipStream_t)hip_stream);
   if (e != hipSuccess) return hip_fail(e, "feature kernel");
   return GPT_OK;
 }
@@ -108,53 +105,35 @@ extern "C" int gpt_pred_dev_timed(const double* w_dev, const double* U_dev, cons
 }
 
 // fhat (Ntest, S) of S stored samples into df, from host arrays (I 1-based): the prediction of
-// gpt_pred_mean.  The uploads are freed on return, after the stream has drained.
+// gpt_pred_mean and the scores of gpt_pred_class; *ms, when given, times gpt_pred_dev alone.  The
+// uploads are freed on return, after the stream has drained.
 int gpt::pred_store_fhat(const double* w, const double* U, const int32_t* I, const double* phitest,
                          int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q, int64_t S,
-                         DevMem& df) {
+                         DevMem& df, double* ms) {
   if (!valid_pred(n, D, Ntest, r, Q) || S < 1) return GPT_ERR_BAD_DIMS;
-  std::vector<int32_t> I0;
-  if (!zero_based_I(I, Q, D, r, I0)) return GPT_ERR_BAD_DIMS;
-  DevMem dw, dU, dI, dphi;
-  GPT_HIPCHK(dw.upload(w, (size_t)Q * S));
-  GPT_HIPCHK(dU.upload(U, (size_t)n * r * D * S));
-  GPT_HIPCHK(dI.upload(I0.data(), I0.size()));
+  TensorSamples ts;
+  DevMem dphi;
+  GPT_TRY(ts.upload(w, U, I, n, D, r, Q, S));
   GPT_HIPCHK(dphi.upload(phitest, (size_t)n * D * Ntest));
   GPT_HIPCHK(df.alloc<double>((size_t)Ntest * S));
-  const int rc = gpt_pred_dev(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(),
-                              n, D, Ntest, r, Q, S, df.as<double>(), nullptr);
-  if (rc != GPT_OK) return rc;
-  GPT_HIPCHK(hipStreamSynchronize(nullptr));
-  return GPT_OK;
-}
-
-static int pred_host(const double* w, const double* U, const int32_t* I, const double* phitest,
-                     const double* ytest, int64_t n, int64_t D, int64_t Ntest, int64_t r,
-                     int64_t Q, int64_t S, double scale, double* fhat_out, double* mean_out,
-                     double* rmse_out) {
-  DevMem df, dy, dmean, dsse;
-  const int rc = pred_store_fhat(w, U, I, phitest, n, D, Ntest, r, Q, S, df);
-  if (rc != GPT_OK) return rc;
-  if (fhat_out) GPT_HIPCHK(df.download(fhat_out, (size_t)Ntest * S));
-  if (ytest) {
-    GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
-    GPT_HIPCHK(dmean.alloc<double>((size_t)Ntest));
-    GPT_HIPCHK(dsse.alloc<double>((size_t)(S + 1)));
-    hipError_t e = launch_mean_rmse(df.as<double>(), dy.as<double>(), Ntest, (int)S,
-                                    dmean.as<double>(), dsse.as<double>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
-    double sse = 0.0;
-    GPT_HIPCHK(dsse.download(&sse, 1));
-    if (mean_out) GPT_HIPCHK(dmean.download(mean_out, (size_t)Ntest));
-    if (rmse_out) *rmse_out = scale * std::sqrt(sse / (double)Ntest);
+  {
+    std::optional<EventTimer> tm;
+    if (ms) tm.emplace(ms, nullptr);
+    GPT_TRY(gpt_pred_dev(ts.w.as<double>(), ts.U.as<double>(), ts.I.as<int32_t>(), dphi.as<double>(),
+                         n, D, Ntest, r, Q, S, df.as<double>(), nullptr));
+    if (tm) tm->stop();
   }
-  GPT_HIPCHK(hipDeviceSynchronize());
+  GPT_HIPCHK(hipStreamSynchronize(nullptr));
   return GPT_OK;
 }
 
 extern "C" int gpt_pred(const double* w, const double* U, const int32_t* I, const double* phitest,
                         int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q, double* fhat_out) {
-  return pred_host(w, U, I, phitest, nullptr, n, D, Ntest, r, Q, 1, 1.0, fhat_out, nullptr, nullptr);
+  DevMem df;
+  GPT_TRY(pred_store_fhat(w, U, I, phitest, n, D, Ntest, r, Q, 1, df));
+  if (fhat_out) GPT_HIPCHK(df.download(fhat_out, (size_t)Ntest));
+  GPT_HIPCHK(hipStreamSynchronize(nullptr));   // every launch and copy of the call went to it
+  return GPT_OK;
 }
 
 extern "C" int gpt_pred_mean(const double* w_store, const double* U_store, const int32_t* I,
@@ -162,8 +141,11 @@ extern "C" int gpt_pred_mean(const double* w_store, const double* U_store, const
                              int64_t Ntest, int64_t r, int64_t Q, int64_t S, double scale,
                              double* mean_out, double* rmse_out) {
   if (!ytest) { set_error("ytest required"); return GPT_ERR_BAD_DIMS; }
-  return pred_host(w_store, U_store, I, phitest, ytest, n, D, Ntest, r, Q, S, scale, nullptr,
-                   mean_out, rmse_out);
+  DevMem df;
+  GPT_TRY(pred_store_fhat(w_store, U_store, I, phitest, n, D, Ntest, r, Q, S, df));
+  GPT_TRY(all_samples_rmse(df, ytest, Ntest, S, scale, mean_out, rmse_out, nullptr));
+  GPT_HIPCHK(hipStreamSynchronize(nullptr));   // as gpt_pred
+  return GPT_OK;
 }
 
 // fhat (Ntest, S) of S stored samples into df with the test features formed on the device from
@@ -176,26 +158,15 @@ int gpt::pred_store_fhat_x(const double* w_store, const double* U_store, const i
   if (!w_store || !U_store || !I || !Xtest || !ytest || !length_scale || !Z || !b || S < 1) {
     set_error("bad pred_mean_x arguments"); return GPT_ERR_BAD_DIMS;
   }
-  if (ls_len != 1 && ls_len != D) {
-    set_error("dimensions of X and length_scale do not match"); return GPT_ERR_BAD_DIMS;
-  }
-  if (!valid_pred(n, D, Ntest, r, Q)) return GPT_ERR_BAD_DIMS;
+  if (!ls_len_ok(ls_len, D) || !valid_pred(n, D, Ntest, r, Q)) return GPT_ERR_BAD_DIMS;
   if (pred_x_lds_bytes((int)n, (int)D, (int)r, (int)Q) > kMaxLds) {
     set_error("pred LDS too large"); return GPT_ERR_BAD_DIMS;
   }
-  std::vector<int32_t> I0;
-  if (!zero_based_I(I, Q, D, r, I0)) return GPT_ERR_BAD_DIMS;
-  std::vector<double> lsv(D);
-  for (int64_t k = 0; k < D; ++k) lsv[k] = length_scale[ls_len == 1 ? 0 : k];
-  const double c = phi_scale * std::pow(sigma_rbf, 1.0 / (double)D) * std::sqrt(2.0 / (double)n);
-  DevMem dw, dU, dI, dX, dls, dZ, db;
-  GPT_HIPCHK(dw.upload(w_store, (size_t)Q * S));
-  GPT_HIPCHK(dU.upload(U_store, (size_t)n * r * D * S));
-  GPT_HIPCHK(dI.upload(I0.data(), I0.size()));
-  GPT_HIPCHK(dX.upload(Xtest, (size_t)Ntest * D));
-  GPT_HIPCHK(dls.upload(lsv.data(), lsv.size()));
-  GPT_HIPCHK(dZ.upload(Z, (size_t)n * D));
-  GPT_HIPCHK(db.upload(b, (size_t)n * D));
+  const double c = tensor_feature_c(sigma_rbf, phi_scale, D, n);
+  TensorSamples ts;
+  FeatureInputs in;
+  GPT_TRY(ts.upload(w_store, U_store, I, n, D, r, Q, S));
+  GPT_TRY(in.upload(Xtest, Ntest, D, length_scale, ls_len, Z, b, n, true));
   GPT_HIPCHK(df.alloc<double>((size_t)Ntest * S));
   // Default: the test features are formed once on the device (feature_kernel, the same doubles
   // as gpt_feature) and every sample is predicted by the stacked-sample MFMA path, which reads
@@ -205,16 +176,16 @@ int gpt::pred_store_fhat_x(const double* w_store, const double* U_store, const i
   hipError_t e;
   DevMem dphi;
   if (pev && std::strcmp(pev, "direct") == 0) {
-    e = launch_pred_x(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dX.as<double>(),
-                      dls.as<double>(), dZ.as<double>(), db.as<double>(), c, (int)n, (int)D,
+    e = launch_pred_x(ts.w.as<double>(), ts.U.as<double>(), ts.I.as<int32_t>(), in.X.as<double>(),
+                      in.ls.as<double>(), in.Z.as<double>(), in.b.as<double>(), c, (int)n, (int)D,
                       Ntest, (int)r, (int)Q, (int)S, df.as<double>(), nullptr);
     if (e != hipSuccess) return hip_fail(e, "pred_x kernel");
   } else {
     GPT_HIPCHK(dphi.alloc<double>((size_t)n * D * Ntest));
-    e = launch_feature(dX.as<double>(), Ntest, (int)D, dls.as<double>(), c, dZ.as<double>(),
-                       db.as<double>(), (int)n, dphi.as<double>(), nullptr);
+    e = launch_feature(in.X.as<double>(), Ntest, (int)D, in.ls.as<double>(), c, in.Z.as<double>(),
+                       in.b.as<double>(), (int)n, dphi.as<double>(), nullptr);
     if (e != hipSuccess) return hip_fail(e, "feature kernel");
-    e = launch_pred(dw.as<double>(), dU.as<double>(), dI.as<int32_t>(), dphi.as<double>(), (int)n,
+    e = launch_pred(ts.w.as<double>(), ts.U.as<double>(), ts.I.as<int32_t>(), dphi.as<double>(), (int)n,
                     (int)D, Ntest, (int)r, (int)Q, (int)S, df.as<double>(), nullptr);
     if (e != hipSuccess) return hip_fail(e, "pred kernels");
   }
@@ -228,23 +199,10 @@ extern "C" int gpt_pred_mean_x(const double* w_store, const double* U_store, con
                                double phi_scale, const double* Z, const double* b, int64_t n,
                                int64_t r, int64_t Q, int64_t S, double scale, double* mean_out,
                                double* rmse_out, double* sample_rmse_out) {
-  DevMem df, dy, dmean, dsse;
-  const int rc = pred_store_fhat_x(w_store, U_store, I, Xtest, ytest, Ntest, D, length_scale, ls_len,
-                                   sigma_rbf, phi_scale, Z, b, n, r, Q, S, df);
-  if (rc != GPT_OK) return rc;
-  GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
-  GPT_HIPCHK(dmean.alloc<double>((size_t)Ntest));
-  GPT_HIPCHK(dsse.alloc<double>((size_t)(S + 1)));
-  hipError_t e = launch_mean_rmse(df.as<double>(), dy.as<double>(), Ntest, (int)S,
-                                  dmean.as<double>(), dsse.as<double>(), nullptr);
-  if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
-  std::vector<double> sse((size_t)S + 1);
-  GPT_HIPCHK(dsse.download(sse.data(), sse.size()));
-  if (mean_out) GPT_HIPCHK(dmean.download(mean_out, (size_t)Ntest));
-  if (rmse_out) *rmse_out = scale * std::sqrt(sse[0] / (double)Ntest);
-  if (sample_rmse_out)
-    for (int64_t z = 0; z < S; ++z) sample_rmse_out[z] = scale * std::sqrt(sse[1 + z] / (double)Ntest);
-  return GPT_OK;
+  DevMem df;
+  GPT_TRY(pred_store_fhat_x(w_store, U_store, I, Xtest, ytest, Ntest, D, length_scale, ls_len,
+                            sigma_rbf, phi_scale, Z, b, n, r, Q, S, df));
+  return all_samples_rmse(df, ytest, Ntest, S, scale, mean_out, rmse_out, sample_rmse_out);
 }
 
 extern "C" int gpt_pred_last_vphase(int32_t* kind) {

@@ -2,9 +2,8 @@
 // predictions, and behind the predictions of stored tensor and full-theta samples, whose fhat
 // stays on the device between the prediction and its evaluation.
 #include <cmath>
-#include <vector>
 
-#include "host_util.h"
+#include "eval_frame.h"
 
 using namespace gpt;
 
@@ -23,9 +22,7 @@ static bool valid_predictive(const void* F, const void* y, int64_t Ntest, int64_
   if (Ntest < 1 || T < 1 || T > (1 << 22) || Ntest > (1LL << 38)) {
     set_error("predictive: bad dimensions"); return false;
   }
-  if (first < 0 || last > T || first >= last) {
-    set_error("predictive: the window must satisfy 0 <= first < last <= T"); return false;
-  }
+  if (!window_ok("predictive", "", first, last, T)) return false;
   if (!std::isfinite(noise_var) || !(noise_var > 0.0)) {
     set_error("predictive: noise_var must be finite and > 0"); return false;
   }
@@ -75,39 +72,25 @@ struct PvHostOut {
   double *fmu, *fs2, *lp, *lpmix, *sums, *covered, *rmse, *sample_rmse;
 };
 
-// Device predictions dF (Ntest, T) against the host's ytest: launch_mean_rmse on all T columns
-// (the per-sample figures) and on the window's (its mean's), as gpt_gpnt_pred, when either is
-// asked for, then the evaluator on the window.
+// Device predictions dF (Ntest, T) against the host's ytest: the window's RMSE figures, as
+// gpt_gpnt_pred's, when either is asked for, then the evaluator on the window.
 static int predictive_to_host(const double* dF, const double* ytest, int64_t Ntest, int64_t T,
                               int64_t first, int64_t last, double scale, double noise_var,
                               const PvHostOut& o) {
-  const int64_t S = last - first;
-  DevMem dy, dsse, dwin, drow[4];
+  DevMem dy, drow[4];
   GPT_HIPCHK(dy.upload(ytest, (size_t)Ntest));
   if (o.rmse || o.sample_rmse) {
-    GPT_HIPCHK(dsse.alloc<double>((size_t)T + 1));
-    GPT_HIPCHK(dwin.alloc<double>((size_t)S + 1));
-    hipError_t e = launch_mean_rmse(dF, dy.as<double>(), Ntest, (int)T, nullptr, dsse.as<double>(),
-                                    nullptr);
-    if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
-    e = launch_mean_rmse(dF + (size_t)first * Ntest, dy.as<double>(), Ntest, (int)S, nullptr,
-                         dwin.as<double>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "mean/sse kernel");
-    std::vector<double> sse((size_t)T + 1);
-    double wsse = 0.0;
-    GPT_HIPCHK(dsse.download(sse.data(), sse.size()));
-    GPT_HIPCHK(dwin.download(&wsse, 1));
-    if (o.sample_rmse)
-      for (int64_t t = 0; t < T; ++t) o.sample_rmse[t] = scale * std::sqrt(sse[1 + t] / (double)Ntest);
-    if (o.rmse) *o.rmse = scale * std::sqrt(wsse / (double)Ntest);
+    WindowRmse ev{Ntest, T, first, last - first};
+    GPT_TRY(ev.stage(false));
+    GPT_TRY(ev.launch(dF, dy.as<double>()));
+    GPT_TRY(ev.fetch(scale, o.sample_rmse, o.rmse, nullptr));
   }
   double* const host[4] = {o.fmu, o.fs2, o.lp, o.lpmix};
   for (int k = 0; k < 4; ++k)
     if (host[k]) GPT_HIPCHK(drow[k].alloc<double>((size_t)Ntest));
-  const int rc = predictive_core(dF, dy.as<double>(), Ntest, first, last, noise_var,
-                                 drow[0].as<double>(), drow[1].as<double>(), drow[2].as<double>(),
-                                 drow[3].as<double>(), o.sums, o.covered, nullptr);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(predictive_core(dF, dy.as<double>(), Ntest, first, last, noise_var, drow[0].as<double>(),
+                          drow[1].as<double>(), drow[2].as<double>(), drow[3].as<double>(), o.sums,
+                          o.covered, nullptr));
   for (int k = 0; k < 4; ++k)
     if (host[k]) GPT_HIPCHK(drow[k].download(host[k], (size_t)Ntest));
   return GPT_OK;
@@ -117,13 +100,13 @@ extern "C" int gpt_predictive(const double* F, const double* y, int64_t Ntest, i
                               int64_t first, int64_t last, double noise_var, double* fmu_out,
                               double* fs2_out, double* lp_out, double* lpmix_out, double* sums_out,
                               double* covered_out, double* rmse_out, double* sample_rmse_out) {
-  if (!valid_predictive(F, y, Ntest, T, first, last, noise_var, sums_out, covered_out))
+  const PvHostOut o{fmu_out, fs2_out, lp_out, lpmix_out, sums_out, covered_out, rmse_out,
+                    sample_rmse_out};
+  if (!valid_predictive(F, y, Ntest, T, first, last, noise_var, o.sums, o.covered))
     return GPT_ERR_BAD_DIMS;
   DevMem dF;
   GPT_HIPCHK(dF.upload(F, (size_t)Ntest * T));
-  return predictive_to_host(dF.as<double>(), y, Ntest, T, first, last, 1.0, noise_var,
-                            {fmu_out, fs2_out, lp_out, lpmix_out, sums_out, covered_out, rmse_out,
-                             sample_rmse_out});
+  return predictive_to_host(dF.as<double>(), y, Ntest, T, first, last, 1.0, noise_var, o);
 }
 
 // The checks the sample routes add to their prediction's own: the RMSE outputs are required.
@@ -147,8 +130,7 @@ extern "C" int gpt_pred_predictive(const double* w_store, const double* U_store,
   }
   if (!valid_route(w_store, ytest, Ntest, S, first, last, noise_var, o)) return GPT_ERR_BAD_DIMS;
   DevMem df;
-  const int rc = pred_store_fhat(w_store, U_store, I, phitest, n, D, Ntest, r, Q, S, df);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(pred_store_fhat(w_store, U_store, I, phitest, n, D, Ntest, r, Q, S, df));
   return predictive_to_host(df.as<double>(), ytest, Ntest, S, first, last, scale, noise_var, o);
 }
 
@@ -165,9 +147,8 @@ extern "C" int gpt_pred_predictive_x(const double* w_store, const double* U_stor
                     sample_rmse_out};
   if (!valid_route(w_store, ytest, Ntest, S, first, last, noise_var, o)) return GPT_ERR_BAD_DIMS;
   DevMem df;
-  const int rc = pred_store_fhat_x(w_store, U_store, I, Xtest, ytest, Ntest, D, length_scale, ls_len,
-                                   sigma_rbf, phi_scale, Z, b, n, r, Q, S, df);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(pred_store_fhat_x(w_store, U_store, I, Xtest, ytest, Ntest, D, length_scale, ls_len,
+                            sigma_rbf, phi_scale, Z, b, n, r, Q, S, df));
   return predictive_to_host(df.as<double>(), ytest, Ntest, S, first, last, scale, noise_var, o);
 }
 
@@ -176,13 +157,10 @@ extern "C" int gpt_pred_predictive_x(const double* w_store, const double* U_stor
 static int gpnt_predictive_core(const double* theta, const double* dphi, const double* ytest,
                                 int64_t n, int64_t Ntest, int64_t T, int64_t first, int64_t last,
                                 double scale, double noise_var, const PvHostOut& o) {
-  DevMem dth, ds;
-  GPT_HIPCHK(dth.upload(theta, (size_t)n * T));
-  GPT_HIPCHK(ds.alloc<double>((size_t)Ntest * T));
-  const hipError_t e = launch_nt_scores(dphi, dth.as<double>(), (int)n, Ntest, T, ds.as<double>(),
-                                        nullptr);
-  if (e != hipSuccess) return hip_fail(e, "nt_scores kernel");
-  return predictive_to_host(ds.as<double>(), ytest, Ntest, T, first, last, scale, noise_var, o);
+  ThetaScores sc{n, Ntest, T};
+  GPT_TRY(sc.stage(theta));
+  GPT_TRY(sc.launch(dphi));
+  return predictive_to_host(sc.s.as<double>(), ytest, Ntest, T, first, last, scale, noise_var, o);
 }
 
 static bool valid_gpnt_route(const void* theta, const void* data, const void* ytest, int64_t n,
@@ -222,8 +200,7 @@ extern "C" int gpt_gpnt_predictive_x(const double* theta, const double* Xtest, c
       !valid_feature_args(length_scale, ls_len, D, Z, b))
     return GPT_ERR_BAD_DIMS;
   DevMem dphi;
-  const int rc = device_features(Xtest, Ntest, D, length_scale, ls_len, sigma_rbf, Z, b, n, dphi);
-  if (rc != GPT_OK) return rc;
+  GPT_TRY(device_features(false, Xtest, Ntest, D, length_scale, ls_len, sigma_rbf, 1.0, Z, b, n, dphi));
   return gpnt_predictive_core(theta, dphi.as<double>(), ytest, n, Ntest, T, first, last, scale,
                               noise_var, o);
 }

@@ -225,20 +225,4 @@ struct ThetaChainSet {
   }
 };
 
-// The predictions of stored samples kept on the device for what evaluates them next.
-// api_pred.hip: fhat (Ntest, S) of S tensor samples from host arrays, as gpt_pred_mean and
-// gpt_pred_mean_x (its checks and routes) form them; the stream has drained on return.
-int pred_store_fhat(const double* w, const double* U, const int32_t* I, const double* phitest,
-                    int64_t n, int64_t D, int64_t Ntest, int64_t r, int64_t Q, int64_t S, DevMem& df);
-int pred_store_fhat_x(const double* w_store, const double* U_store, const int32_t* I,
-                      const double* Xtest, const double* ytest, int64_t Ntest, int64_t D,
-                      const double* length_scale, int64_t ls_len, double sigma_rbf, double phi_scale,
-                      const double* Z, const double* b, int64_t n, int64_t r, int64_t Q, int64_t S,
-                      DevMem& df);
-// api_gpnt.hip: the feature checks of the full-theta entries and their features (n, rows) formed
-// on the device from X
-bool valid_feature_args(const double* ls, int64_t ls_len, int64_t D, const double* Z, const double* b);
-int device_features(const double* X, int64_t rows, int64_t D, const double* ls, int64_t ls_len,
-                    double sigma_rbf, const double* Z, const double* b, int64_t n, DevMem& dphi);
-
 }  // namespace gpt
